@@ -16,7 +16,19 @@ all-reduced and factor shards all-gathered over RCCL: the total work is fixed
 value = users updated per second of training wall time = N_users * K / T,
 T = max over ranks of the K-epoch wall time.  sec_per_epoch = T / K.
 
-`workloads` carries the same measurement for BASELINE configs[2] (SAFER2 d=256
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what that
+figure needs: set up, warm up, time the K steps, write the outputs when
+`--dump-outputs DIR` is given, print the line.  Everything below that takes
+runs of its own -- the other workloads and the CPU baselines -- is measured
+under `--full` only.
+
+`--dump-outputs DIR` writes what the last timed Train() left in the model, the
+factor tables a caller reads back (frecsys_get_embeddings), as DIR/user_emb.npy
+and DIR/item_emb.npy (float32): every row of a table of at most DUMP_SIDE_BYTES,
+a fixed seeded sample of the rows (ascending) of a larger one.  The data and the
+init are seeded, so two builds run with the same arguments see the same inputs.
+
+`workloads` (--full) carries the same measurement for BASELINE configs[2] (SAFER2 d=256
 ML-20M-shaped, README.md:79 flags, pd=1 xi=5 use_snr=1 sampling_ratio=0.1) and
 configs[3] (iALS d=512 MSD-shaped, README.md:105), each with its own roofline,
 gather roofline and cpu_baseline, and configs[4] (SAFER2 d=1024 2M x 500K,
@@ -32,8 +44,8 @@ half-steps, vs 8 TB/s -- the north-star figure at d=512 on the MSD shape.
 loss_gather_roofline: the same bytes of the ComputeUserLoss pass (a pure
 embedding gather) / its time.
 
-cpu_baseline: a blocked, vectorised CPU restatement of the reference's Eigen
-path (oracle/cpu_baseline.c, kind "port") timing samples of both half-steps
+cpu_baseline (--full): a blocked, vectorised CPU restatement of the reference's
+Eigen path (oracle/cpu_baseline.c, kind "port") timing samples of both half-steps
 on this host's CPU share, projected to one epoch: users per epoch-second,
 like the GPU value.
 
@@ -89,23 +101,40 @@ HEADLINE = "ials_ml20m_d256"
 # on 8 GPUs (BASELINE.json), so the driver's N = 1, 2, 4, 8 sweep measures
 # them all; config 5 last (its data takes ~40 s per rank)
 DEFAULT_EXTRAS = ("safer2_ml20m_d256", "ials_msd_d512", "safer2_2m500k_d1024")
+# --dump-outputs: bytes of one factor table written whole; a larger one is
+# sampled down to this (two tables: at most 48 MB per dump)
+DUMP_SIDE_BYTES = 24 * 10 ** 6
+DUMP_SEED = 20240229
 
 
 def default_extras(world):
-    """The extra workloads of a default run at any world size: BASELINE
+    """The extra workloads of a --full run at any world size: BASELINE
     configs 3, 4 and 5 (the CPU baseline is timed at N = 1 only)."""
     del world
     return ",".join(DEFAULT_EXTRAS)
 
 
+def extras_of(args, world):
+    """The extra workloads this run measures after the headline: none
+    without --full."""
+    if not args.full:
+        return []
+    extras = args.extras if args.extras is not None else default_extras(world)
+    return [x for x in extras.split(",") if x and x != args.workload]
+
+
+def cpu_seconds_of(args):
+    """The CPU-baseline budget per workload: 0 (no baseline) without --full."""
+    return args.cpu_seconds if args.full else 0.0
+
+
 def launch_plan(args, world):
     """What a run of these arguments measures: the rank launch (None when this
     process is already a rank), the headline and the extra workloads."""
-    extras = args.extras if args.extras is not None else default_extras(world)
     return {"launch": launch_command(args) if world_from_env(args) is None else None,
-            "n_gpus": world, "workload": args.workload,
-            "extras": [x for x in extras.split(",") if x and x != args.workload],
-            "cpu_baseline": world == 1 and args.cpu_seconds > 0}
+            "n_gpus": world, "workload": args.workload, "full": args.full,
+            "extras": extras_of(args, world),
+            "cpu_baseline": world == 1 and cpu_seconds_of(args) > 0}
 
 
 def parse():
@@ -114,19 +143,29 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the extra workloads and the CPU "
+                         "baselines (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline's factor tables as the last "
+                         "step left them to DIR/user_emb.npy and DIR/item_emb.npy (float32)")
     ap.add_argument("--extras", default=None,
-                    help="comma-separated extra workloads measured after the headline "
-                         "('' for none; default: the other BASELINE configs 3, 4, 5)")
+                    help="with --full: comma-separated extra workloads measured after the "
+                         "headline ('' for none; default: the other BASELINE configs 3, 4, 5)")
     ap.add_argument("--extra-steps", type=int, default=3)
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU-baseline sample duration per workload (0 disables)")
+                    help="with --full: target CPU-baseline sample duration per workload "
+                         "(0 disables)")
     ap.add_argument("--allow-env", action="store_true",
                     help="run although FRECSYS_* variables are set (recorded in the line)")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--print-launch", action="store_true",
                     help="print the launch plan (the N-rank command bench.py would run, the "
                          "headline and extra workloads) as JSON and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.extras and not args.full:
+        ap.error("--extras names workloads for a --full run: pass --full with it")
+    return args
 
 
 def free_port():
@@ -369,7 +408,27 @@ def cpu_baseline(spec, up, uc, ip, ic, U, V, seconds, nthreads, host):
                       f"{epoch:.2f} s projected; not Eigen itself"}
 
 
-def run_workload(name, args, world, rank, local_rank, dist, data_cache, steps, warmup, cpu_s):
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: the user and item factor tables as the last Train()
+    left them, read back as a caller does (frecsys_get_embeddings; the whole
+    tables on every rank).  A table above DUMP_SIDE_BYTES is written as a
+    fixed sample of its rows: DUMP_SEED, without replacement, ascending."""
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for fname, side in (("user_emb", fh.SIDE_USER), ("item_emb", fh.SIDE_ITEM)):
+        emb = ctx.get_embeddings(side)
+        n, d = emb.shape
+        keep = max(1, DUMP_SIDE_BYTES // (d * 4))
+        if n > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED + side).choice(n, keep, replace=False))
+            emb = emb[rows]
+        np.save(os.path.join(out_dir, fname + ".npy"), np.ascontiguousarray(emb, np.float32))
+        shapes[fname] = {"rows": int(emb.shape[0]), "of": int(n), "dim": int(d)}
+    return shapes
+
+
+def run_workload(name, args, world, rank, local_rank, dist, data_cache, steps, warmup, cpu_s,
+                 dump_dir=None):
     spec = WORKLOADS[name]
     t0 = time.time()
     if spec["shape"] not in data_cache:
@@ -489,6 +548,7 @@ def run_workload(name, args, world, rank, local_rank, dist, data_cache, steps, w
     res["tagged_timeouts"] = ctx.counter("tagged_timeouts")
     if spec["model"] != "ials":
         res["mean_dual_weight"] = model.mean_weight()
+    res["dumped_outputs"] = dump_outputs(ctx, dump_dir) if dump_dir and rank == 0 else None
     if cpu_s > 0 and world == 1 and rank == 0:
         try:
             nthreads, host = host_cpu_share()
@@ -534,15 +594,13 @@ def main():
 
     data_cache = {}
     head = run_workload(args.workload, args, world, rank, local_rank, dist, data_cache,
-                        args.steps, args.warmup, args.cpu_seconds)
+                        args.steps, args.warmup, cpu_seconds_of(args), args.dump_outputs)
     extras = []
-    if args.extras is None:
-        args.extras = default_extras(world)
-    for name in [x for x in args.extras.split(",") if x and x != args.workload]:
+    for name in extras_of(args, world):
         steps = min(args.extra_steps, WORKLOADS[name].get("max_extra_steps", args.extra_steps))
         try:
             extras.append(run_workload(name, args, world, rank, local_rank, dist, data_cache,
-                                       steps, 1, args.cpu_seconds))
+                                       steps, 1, cpu_seconds_of(args)))
         except Exception as e:  # an extra never takes the headline line down with it
             log(f"[bench] {name} failed on rank {rank}: {e!r}")
             extras.append({"workload": name, "error": repr(e)})
@@ -574,6 +632,8 @@ def main():
                        "flags": spec["flags"], "parallelism": f"entity-sharded x{world}"},
             "timed_path": "frecsys_model_train -> Recommender::Train (include/frecsys_model.h)",
             "frecsys_env": env,
+            "full": args.full,
+            "dumped_outputs": head["dumped_outputs"],
         }
         for k in ("u_halfstep_solve_updates_per_s", "kernel_ms_per_epoch", "roofline", "paths",
                   "gather_roofline", "loss_gather_roofline", "cpu_baseline", "hspace_reruns",

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Config 5 (2M x 500K, d = 1024, SAFER2) measurement pass on the GPU box:
-#   1. the default bench line (headline + extras, config 5 included at N=1)
+#   1. the --full bench line (headline + extras, config 5 included at N=1)
 #   2. rocprofv3 kernel stats of config 5 alone (2 timed epochs)
 #   3. FETCH_SIZE and WRITE_SIZE passes (separate runs, no tracing domains),
 #      summarised by scripts/pmc_summary.py into <out>/latest_pmc.json
@@ -12,7 +12,7 @@ OUT=gpurun_out/$1
 W=safer2_2m500k_d1024
 mkdir -p $OUT
 if [ -z "$2" ]; then
-  timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
   echo "bench ok"
 fi
 ARGS="--workload $W --extras= --steps 2 --warmup 1 --cpu-seconds 0"

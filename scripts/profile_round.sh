@@ -1,6 +1,6 @@
 #!/bin/bash
 # Measurement pass for the round (run on the GPU box through gpurun):
-#   1. the default bench line (headline + extra workloads, CPU baselines)
+#   1. the --full bench line (headline + extra workloads, CPU baselines)
 #   2. per workload: rocprofv3 kernel stats of the same command, then the
 #      FETCH_SIZE and WRITE_SIZE passes (separate runs, no tracing domains),
 #      summarised into profiles/latest_pmc.json by scripts/pmc_summary.py
@@ -20,7 +20,7 @@ shift
 WL=${*:-ials_ml20m_d256 safer2_ml20m_d256 ials_msd_d512}
 mkdir -p $OUT
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
+  timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; exit 1; }
   echo "bench ok"
 fi
 for w in $WL; do

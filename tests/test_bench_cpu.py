@@ -51,16 +51,16 @@ def test_frecsys_env_refused():
 
 
 def test_default_extras_every_config_at_every_n():
-    """BASELINE configs[3] and [4] are defined on 8 GPUs: the driver's N = 8
-    run measures configs 3, 4 and 5 beside the headline."""
+    """BASELINE configs[3] and [4] are defined on 8 GPUs: the N = 8 run with
+    --full measures configs 3, 4 and 5 beside the headline."""
     import bench
     for n in (1, 2, 4, 8):
         assert bench.default_extras(n).split(",") == ["safer2_ml20m_d256", "ials_msd_d512",
                                                       "safer2_2m500k_d1024"]
     assert bench.WORKLOADS["safer2_2m500k_d1024"]["max_extra_steps"] == 2
     for n in (1, 8):
-        plan = _plan(_run(["--gpus", str(n), "--print-launch"]))
-        assert plan["n_gpus"] == n and plan["workload"] == "ials_ml20m_d256"
+        plan = _plan(_run(["--gpus", str(n), "--full", "--print-launch"]))
+        assert plan["n_gpus"] == n and plan["workload"] == "ials_ml20m_d256" and plan["full"]
         assert plan["extras"] == ["safer2_ml20m_d256", "ials_msd_d512", "safer2_2m500k_d1024"]
         assert plan["cpu_baseline"] == (n == 1)  # the CPU baseline stays at N = 1
         assert (plan["launch"] is None) == (n == 1)
@@ -68,3 +68,60 @@ def test_default_extras_every_config_at_every_n():
             assert "--nproc-per-node=8" in plan["launch"]
     # every default extra is a BASELINE config the bench knows
     assert all(w in bench.WORKLOADS for w in bench.DEFAULT_EXTRAS)
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full a run times the headline and nothing else: no extra
+    workloads, no CPU baseline, whatever --cpu-seconds says; --extras without
+    --full is refused, not dropped silently."""
+    for n in (1, 8):
+        plan = _plan(_run(["--gpus", str(n), "--steps", "3", "--warmup", "1", "--cpu-seconds", "10",
+                           "--print-launch"]))
+        assert plan["workload"] == "ials_ml20m_d256" and plan["full"] is False
+        assert plan["extras"] == [] and plan["cpu_baseline"] is False
+    assert _plan(_run(["--extras=", "--print-launch"]))["extras"] == []
+    r = _run(["--extras", "ials_msd_d512", "--print-launch"])
+    assert r.returncode != 0 and "--full" in r.stderr
+    plan = _plan(_run(["--full", "--extras", "ials_msd_d512", "--cpu-seconds", "0",
+                       "--print-launch"]))
+    assert plan["extras"] == ["ials_msd_d512"] and plan["cpu_baseline"] is False
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: a table above DUMP_SIDE_BYTES is written as the same
+    ascending sample of rows on every call, a smaller one whole; two tables
+    stay under 64 MB."""
+    import numpy as np
+    import bench
+
+    class Ctx:
+        def __init__(self):
+            self.t = {0: np.arange(50000 * 256, dtype=np.float32).reshape(50000, 256),
+                      1: np.arange(300 * 256, dtype=np.float32).reshape(300, 256)}
+
+        def get_embeddings(self, side):
+            return self.t[side]
+
+    class FH:
+        SIDE_USER, SIDE_ITEM = 0, 1
+
+    assert 2 * bench.DUMP_SIDE_BYTES <= 64 * 10 ** 6
+    old, bench.fh = bench.fh, FH
+    try:
+        import tempfile
+        with tempfile.TemporaryDirectory() as a, tempfile.TemporaryDirectory() as b:
+            sa = bench.dump_outputs(Ctx(), os.path.join(a, "sub"))
+            bench.dump_outputs(Ctx(), b)
+            ua = np.load(os.path.join(a, "sub", "user_emb.npy"))
+            ub = np.load(os.path.join(b, "user_emb.npy"))
+            va = np.load(os.path.join(a, "sub", "item_emb.npy"))
+    finally:
+        bench.fh = old
+    assert ua.dtype == np.float32 and va.dtype == np.float32
+    assert np.array_equal(ua, ub) and np.array_equal(va, Ctx().t[1])
+    rows = bench.DUMP_SIDE_BYTES // (256 * 4)
+    assert ua.shape == (rows, 256) and ua.nbytes <= bench.DUMP_SIDE_BYTES
+    first = ua[:, 0] / 256  # the row index of each sampled row
+    assert np.all(np.diff(first) > 0) and np.array_equal(ua, Ctx().t[0][first.astype(np.int64)])
+    assert sa == {"user_emb": {"rows": rows, "of": 50000, "dim": 256},
+                  "item_emb": {"rows": 300, "of": 300, "dim": 256}}
