@@ -331,8 +331,11 @@ int frecsys_timing_reset(frecsys_ctx* ctx);
  * timed calls, as frecsys_timing does.  Any output may be NULL. */
 int frecsys_work(const frecsys_ctx* ctx, const char* what, double* flops, double* bytes,
                  int64_t* entities, int64_t* launches);
-/* Longest assembly history (h_eff) the history-space path takes on this
- * context (0: that path is off); longer histories run the d-space solve. */
+/* The context's default threshold: the longest assembly history (h_eff) the
+ * history-space path takes on a side that has no threshold of its own (0: that
+ * path is off); longer histories run the d-space solve.  A side can differ
+ * (Dp = 512: users 320 beside this 256), so to tell which rows a solve puts in
+ * which space, ask frecsys_history_space_max_h_side() for the solved side. */
 int32_t frecsys_history_space_max_h(const frecsys_ctx* ctx);
 /* The same for one solved side (FRECSYS_SIDE_USER / _ITEM: the rows solved by
  * frecsys_solve_side(side)); the sides differ where a default or

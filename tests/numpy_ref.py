@@ -78,6 +78,78 @@ def cvar_v(hist, e, X, G, reg, w, nu, eta, quirk):
     return e - eta * (Af @ e - b)
 
 
+# ---- whole-side drivers: one float64 half-step over every entity ----
+# The Gramian is the float64 X^T X (or X^T diag(omega) X) of the fp32 rows,
+# and lambda is the regularisation the models really pass (ials.h:310-315,
+# safer2.h:418-432, cvar_mf.h:413-424). Scalars are taken at the fp32 value the
+# library receives.  Rows with an empty history keep E's values.
+def _f32(x):
+    return float(np.float32(x))
+
+
+def gram64(X, weights=None):
+    X = X.astype(np.float64)
+    if weights is None:
+        return X.T @ X
+    return X.T @ (X * weights.astype(np.float64)[:, None])
+
+
+def _histories(ptr, col):
+    for e in range(len(ptr) - 1):
+        if ptr[e + 1] > ptr[e]:
+            yield e, col[ptr[e]:ptr[e + 1]]
+
+
+def ials_side(ptr, col, X, E, reg, w, reg_exp=1.0):
+    reg, w, n_other = _f32(reg), _f32(w), X.shape[0]
+    G = gram64(X)
+    out = E.astype(np.float64)
+    for e, hist in _histories(ptr, col):
+        lam = reg * (len(hist) + w * n_other) ** _f32(reg_exp)
+        out[e] = ials(hist, X, G, lam, w)
+    return out
+
+
+def project_u_side(ptr, col, X, E, reg, w, omega):
+    reg, w = _f32(reg), _f32(w)
+    lam = reg * (1.0 + w * X.shape[0])
+    G = gram64(X)
+    out = E.astype(np.float64)
+    for e, hist in _histories(ptr, col):
+        out[e] = project_u(hist, X, G, lam, w, float(omega[e]))
+    return out
+
+
+def project_v_side(ptr, col, X, E, reg, w, alpha, item_reg, nu, gram_weights, quirk):
+    reg, w, alpha = _f32(reg), _f32(w), _f32(alpha)
+    G = gram64(X, gram_weights)
+    out = E.astype(np.float64)
+    for e, hist in _histories(ptr, col):
+        lam = reg * (float(item_reg[e]) + alpha * w * X.shape[0])
+        out[e] = project_v(hist, X, G, lam, w, nu, quirk)
+    return out
+
+
+def cvar_u_side(ptr, col, X, E, reg, w, eta, omega):
+    reg, w, eta = _f32(reg), _f32(w), _f32(eta)
+    lam = reg * (1.0 + w * X.shape[0])
+    G = gram64(X)
+    out = E.astype(np.float64)
+    for e, hist in _histories(ptr, col):
+        out[e] = cvar_u(hist, out[e].copy(), X, G, lam, w, eta, float(omega[e]))
+    return out
+
+
+def cvar_v_side(ptr, col, X, E, reg, w, alpha, eta, item_reg, nu, gram_weights, quirk):
+    reg, w, alpha, eta = _f32(reg), _f32(w), _f32(alpha), _f32(eta)
+    G = gram64(X, gram_weights)
+    out = E.astype(np.float64)
+    for e, hist in _histories(ptr, col):
+        lam = reg * (float(item_reg[e]) + alpha * w * X.shape[0])
+        out[e] = cvar_v(hist, out[e].copy(), X, G, lam, w, nu, eta, quirk)
+    return out
+
+
 def user_loss(hist, u, X, G, beta, half):
     p = X[hist].astype(np.float64) @ u.astype(np.float64)
     l = np.mean((p - 1.0) ** 2) + beta * (u @ G.astype(np.float64) @ u)

@@ -21,15 +21,21 @@ pytestmark = pytest.mark.gpu
 fh = pytest.importorskip("frecsys_hip")
 
 TOL_ROW = 1e-4
+MID_EDGES = (257, 320, 321, 384, 385, 512)  # user-side lengths mid_data must hold
 
 
 @pytest.fixture(scope="module")
 def mid_data():
     """Users with 1..600 rows, items with ~250..500: both sides fill the
-    wide bucket, the tridiagonal buckets below it and the d-space above."""
+    wide bucket, the tridiagonal buckets below it and the d-space above.
+    The user side has both sides of the wide bucket's edges (256 | 257, the
+    Dp = 512 user threshold 320 | 321, 384 | 385, 512): a length the draw of
+    1,500 misses (385) is appended as one more user after the drawn ones."""
     rng = np.random.default_rng(5)
     n_users, n_items = 1500, 1200
     hs = rng.integers(1, 600, n_users)
+    hs = np.concatenate([hs, [h for h in MID_EDGES if h not in hs]])
+    n_users = len(hs)
     users, items = [], []
     for u, h in enumerate(hs):
         its = rng.choice(n_items, int(h), replace=False)
@@ -40,6 +46,8 @@ def mid_data():
     from frecsys_hip.data import _csr_from_pairs
     up, uc = _csr_from_pairs(users, items, n_users)
     ip, ic = _csr_from_pairs(items, users, n_items)
+    hu = np.diff(up)
+    assert all((hu == h).any() for h in MID_EDGES), [h for h in MID_EDGES if not (hu == h).any()]
     return n_users, n_items, up, uc, ip, ic
 
 
