@@ -632,7 +632,9 @@ struct WaveCfg {
   static_assert(3 * ((bytes(0) + 511) / 512) * 512 <= 163840, "three workgroups per CU");
 };
 
-template <int TH, bool BF>
+// OFF64: the coalesced fetch's row offsets in 64 bits (launch_wave_v: the
+// other side holds 2^32 floats or more, or FRECSYS_GATHER64=1).
+template <int TH, bool BF, bool OFF64>
 __global__ void __launch_bounds__(256) dual_wave_kernel(DualArgs a) {
   using C = WaveCfg<TH, BF>;
   constexpr int HP = C::HP, NT = C::NT;
@@ -697,13 +699,15 @@ __global__ void __launch_bounds__(256) dual_wave_kernel(DualArgs a) {
   // and ML-20M unchanged (profiles/r06/wave_coal/).
   constexpr bool COAL = FRECSYS_WAVE_COAL != 0;
   constexpr int NQ = COAL ? HP / 8 : 8;  // prefetch registers per lane
-  // COAL: row 8 q + lane / 8's offset (32-bit while rows x Dp < 2^32, as the
-  // wave's own rows: the wave kernels run at Dp <= 1024 on tables < 4G floats)
-  uint32_t coff[COAL ? NQ : 1];
+  // COAL: row 8 q + lane / 8's element offset, 32-bit while rows x Dp < 2^32
+  // and 64-bit above (OFF64, kernels.h gather_off64: the same rows, the same
+  // bits)
+  using coff_t = std::conditional_t<OFF64, int64_t, uint32_t>;
+  coff_t coff[COAL ? NQ : 1];
   if constexpr (COAL) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
-      coff[q] = (uint32_t)max(ids[8 * q + (lane >> 3)], 0) * (uint32_t)Dp + 4u * (lane & 7);
+      coff[q] = (coff_t)max(ids[8 * q + (lane >> 3)], 0) * (coff_t)Dp + 4u * (lane & 7);
   }
   // unconditional loads (row 0 stands in for padding rows, whose c_j = 0):
   // no branches around the loads, so the prefetch stays in flight
@@ -1221,7 +1225,10 @@ template <int TH, bool BF>
 hipError_t launch_wave_v(const DualArgs& a, hipStream_t s) {
   using C = WaveCfg<TH, BF>;
   const unsigned nb = (unsigned)((a.n_rows + 3) / 4);
-  hipLaunchKernelGGL((dual_wave_kernel<TH, BF>), dim3(nb), dim3(256), C::bytes(a.Dp), s, a);
+  if (gather_off64(a.n_other, a.Dp))
+    hipLaunchKernelGGL((dual_wave_kernel<TH, BF, true>), dim3(nb), dim3(256), C::bytes(a.Dp), s, a);
+  else
+    hipLaunchKernelGGL((dual_wave_kernel<TH, BF, false>), dim3(nb), dim3(256), C::bytes(a.Dp), s, a);
   return hipGetLastError();
 }
 

@@ -44,7 +44,10 @@ __global__ void __launch_bounds__(256) user_loss_kernel(LossArgs a) {
   const int64_t e = a.row_lo + idx;
   const int64_t p0 = a.row_ptr[e];
   const int64_t h = a.row_ptr[e + 1] - p0;
-  if (h == 0) return;
+  if (h == 0) {  // an idle row reads 0, whatever an earlier call left in out
+    if (lane == 0) a.out[e] = 0.0f;
+    return;
+  }
   const int g = lane / LPR, c4 = lane % LPR;
   const bool has = c4 < Dp / 4;
   float4 u4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -177,7 +180,10 @@ __global__ void __launch_bounds__(256) loss_gather_kernel(LossArgs a) {
   const int64_t e = a.row_lo + idx;
   const int64_t p0 = a.row_ptr[e];
   const int64_t h = a.row_ptr[e + 1] - p0;
-  if (h == 0) return;
+  if (h == 0) {  // an idle row reads 0, whatever an earlier call left in out
+    if (lane == 0) a.out[e] = 0.0f;
+    return;
+  }
   const int g = lane >> 3, c = lane & 7;
   float4 u4[Q];
 #pragma unroll

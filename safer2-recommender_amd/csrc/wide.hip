@@ -2042,7 +2042,10 @@ __global__ void __launch_bounds__(256) loss_gather_wide_kernel(LossArgs a) {
   const int64_t e = a.row_lo + idx;
   const int64_t p0 = a.row_ptr[e];
   const int64_t h = a.row_ptr[e + 1] - p0;
-  if (h == 0) return;
+  if (h == 0) {  // an idle row reads 0, whatever an earlier call left in out
+    if (lane == 0) a.out[e] = 0.0f;
+    return;
+  }
   const int g = lane / LPR, c = lane % LPR;
   float4 u4[8];
 #pragma unroll

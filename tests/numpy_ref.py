@@ -224,3 +224,52 @@ def safer2_xi(losses, prev_xi, iters, alpha, bw, epan=False):
                 break
         xi = xi - gamma * d
     return xi
+
+
+# ---- the kernels around the solve (tests/aux_data.py), float64 throughout ----
+def user_loss_side(ptr, col, U, V, G64, beta, half):
+    """ComputeUserLoss over one side: l_e of every row with a history, 0 for
+    the empty ones.  G64: the float64 Gramian of V (gram64); beta at the fp32
+    value the library receives."""
+    beta = _f32(beta)
+    out = np.zeros(len(ptr) - 1)
+    for e, hist in _histories(ptr, col):
+        out[e] = user_loss(hist, U[e], V, G64, beta, half)
+    return out
+
+
+def train_stats64(up, uc, U, V):
+    """(observed, unobserved, ||U_r||^2, ||V_r||^2): the parts of
+    ComputeLosses (ials.h:226-305): sum over the observed pairs of (u.v - 1)^2
+    and sum_ij (U^T U)_ij (V^T V)_ij."""
+    U64, V64 = U.astype(np.float64), V.astype(np.float64)
+    rows = np.repeat(np.arange(len(up) - 1), np.diff(up))
+    pred = np.einsum("ij,ij->i", U64[rows], V64[uc])
+    obs = float(np.sum((pred - 1.0) ** 2))
+    unobs = float(np.sum(gram64(U) * gram64(V)))
+    return obs, unobs, np.sum(U64 ** 2, axis=1), np.sum(V64 ** 2, axis=1)
+
+
+def topk64(Ue, V, ep, ec, k):
+    """(S, top): the float64 scores with every history item at -inf, and per
+    row the k first items by (score descending, item id ascending) -- so the
+    excluded items come after every free one, by ascending id."""
+    S = Ue.astype(np.float64) @ V.astype(np.float64).T
+    for r in range(len(ep) - 1):
+        S[r, ec[ep[r]:ep[r + 1]]] = -np.inf
+    ids = np.broadcast_to(np.arange(S.shape[1]), S.shape)
+    order = np.lexsort((ids, -S), axis=1)
+    return S, order[:, :k].astype(np.int32)
+
+
+def topk_close_rows(S, k, rtol=2e-6):
+    """Rows of S (topk64) whose ranking fp32 scores cannot be asked to
+    reproduce exactly: two adjacent listed scores, or the k-th and the
+    (k+1)-th, closer than rtol * max|S|.  Excluded items (-inf) tie exactly
+    and are ordered by id, which is exact in any precision: they never flag."""
+    tol = rtol * np.abs(S[np.isfinite(S)]).max() if np.isfinite(S).any() else 0.0
+    srt = -np.sort(-S, axis=1)[:, :k + 1]
+    with np.errstate(invalid="ignore"):
+        gap = srt[:, :-1] - srt[:, 1:]
+    fin = np.isfinite(srt[:, :-1]) & np.isfinite(srt[:, 1:])
+    return np.any(fin & (gap < tol), axis=1), tol

@@ -8,11 +8,19 @@ beyond 16.7M rows, Dp = 1024 beyond 4.19M).  A table of that size takes
 17 GB of host and device memory to build, so the dispatch is forced here with
 FRECSYS_GATHER64=1 (read at every launch) and both widths must give the same
 bits: every kind, the long-history split slabs included.
+
+The history-space wave kernel (dual.hip dual_wave_kernel, h_eff <= 64) has the
+same pair for the row offsets of its coalesced slab fetch, under the same
+switch: test_wave_kernel_offsets_64_bit_identical runs it on the seam fixture
+with the shipped dispatch (no FRECSYS_DUAL override).
 """
+import os
+
 import numpy as np
 import pytest
 
 import frecsys_hip as fh
+import seam_data as S
 
 pytestmark = pytest.mark.gpu
 
@@ -57,3 +65,41 @@ def test_gather_offsets_64_bit_identical(monkeypatch, quirk_data, dim):
     for x, y in zip(a, b):
         assert np.all(np.isfinite(x))
         np.testing.assert_array_equal(x, y)
+
+
+def _run_hspace(monkeypatch, key, dim, off64):
+    for k in [k for k in os.environ if k.startswith("FRECSYS_")]:
+        monkeypatch.delenv(k)
+    monkeypatch.setenv("FRECSYS_GATHER64", "1" if off64 else "0")
+    c = S.seam_case(key, dim)
+    ctx = fh.Context(dim, c.nu, c.ni, device=0, parity_quirks=c.quirk)
+    ctx.load_csr(fh.SIDE_USER, c.up, c.uc)
+    ctx.load_csr(fh.SIDE_ITEM, c.ip, c.ic)
+    ctx.set_embeddings(fh.SIDE_USER, c.U)
+    ctx.set_embeddings(fh.SIDE_ITEM, c.V)
+    side, other = (fh.SIDE_USER, fh.SIDE_ITEM) if c.seam == "user" else (fh.SIDE_ITEM, fh.SIDE_USER)
+    ctx.gramian(other, weights=c.gram_weights, fetch=False)
+    if c.kind == fh.KIND_IALS:
+        kw = dict(reg_exp=c.reg_exp)
+    elif c.kind == fh.KIND_WEIGHTED_U:
+        kw = dict(entity_weight=c.entity_weight)
+    else:
+        kw = dict(alpha=c.alpha, entity_reg=c.entity_reg, other_weight=c.other_weight)
+    ctx.solve_side(side, c.kind, c.reg, c.w, **kw)
+    tag = "solve_user" if c.seam == "user" else "solve_item"
+    out = ctx.get_embeddings(side), ctx.work(tag + ".hspace")[2], ctx.counter("hspace_reruns")
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("dim", [64, 256, 500, 1000])
+@pytest.mark.parametrize("key", ["ials_user", "weighted_u", "weighted_v_quirk"])
+def test_wave_kernel_offsets_64_bit_identical(monkeypatch, key, dim):
+    a, n_a, reruns_a = _run_hspace(monkeypatch, key, dim, False)
+    b, n_b, reruns_b = _run_hspace(monkeypatch, key, dim, True)
+    c = S.seam_case(key, dim)
+    assert ((c.h_eff > 0) & (c.h_eff <= 64)).sum() >= 10  # entities of the wave kernels
+    assert n_a > 0 and n_b == n_a
+    assert reruns_a == 0 and reruns_b == 0
+    assert np.all(np.isfinite(a))
+    np.testing.assert_array_equal(a, b)
