@@ -271,6 +271,34 @@ int frecsys_set_transport(frecsys_ctx* ctx, const frecsys_transport* t);
  * ascending item id (the reference leaves tie order unspecified), into
  * topk[r*k .. r*k+k) (host int32).  1 <= k <= 1024, k <= items. */
 int frecsys_eval_topk(frecsys_ctx* ctx, int32_t k, int32_t* topk);
+/* Recommendations for rows of a user-factor table (no reference counterpart
+ * beyond EvaluateUser's scoring, recommender.h:132-199): for each of the
+ * n_rows query rows -- rows[i] of `side` (USER: the trained users, EVAL: the
+ * fold-in rows; any order, repeats allowed), or rows 0 .. n_rows-1 when rows
+ * is NULL -- the k best eligible items by descending score s = V u_r (each
+ * score an fp32 FMA chain over the dim, the same whichever tile, item split
+ * or row batch it falls in), ties by ascending item id, into
+ * items[i*k .. i*k+k) and, unless scores is NULL, their scores into
+ * scores[i*k .. i*k+k) (host).  An item is eligible when its item_mask byte
+ * is non-zero (item_mask: host [n_items], or NULL = every item) and, with
+ * FRECSYS_REC_EXCLUDE_HISTORY in flags, it is not in the CSR history of that
+ * row on that side (USER: the training history, EVAL: the fold-in history).
+ * 1 <= k <= 1024; k may exceed the eligible count: the slots beyond it hold
+ * item -1 and score -FLT_MAX.  Scoring and top-K are fused on the device:
+ * no rows x items score matrix exists; rows are ranked in batches whose
+ * workspace (candidates, one history bitmap per row) stays within
+ * FRECSYS_RECOMMEND_WS_MB (default 256), the items cut into
+ * FRECSYS_RECOMMEND_SPLITS parts (default: enough for about 2 workgroups per
+ * CU) -- neither changes a result bit.  Rank-local at any world size (every
+ * rank holds the full tables after a step): no collective, no Gramian.
+ * FRECSYS_ERR_INVALID: side ITEM, k out of range, a row id out of range, the
+ * exclude flag on a side with no CSR loaded, null outputs.  Timer key
+ * "recommend" (one launch per row batch); frecsys_work("recommend"):
+ * 2 rows items d flops. */
+#define FRECSYS_REC_EXCLUDE_HISTORY 1
+int frecsys_recommend(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                      int32_t k, int32_t flags, const uint8_t* item_mask, int32_t* items,
+                      float* scores);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,
@@ -296,6 +324,8 @@ int frecsys_snapshot_residual(frecsys_ctx* ctx, int32_t side, double* sq);
  *                     budget by a failed device allocation: a halved batch,
  *                     fewer long-history slabs, or the register-staged SYRK
  *                     instead of the pre-split table -- results unchanged.
+ * And one value that is no sum: "recommend_splits", the item splits the last
+ * frecsys_recommend call ran with.
  * No reference counterpart (diagnostics of the MI355X path). */
 int frecsys_counter(frecsys_ctx* ctx, const char* what, int64_t* value);
 /* Block until all queued device work is done (all calls already do). */

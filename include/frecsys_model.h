@@ -81,6 +81,26 @@ float frecsys_model_mean_weight(const frecsys_model* m);
  * NULL; iALS has none of these (FRECSYS_ERR_INVALID for weights/item_reg). */
 int frecsys_model_dual_state(const frecsys_model* m, float* weights, float* losses,
                              float* item_reg, float* xi);
+/* The k best items for n trained users (users[i]: a row of U; any order,
+ * repeats allowed) with their scores, items / scores: host [n * k] (scores
+ * may be NULL); exclude_seen != 0 drops each user's training history (the
+ * model must have been trained: Train() loads it), item_mask: host
+ * [n_items] bytes, non-zero = candidate, or NULL.  Ranking, ties, the -1 /
+ * -FLT_MAX fill and the errors are frecsys_recommend's (frecsys_hip.h); no
+ * reference counterpart beyond EvaluateUser's scoring, recommender.h:132-199. */
+int frecsys_model_recommend(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                            int32_t exclude_seen, const uint8_t* item_mask,
+                            int32_t* items, float* scores);
+/* The same for n unseen users given by their histories (hist_items[hist_ptr[i]
+ * .. hist_ptr[i+1]): item ids of user i, hist_ptr[0] = 0): the model's own
+ * fold-in projection (the first half of its EvaluateDataset: ials.h:148-174
+ * and the variants; 8 epochs of block steps for iALS++ / SAFER2++,
+ * ialspp.h:148-206) into the EVAL side of its context, then the ranking of
+ * those rows; exclude_seen drops the given history. */
+int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                    const int32_t* hist_items, int64_t n, int32_t k,
+                                    int32_t exclude_seen, const uint8_t* item_mask,
+                                    int32_t* items, float* scores);
 void frecsys_model_destroy(frecsys_model* m);
 const char* frecsys_model_last_error(void);
 

@@ -148,6 +148,9 @@ struct frecsys_ctx {
   size_t cap_scores = 0;
   int32_t* d_topk = nullptr;     // [eval rows][k]
   size_t cap_topk = 0;
+  char* d_rec = nullptr;         // frecsys_recommend: candidates, counts, bitmaps, outputs
+  size_t cap_rec = 0;
+  int64_t rec_splits = 0;        // item splits of the last call (frecsys_counter "recommend_splits")
   float* wide_ws = nullptr;      // [wide batch][wide_slot_floats(Dp)]
   size_t cap_wide_ws = 0;
   // the pre-split copy of the other side for the wide d-space SYRK
@@ -1225,6 +1228,7 @@ void frecsys_ctx_destroy(frecsys_ctx* c) {
   if (c->d_gstat) (void)hipFree(c->d_gstat);
   if (c->d_dot) (void)hipFree(c->d_dot);
   if (c->d_topk) (void)hipFree(c->d_topk);
+  if (c->d_rec) (void)hipFree(c->d_rec);
   if (c->d_split) (void)hipFree(c->d_split);
   if (c->d_work) (void)hipFree(c->d_work);
   if (c->d_slabs) (void)hipFree(c->d_slabs);
@@ -2110,6 +2114,112 @@ int frecsys_eval_topk(frecsys_ctx* c, int32_t k, int32_t* topk) {
   return FRECSYS_OK;
 }
 
+int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
+                      int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
+  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: side must be USER or EVAL");
+  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, "recommend: k must be in [1, 1024]");
+  if (flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: unknown flag");
+  if (n_rows < 0 || (n_rows > 0 && !items))
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: bad arguments (null outputs)");
+  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  if (exclude && !c->rp[side])
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: exclude flag on a side with no CSR loaded");
+  if (!c->emb[side] || !c->emb[1])
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: side has no embeddings yet");
+  const int64_t ns = c->n[side], m = c->n[1], n = n_rows;
+  if (rows) {
+    for (int64_t i = 0; i < n; ++i)
+      if (rows[i] < 0 || rows[i] >= ns)
+        return fail(c, FRECSYS_ERR_INVALID,
+                    "recommend: row id " + std::to_string(rows[i]) + " out of range");
+  } else if (n > ns) {
+    return fail(c, FRECSYS_ERR_INVALID, "recommend: more rows than the side has");
+  }
+  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, "recommend: no items");
+  if (n == 0) return FRECSYS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // knobs, read per call
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  int dev_cus = 256;
+  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  // item splits: about 2 workgroups per CU over the call's 64-row blocks,
+  // within what the merge keeps in LDS
+  const int max_splits = recommend_max_splits(k, m);
+  const int64_t row_blocks = (n + 63) / 64;
+  int splits = (int)std::min<int64_t>(max_splits, (2 * (int64_t)dev_cus + row_blocks - 1) / row_blocks);
+  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS"))
+    if (atoi(v) > 0) splits = std::min(max_splits, atoi(v));
+  splits = std::max(1, splits);
+  const int cap = recommend_cap(k);
+  const int64_t W = recommend_words(m);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  // per row of a batch: candidates, counts, history bits, outputs
+  const size_t per_row = (size_t)splits * cap * 8 + (size_t)splits * 4 +
+                         (exclude ? (size_t)W * 4 : 0) + (size_t)k * 8;
+  int64_t nb = std::max<int64_t>(1, (int64_t)(((size_t)ws_mb << 20) / per_row));
+  if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
+  nb = std::min(nb, n);
+  const size_t o_cand = 0;
+  const size_t o_counts = up16(o_cand + (size_t)nb * splits * cap * 8);
+  const size_t o_bitmap = up16(o_counts + (size_t)nb * splits * 4);
+  const size_t o_items = up16(o_bitmap + (exclude ? (size_t)nb * W * 4 : 0));
+  const size_t o_scores = up16(o_items + (size_t)nb * k * 4);
+  const size_t o_mask = up16(o_scores + (size_t)nb * k * 4);
+  const size_t o_qrows = up16(o_mask + (size_t)W * 4);
+  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
+  int rc = ensure(c, &c->d_rec, &c->cap_rec, total);
+  if (rc) return rc;
+  // eligibility bits of the items: the mask and id < n_items
+  std::vector<uint32_t> maskw((size_t)W, 0u);
+  for (int64_t j = 0; j < m; ++j)
+    if (!item_mask || item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
+                            hipMemcpyHostToDevice, c->stream));
+  if (rows)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  RecommendArgs a{};
+  a.X = c->emb[side];
+  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
+  a.Y = c->emb[1];
+  a.m = m;
+  a.Dp = c->Dp;
+  a.k = k;
+  a.splits = splits;
+  c->rec_splits = splits;
+  a.row_ptr = exclude ? c->rp[side] : nullptr;
+  a.col = exclude ? c->col[side] : nullptr;
+  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
+  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
+  a.cand = (unsigned long long*)(c->d_rec + o_cand);
+  a.counts = (int32_t*)(c->d_rec + o_counts);
+  a.out_items = (int32_t*)(c->d_rec + o_items);
+  a.out_scores = (float*)(c->d_rec + o_scores);
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
+    a.r0 = r0;
+    a.n = std::min(nb, n - r0);
+    ScopedTimer t(c, "recommend");
+    HIP_TRY(c, launch_recommend(a, c->stream));
+    t.stop();
+    HIP_TRY(c, hipMemcpyAsync(items + r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
+                              hipMemcpyDeviceToHost, c->stream));
+    if (scores)
+      HIP_TRY(c, hipMemcpyAsync(scores + r0 * k, a.out_scores, sizeof(float) * a.n * k,
+                                hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // scoring flops at the logical dim; bytes: both tables read once, lists written
+  const double dd = c->dim;
+  add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
+           ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
 int frecsys_pp_set_rating_index(frecsys_ctx* c, int32_t side, const int32_t* rix) {
   if (!c || (side != 0 && side != 1) || !rix)
     return fail(c, FRECSYS_ERR_INVALID, "pp_set_rating_index: bad arguments");
@@ -2524,6 +2634,10 @@ int frecsys_counter(frecsys_ctx* c, const char* what, int64_t* value) {
   }
   if (!strcmp(what, "ws_shrinks")) {
     *value = c->ws_shrinks;
+    return FRECSYS_OK;
+  }
+  if (!strcmp(what, "recommend_splits")) {
+    *value = c->rec_splits;
     return FRECSYS_OK;
   }
   if (!strcmp(what, "tagged_timeouts")) {

@@ -135,6 +135,16 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
+// Ranking key of a score (topk.hip, recommend.hip): unsigned order = float
+// order, and score_unkey is its exact inverse.
+__device__ __forceinline__ uint32_t score_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone in x
+}
+__device__ __forceinline__ float score_unkey(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
 // ---- fp32 products on the bf16 matrix cores ----
 // x = hi + mid + lo with three bf16 pieces (8 significant bits each; every
 // subtraction is exact, the remainder is below 2^-26 |x|).  The six products

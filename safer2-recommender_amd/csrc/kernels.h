@@ -284,6 +284,41 @@ hipError_t launch_eval_topk(const float* X, int64_t r0, int64_t n, const float* 
                             int Dp, const int64_t* row_ptr, const int32_t* col, int k, float* S,
                             int32_t* out, hipStream_t s);
 
+// Fused scoring + streaming top-K (recommend.hip): the k best eligible items
+// of each of n query rows, with their scores, without a rows x items score
+// buffer.  Query row i of the batch is row qrows[r0 + i] (or r0 + i when
+// qrows == nullptr) of X; an item j is eligible when bit j of maskw is set
+// (the caller folds the item mask and j < m into it) and, with row_ptr / col /
+// bitmap given, j is not in that row's CSR history.
+struct RecommendArgs {
+  const float* X;            // query table, ld = Dp
+  const int64_t* qrows;      // table row of every query row of the call, or nullptr
+  int64_t r0, n;             // this batch: query rows r0 .. r0 + n - 1
+  const float* Y;            // items, ld = Dp
+  int64_t m;                 // items
+  int Dp;
+  int k;                     // 1 .. 1024
+  int splits;                // item splits, 1 .. recommend_max_splits(k, m)
+  const int64_t* row_ptr;    // CSR of the query table's side, or nullptr (no exclusion)
+  const int32_t* col;
+  const uint32_t* maskw;     // [recommend_words(m)] eligibility bits of the items
+  uint32_t* bitmap;          // [n][recommend_words(m)] history bits (workspace), or nullptr
+  unsigned long long* cand;  // [n][splits][recommend_cap(k)] candidates (workspace)
+  int32_t* counts;           // [n][splits] candidates kept per split (workspace)
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k]
+};
+// Candidate slots per (row, split): 4 k rounded up to a power of two, from
+// 512 to 2048 (2 k at k = 1024: a 128-item tile always fits behind k kept
+// candidates; the room beyond k is what spaces the compactions).
+int recommend_cap(int k);
+// 32-bit words per row of the eligibility bitmaps: 4 per 128-item tile.
+int64_t recommend_words(int64_t m);
+// Largest split count: one 128-item tile per split at least, and splits * k
+// candidates within the merge kernel's LDS.
+int recommend_max_splits(int k, int64_t m);
+hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
+
 // Wide dims, Dp = 512 / 1024 (wide.hip).  d-space solve with A in an HBM
 // workspace ([batch][wide_slot_floats(Dp)]), entities a.order[0..n_rows)
 // in batches; Gramian by 128x128 block pairs; per-step tridiagonalisation

@@ -81,11 +81,6 @@ __global__ void __launch_bounds__(64)
   for (int64_t k = p0 + threadIdx.x; k < p1; k += 64) S[u * m + col[k]] = -FLT_MAX;
 }
 
-__device__ __forceinline__ uint32_t score_key(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone in x
-}
-
 // One workgroup per row: the k best items, score descending, item ascending.
 __global__ void __launch_bounds__(256)
     topk_kernel(const float* __restrict__ S, int64_t m, int k, int32_t* __restrict__ out) {

@@ -18,6 +18,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
+REC_EXCLUDE_HISTORY = 1
 KIND_IALS, KIND_WEIGHTED_U, KIND_WEIGHTED_V, KIND_CVAR_GRAD_U, KIND_CVAR_GRAD_V = range(5)
 
 OK = 0
@@ -41,7 +42,7 @@ EXPORTS = (
     "frecsys_get_gram_groups", "frecsys_set_gram_groups", "frecsys_get_gramian",
     "frecsys_gram_plan", "frecsys_work", "frecsys_snapshot_residual", "frecsys_counter",
     "frecsys_pp_sync", "frecsys_release_workspaces", "frecsys_pp_get_predictions",
-    "frecsys_set_transport",
+    "frecsys_set_transport", "frecsys_recommend",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -49,6 +50,7 @@ MODEL_EXPORTS = (
     "frecsys_model_config_default", "frecsys_model_create", "frecsys_model_initialize",
     "frecsys_model_train", "frecsys_model_context", "frecsys_model_mean_weight",
     "frecsys_model_destroy", "frecsys_model_last_error", "frecsys_model_dual_state",
+    "frecsys_model_recommend", "frecsys_model_recommend_fold_in",
 )
 
 
@@ -159,6 +161,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_release_workspaces": (ctypes.c_int, [P]),
         "frecsys_pp_get_predictions": (ctypes.c_int, [P, I32, P]),
         "frecsys_set_transport": (ctypes.c_int, [P, P]),
+        "frecsys_recommend": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -188,6 +191,8 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_destroy": (None, [P]),
         "frecsys_model_last_error": (ctypes.c_char_p, []),
         "frecsys_model_dual_state": (ctypes.c_int, [P, P, P, P, P]),
+        "frecsys_model_recommend": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
+        "frecsys_model_recommend_fold_in": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -360,7 +365,8 @@ class Context:
 
     def counter(self, what: str) -> int:
         """Cumulative event counter: "hspace_reruns", "tagged_timeouts" or
-        "ws_shrinks"."""
+        "ws_shrinks"; "recommend_splits": the item splits of the last
+        recommend call."""
         v = ctypes.c_int64()
         self._check(self.lib.frecsys_counter(self.h, what.encode(), ctypes.byref(v)))
         return int(v.value)
@@ -440,6 +446,28 @@ class Context:
         out = np.zeros((self.n[SIDE_EVAL], k), dtype=np.int32)
         self._check(self.lib.frecsys_eval_topk(self.h, k, _ptr(out)))
         return out
+
+    def recommend(self, side: int, k: int, rows=None, exclude_history: bool = True,
+                  item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(items int32 [n, k], scores float32 [n, k]): the k best eligible
+        items of each query row of `side` (SIDE_USER or SIDE_EVAL) by score
+        descending, item id ascending -- frecsys_recommend, fused scoring +
+        top-K on the GPU.  rows: row ids (any order, repeats allowed; None =
+        every row of the side); exclude_history drops the row's CSR history;
+        item_mask [n_items]: non-zero = candidate.  Slots beyond the eligible
+        count hold item -1 and score -FLT_MAX."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        items = np.full((n, k) if k > 0 else (n, 0), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        self._check(self.lib.frecsys_recommend(self.h, side, _ptr(r), n, k,
+                                               REC_EXCLUDE_HISTORY if exclude_history else 0,
+                                               _ptr(mk), _ptr(items), _ptr(scores)))
+        return items, scores
 
     def pp_set_rating_index(self, side: int, rix: np.ndarray):
         r = np.ascontiguousarray(rix, dtype=np.int32)
@@ -600,6 +628,47 @@ class Model:
 
     def mean_weight(self) -> float:
         return float(self.lib.frecsys_model_mean_weight(self.h))
+
+    def _mask(self, item_mask):
+        if item_mask is None:
+            return None
+        mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+        assert mk.shape == (self.n_items,), mk.shape
+        return mk
+
+    def recommend(self, users, k: int, exclude_seen: bool = True, item_mask=None):
+        """(items int32 [n, k], scores float32 [n, k]) for trained users
+        (frecsys_model_recommend): best k items by score, ties by item id;
+        exclude_seen drops the training history; item -1 / score -FLT_MAX
+        beyond the eligible count."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        mk = self._mask(item_mask)
+        items = np.full((len(u), max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        rc = self.lib.frecsys_model_recommend(self.h, _ptr(u), len(u), k, int(bool(exclude_seen)),
+                                              _ptr(mk), _ptr(items), _ptr(scores))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return items, scores
+
+    def recommend_fold_in(self, hist_ptr, hist_items, k: int, exclude_seen: bool = True,
+                          item_mask=None):
+        """The same for unseen users given by their histories (CSR: hist_ptr
+        int64 [n + 1], hist_items int32): the model's fold-in projection, then
+        the ranking (frecsys_model_recommend_fold_in).  The projected rows stay
+        in the EVAL side of the model's context."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        mk = self._mask(item_mask)
+        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        rc = self.lib.frecsys_model_recommend_fold_in(self.h, _ptr(hp), _ptr(hi), n, k,
+                                                      int(bool(exclude_seen)), _ptr(mk),
+                                                      _ptr(items), _ptr(scores))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return items, scores
 
     def close(self):
         if getattr(self, "h", None):

@@ -47,9 +47,13 @@ class CVaRMFRecommender : public detail::DeviceModel {
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
+  }
+
+  void FoldIn(const Csr& csr) override {
     frecsys_solve_params p = solve_params(FRECSYS_KIND_WEIGHTED_U, regularization_,
                                           unobserved_weight_);  // StepU_eval, omega = 1
-    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user, p);
+    FoldInSolve(csr, p);
   }
 
   void Train(const Dataset& data) override {

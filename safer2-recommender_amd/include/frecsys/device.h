@@ -9,6 +9,7 @@
 // (ials.h:141) -> LOG(FATAL) (abort) here, naming the entity.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -180,6 +181,29 @@ class DeviceContext {
     std::vector<int32_t> out((size_t)n_[EVAL] * k);
     check(frecsys_eval_topk(ctx_, k, out.data()), "eval_topk");
     return out;
+  }
+
+  // Best k eligible items per query row with their scores, [rows][k] each
+  // (frecsys_recommend: fused GPU scoring + top-K; item -1 / score -FLT_MAX
+  // beyond the eligible count).  rows: row ids of `side` (USER or EVAL).
+  struct Recommendations {
+    std::vector<int32_t> items;
+    std::vector<float> scores;
+  };
+  // The status code instead of LOG(FATAL), for callers that report errors.
+  int TryRecommend(int side, const int64_t* rows, int64_t n, int k, int flags,
+                   const uint8_t* mask, int32_t* items, float* scores) {
+    return frecsys_recommend(ctx_, side, rows, n, k, flags, mask, items, scores);
+  }
+  Recommendations Recommend(int side, const std::vector<int64_t>& rows, int k, int flags,
+                            const uint8_t* mask = nullptr) {
+    Recommendations r;
+    r.items.resize(rows.size() * (size_t)std::max(k, 0));
+    r.scores.resize(r.items.size());
+    check(TryRecommend(side, rows.data(), (int64_t)rows.size(), k, flags, mask, r.items.data(),
+                       r.scores.data()),
+          "recommend");
+    return r;
   }
 
   // Per-user loss of `side` (USER or EVAL) against ITEM / G[ITEM].

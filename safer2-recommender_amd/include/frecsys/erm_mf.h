@@ -52,9 +52,13 @@ class ERMMFRecommender : public detail::DeviceModel {
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
+  }
+
+  void FoldIn(const Csr& csr) override {
     frecsys_solve_params p = solve_params(FRECSYS_KIND_WEIGHTED_U, regularization_,
                                           unobserved_weight_);  // omega = 1 (erm_mf.h:235-244)
-    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user, p);
+    FoldInSolve(csr, p);
   }
 
   void Train(const Dataset& data) override {

@@ -51,8 +51,12 @@ class IALSRecommender : public detail::DeviceModel {
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
+  }
+
+  void FoldIn(const Csr& csr) override {
     dev_->Gramian(DeviceContext::ITEM);  // Step's V^T V (ials.h:321)
-    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user, params());
+    FoldInSolve(csr, params());
   }
 
   void Train(const Dataset& data) override {

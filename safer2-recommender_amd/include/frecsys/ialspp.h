@@ -39,13 +39,15 @@ class IALSppRecommender : public detail::DeviceModel {
     throw("Function 'Score' is not implemented");  // ialspp.h:62-65
   }
 
-  // Fold-in: 8 epochs of block steps from zero user embeddings
-  // (ialspp.h:148-206), then GPU scoring + top-K.
+  // FoldIn, then GPU scoring + top-K.
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
-    std::vector<int32_t> ids;
-    Csr csr;
-    data.compact_users(&ids, &csr);
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
+  }
+
+  // Fold-in: 8 epochs of block steps from zero user embeddings
+  // (ialspp.h:148-206).
+  void FoldIn(const Csr& csr) override {
     dev_->LoadEval(csr);
     dev_->ZeroEval(dim_);
     const frecsys_solve_params p = params();
@@ -57,7 +59,6 @@ class IALSppRecommender : public detail::DeviceModel {
         dev_->PPStep(DeviceContext::EVAL, start, end, p);
       }
     }
-    return RankEval(k_list, alpha_list, ids, eval_by_user);
   }
 
   void Train(const Dataset& data) override {

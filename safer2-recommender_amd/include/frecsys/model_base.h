@@ -55,22 +55,52 @@ class DeviceModel : public Recommender {
   const VectorXf& item_regularization() const { return item_reg_; }
   DeviceContext& device() { return *dev_; }
 
+  // The model's projection of held-out users (the fold-in of its
+  // EvaluateDataset: ials.h:148-174 and the model variants): row r of `csr`
+  // is one user's history; loads it as the EVAL side and leaves the projected
+  // embeddings there.
+  virtual void FoldIn(const Csr& csr) = 0;
+
+  // The k best items for trained users (rows of U), with scores; exclude_seen
+  // drops each user's training history (Train() must have loaded it), mask:
+  // [num_items] bytes, non-zero = candidate, or nullptr.  No reference
+  // counterpart beyond EvaluateUser's scoring (recommender.h:132-199).
+  DeviceContext::Recommendations Recommend(const std::vector<int64_t>& users, int k,
+                                           bool exclude_seen, const uint8_t* mask = nullptr) {
+    return dev_->Recommend(DeviceContext::USER, users, k,
+                           exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
+  }
+  // The same for unseen users given by their histories: FoldIn, then the
+  // ranking of the EVAL rows (exclude_seen drops the fold-in history).
+  DeviceContext::Recommendations RecommendFoldIn(const Csr& csr, int k, bool exclude_seen,
+                                                 const uint8_t* mask = nullptr) {
+    FoldIn(csr);
+    std::vector<int64_t> rows((size_t)csr.rows());
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = (int64_t)i;
+    return dev_->Recommend(DeviceContext::EVAL, rows, k,
+                           exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
+  }
+
  protected:
   virtual void OnEmbeddingsSet() {}
 
-  // Fold-in + evaluation (ials.h:148-185 and its model variants, then
-  // EvaluateDatasetInternal / EvaluateUser, recommender.h:78-199): project
-  // the users of `data` with `params`, score every item, exclude each user's
-  // fold-in history and rank -- all on the GPU (frecsys_eval_topk); Recall /
-  // NDCG of the k_list cut-offs on host.
+  // FoldIn of the models that project with one solve (ials.h:148-185 and its
+  // variants): the EVAL rows solved with `params`.
+  void FoldInSolve(const Csr& csr, const frecsys_solve_params& params) {
+    dev_->LoadEval(csr);
+    dev_->Solve(DeviceContext::EVAL, params);
+  }
+
+  // Fold-in + evaluation (then EvaluateDatasetInternal / EvaluateUser,
+  // recommender.h:78-199): project the users of `data` (FoldIn), score every
+  // item, exclude each user's fold-in history and rank -- all on the GPU
+  // (frecsys_eval_topk); Recall / NDCG of the k_list cut-offs on host.
   EvaluationResult FoldInEvaluate(const VectorXi& k_list, const VectorXf& alpha_list,
-                                  const Dataset& data, const SpMatrix& eval_by_user,
-                                  const frecsys_solve_params& params) {
+                                  const Dataset& data, const SpMatrix& eval_by_user) {
     std::vector<int32_t> ids;
     Csr csr;
     data.compact_users(&ids, &csr);
-    dev_->LoadEval(csr);
-    dev_->Solve(DeviceContext::EVAL, params);
+    FoldIn(csr);
     return RankEval(k_list, alpha_list, ids, eval_by_user);
   }
 

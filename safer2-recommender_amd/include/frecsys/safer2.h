@@ -202,9 +202,11 @@ class SAFER2Recommender : public detail::DeviceModel {
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
-    // StepU with omega = 1 and the cached item gramian (safer2.h:246-252)
-    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user, u_params(false));
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
   }
+
+  // StepU with omega = 1 and the cached item gramian (safer2.h:246-252)
+  void FoldIn(const Csr& csr) override { FoldInSolve(csr, u_params(false)); }
 
   void Train(const Dataset& data) override {
     // FRECSYS_HOST_PROF (diagnostics): wall ms of each Train() phase on stderr

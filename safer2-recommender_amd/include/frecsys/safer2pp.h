@@ -34,13 +34,15 @@ class SAFER2ppRecommender : public SAFER2Recommender {
     block_size_ = block_size;
   }
 
-  // Fold-in: 8 epochs of weighted (omega = 1) user block steps from zero
-  // embeddings (safer2pp.h:220-286), then GPU scoring + top-K.
+  // FoldIn, then GPU scoring + top-K.
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,
                                    const Dataset& data, const SpMatrix& eval_by_user) override {
-    std::vector<int32_t> ids;
-    Csr csr;
-    data.compact_users(&ids, &csr);
+    return FoldInEvaluate(k_list, alpha_list, data, eval_by_user);
+  }
+
+  // Fold-in: 8 epochs of weighted (omega = 1) user block steps from zero
+  // embeddings (safer2pp.h:220-286).
+  void FoldIn(const Csr& csr) override {
     dev_->LoadEval(csr);
     dev_->ZeroEval(dim_);
     const frecsys_solve_params p = u_params(false);
@@ -52,7 +54,6 @@ class SAFER2ppRecommender : public SAFER2Recommender {
         dev_->PPStep(DeviceContext::EVAL, start, end, p);
       }
     }
-    return RankEval(k_list, alpha_list, ids, eval_by_user);
   }
 
   void Train(const Dataset& data) override {

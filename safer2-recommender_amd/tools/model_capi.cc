@@ -161,6 +161,50 @@ int frecsys_model_dual_state(const frecsys_model* m, float* weights, float* loss
   return FRECSYS_OK;
 }
 
+int frecsys_model_recommend(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                            int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                            float* scores) {
+  if (!m || n < 0 || (n > 0 && !users))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend: bad arguments");
+  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const int rc = dev.TryRecommend(FRECSYS_SIDE_USER, users, n, k,
+                                  exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
+                                  items, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                    const int32_t* hist_items, int64_t n, int32_t k,
+                                    int32_t exclude_seen, const uint8_t* item_mask,
+                                    int32_t* items, float* scores) {
+  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0)
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: bad arguments");
+  // checked here: the C++ layer treats a bad EVAL CSR as fatal
+  if (k < 1 || k > 1024 || (n > 0 && !items))
+    return model_fail(FRECSYS_ERR_INVALID,
+                      "frecsys_model_recommend_fold_in: k must be in [1, 1024], items non-null");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i])
+      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: hist_ptr not monotone");
+  if (hist_ptr[n] > 0 && !hist_items)
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: null hist_items");
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: item id " +
+                                                 std::to_string(hist_items[p]) + " out of range");
+  if (n == 0) return FRECSYS_OK;
+  frecsys::Csr csr;
+  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+  dm->FoldIn(csr);
+  const int rc = dm->device().TryRecommend(FRECSYS_SIDE_EVAL, nullptr, n, k,
+                                           exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
+                                           item_mask, items, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
 void frecsys_model_destroy(frecsys_model* m) { delete m; }
 
 const char* frecsys_model_last_error(void) { return g_model_error.c_str(); }
