@@ -30,6 +30,9 @@
  *       their static per-entity Project / ProjectU / ProjectV /
  *       ProjectU_eval (ials.h:88-144 + 317-365; safer2.h:104-221 + 437-555;
  *       erm_mf.h:91-210 + 397-513; cvar_mf.h:88-229 + 427-538 + 645-692)
+ *   frecsys_solve_side_cg         -- the same drivers with use_cg: the
+ *       Eigen::ConjugateGradient branch of Project / ProjectU / ProjectV
+ *       (ials.h:133-139; safer2.h:152-157, 210-215)
  *   frecsys_user_loss             -- ComputeUserLoss / ComputeLoss
  *       (ials.h:70-86 + 367-408; safer2.h:85-101 + 558-596)
  *   frecsys_comm_* / frecsys_partition -- new: the reference has no
@@ -195,6 +198,49 @@ int frecsys_set_gramian(frecsys_ctx* ctx, int32_t side, const float* host,
  * solves against ITEM and writes the EVAL embeddings. */
 int frecsys_solve_side(frecsys_ctx* ctx, int32_t side,
                        const frecsys_solve_params* params);
+/* ---- conjugate-gradient solve (--use_cg) ----
+ * The `use_cg` branch of the reference's Project / ProjectU / ProjectV
+ * (ials.h:133-139, safer2.h:152-157, 210-215), there
+ * Eigen::ConjugateGradient<MatrixXf, Lower> on the assembled d x d matrix:
+ * here the same recurrence on the operator, A never formed (cg.hip),
+ *   A p = s_G G p + sum_j c_j y_j (y_j . p) + lambda p
+ * with the terms of frecsys_solve_side's assembly (IALS: s_G = w, c_j = 1;
+ * WEIGHTED_U: s_G = omega w, c_j = omega / h; WEIGHTED_V: s_G = w, c_j = nu_j,
+ * the parity tail-quirk rows a second time in c_j and not in b).  Recurrence
+ * (Jacobi preconditioner, zero start):
+ *   x = 0; r = b; ||b||^2 == 0 -> x = 0, 0 iterations
+ *   thr = max(tolerance^2 ||b||^2, FLT_MIN); ||r||^2 < thr -> done
+ *   p = r ./ diag(A); rho = r.p; i = 0
+ *   while i < max_iterations:
+ *     t = A p; alpha = rho / (p.t); x += alpha p; r -= alpha t
+ *     if ||r||^2 < thr: break
+ *     z = r ./ diag(A); rho' = r.z; p = z + (rho'/rho) p; rho = rho'; i += 1
+ * (a zero diagonal entry has inverse 1): it stops at
+ * ||r||^2 < tolerance^2 ||b||^2 or at i = max_iterations; max_iterations = 0
+ * gives x = 0.  An entity's result bits do not depend on the other entities
+ * of the call, the shard or the world size. */
+typedef struct {
+  int32_t max_iterations; /* --cg_max_iterations */
+  float tolerance;        /* --cg_error_tolerance */
+} frecsys_cg_params;
+/* frecsys_solve_side by conjugate gradients: sides USER / ITEM / EVAL, kinds
+ * IALS / WEIGHTED_U / WEIGHTED_V; the same sharding, all-gather of the rows,
+ * external-exchange rules and "rows with an empty history are left
+ * untouched".  FRECSYS_ERR_INVALID: max_iterations < 0, a negative or NaN
+ * tolerance, a CVAR_GRAD kind (no CG form in the reference);
+ * FRECSYS_ERR_UNSUPPORTED: dim > 256 (the CG kernel is built for dim <= 256);
+ * FRECSYS_ERR_NAN: a non-finite result row (entity via
+ * frecsys_last_error_entity); there is no NOT_SPD on this path.  Counters
+ * "cg_iterations" (sum of i over the solved entities) and "cg_unconverged"
+ * (entities that stopped at the cap); timer key "<solve>.cg";
+ * frecsys_work("<solve>.cg"): sum_e i_e (2 d^2 + 4 h_e d) flops and
+ * sum_e i_e (h_e d 4 + h_e 4) gather bytes. */
+int frecsys_solve_side_cg(frecsys_ctx* ctx, int32_t side, const frecsys_solve_params* params,
+                          const frecsys_cg_params* cg);
+/* The i of the last frecsys_solve_side_cg per row of `side` (host [rows of
+ * side]); -1 for a row not solved here (empty history, another rank's row, no
+ * CG call yet). */
+int frecsys_cg_iterations(frecsys_ctx* ctx, int32_t side, int32_t* host);
 /* Per-user loss over `side` (USER or EVAL) rows against ITEM embeddings and
  * G[ITEM]: (1/h) sum (x.u - 1)^2 + beta u^T G u, halved if half != 0.
  * Rows with empty history get 0.  host_out [rows] may be NULL (result kept
@@ -323,7 +369,10 @@ int frecsys_snapshot_residual(frecsys_ctx* ctx, int32_t side, double* sq);
  *   "ws_shrinks"      wide workspaces (d = 257..1024) cut below their
  *                     budget by a failed device allocation: a halved batch,
  *                     fewer long-history slabs, or the register-staged SYRK
- *                     instead of the pre-split table -- results unchanged.
+ *                     instead of the pre-split table -- results unchanged;
+ *   "cg_iterations"   sum of the CG iteration counts of every entity solved
+ *                     by frecsys_solve_side_cg;
+ *   "cg_unconverged"  entities whose CG stopped at max_iterations.
  * And one value that is no sum: "recommend_splits", the item splits the last
  * frecsys_recommend call ran with.
  * No reference counterpart (diagnostics of the MI355X path). */
@@ -345,7 +394,8 @@ int frecsys_release_workspaces(frecsys_ctx* ctx);
  * "allreduce"; per solve also "<solve>.dspace" (d x d solve of the long
  * histories), "<solve>.split" (partial SYRKs of the longest of them),
  * "<solve>.basis" (tridiagonalisation of G + rotation of the other side),
- * "<solve>.hspace" (history-space solve), "<solve>.rotate")
+ * "<solve>.hspace" (history-space solve), "<solve>.rotate", "<solve>.cg"
+ * (the conjugate-gradient kernel of frecsys_solve_side_cg))
  * since the last frecsys_timing_reset. */
 int frecsys_timing(const frecsys_ctx* ctx, const char* what, double* total_ms,
                    int64_t* launches);

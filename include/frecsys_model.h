@@ -61,6 +61,14 @@ typedef struct {
   int32_t rank;           /* -1: RANK */
   const uint8_t* comm_id; /* world > 1: the 128-byte RCCL id of rank 0
                              (frecsys_comm_unique_id); NULL: FRECSYS_COMM_FILE */
+  /* --use_cg / --cg_error_tolerance / --cg_max_iterations (run_model.cc:172):
+   * ials and safer2 solve by conjugate gradients (frecsys_solve_side_cg);
+   * erm_mf with use_cg is FRECSYS_ERR_UNSUPPORTED (its BiCGSTAB path is not
+   * built); ialspp, safer2pp and cvar_mf take no such arguments in the
+   * reference and ignore them. */
+  int32_t use_cg;
+  float cg_error_tolerance;
+  int32_t cg_max_iterations;
 } frecsys_model_config;
 
 /* The run_model defaults (model_name NULL: must be set by the caller). */

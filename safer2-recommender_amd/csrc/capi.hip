@@ -151,6 +151,18 @@ struct frecsys_ctx {
   char* d_rec = nullptr;         // frecsys_recommend: candidates, counts, bitmaps, outputs
   size_t cap_rec = 0;
   int64_t rec_splits = 0;        // item splits of the last call (frecsys_counter "recommend_splits")
+  // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
+  // per row of each side (device scratch + host copy; -1: not solved here),
+  // the kernel's {sum of i, entities at the cap} and the cumulative counters
+  int32_t* d_cg_iters = nullptr;
+  size_t cap_cg_iters = 0;
+  unsigned long long* d_cg_stats = nullptr;
+  size_t cap_cg_stats = 0;
+  int32_t* d_cg_bstart = nullptr;  // batches of the queue (cg_plan_batches)
+  size_t cap_cg_bstart = 0;
+  std::vector<int32_t> cg_bstart;
+  std::vector<int32_t> cg_iters[3];
+  int64_t cg_iterations = 0, cg_unconverged = 0;
   float* wide_ws = nullptr;      // [wide batch][wide_slot_floats(Dp)]
   size_t cap_wide_ws = 0;
   // the pre-split copy of the other side for the wide d-space SYRK
@@ -1229,6 +1241,9 @@ void frecsys_ctx_destroy(frecsys_ctx* c) {
   if (c->d_dot) (void)hipFree(c->d_dot);
   if (c->d_topk) (void)hipFree(c->d_topk);
   if (c->d_rec) (void)hipFree(c->d_rec);
+  if (c->d_cg_iters) (void)hipFree(c->d_cg_iters);
+  if (c->d_cg_stats) (void)hipFree(c->d_cg_stats);
+  if (c->d_cg_bstart) (void)hipFree(c->d_cg_bstart);
   if (c->d_split) (void)hipFree(c->d_split);
   if (c->d_work) (void)hipFree(c->d_work);
   if (c->d_slabs) (void)hipFree(c->d_slabs);
@@ -2010,6 +2025,149 @@ int frecsys_solve_side(frecsys_ctx* c, int32_t side, const frecsys_solve_params*
   return solve_side_impl(c, side, p, false);
 }
 
+// Conjugate-gradient form of frecsys_solve_side (cg.hip): the same sharding,
+// queue, uploads and row all-gather; no factorisation, so no NOT_SPD.
+int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
+                          const frecsys_cg_params* cg) {
+  if (!c || !valid_side(side) || !p || !cg)
+    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: bad arguments");
+  if (cg->max_iterations < 0 || !(cg->tolerance >= 0.0f))
+    return fail(c, FRECSYS_ERR_INVALID,
+                "solve_cg: max_iterations and tolerance must be >= 0 (and not NaN)");
+  const int kind = p->kind;
+  if (kind < FRECSYS_KIND_IALS || kind > FRECSYS_KIND_CVAR_GRAD_V)
+    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: bad kind");
+  if (kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V)
+    return fail(c, FRECSYS_ERR_INVALID,
+                "solve_cg: the CVaR gradient kinds have no conjugate-gradient form");
+  if (c->dim > 256)
+    return fail(c, FRECSYS_ERR_UNSUPPORTED,
+                "solve_cg: the conjugate-gradient path is built for dim <= 256 (dim " +
+                    std::to_string(c->dim) + ")");
+  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "solve_cg: no CSR loaded for side");
+  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V;
+  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U;
+  if (vkind && (!p->entity_reg || !p->other_weight))
+    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: V kinds need entity_reg and other_weight");
+  const int other = side == 1 ? 0 : 1;
+  if (p->from_snapshot && !c->snap[other])
+    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: from_snapshot without a snapshot");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc = join_eager(c, side < 2 ? 1 << side : 0, c->stream);  // a build still reading emb[side]
+  if (rc) return rc;
+  if (ukind && p->entity_weight) {
+    rc = upload(c, &c->d_entity_weight, &c->cap_entity_weight, p->entity_weight,
+                (size_t)c->n[side]);
+    if (rc) return rc;
+  }
+  if (vkind) {
+    rc = upload(c, &c->d_entity_reg, &c->cap_entity_reg, p->entity_reg, (size_t)c->n[side]);
+    if (rc) return rc;
+    rc = upload(c, &c->d_other_weight, &c->cap_other_weight, p->other_weight, (size_t)c->n[other]);
+    if (rc) return rc;
+  }
+  rc = build_order(c, side);
+  if (rc) return rc;
+  const int64_t n = c->n[side];
+  rc = ensure(c, &c->d_cg_iters, &c->cap_cg_iters, (size_t)std::max<int64_t>(n, 1));
+  if (rc) return rc;
+  rc = ensure(c, &c->d_cg_stats, &c->cap_cg_stats, (size_t)2);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->d_cg_iters, 0xFF, sizeof(int32_t) * std::max<int64_t>(n, 1),
+                            c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_cg_stats, 0, sizeof(unsigned long long) * 2, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
+  CgArgs a{};
+  a.kind = kind;
+  a.quirk = c->quirks;
+  a.Dp = c->Dp;
+  a.dim = c->dim;
+  a.order = c->d_order[side];
+  cg_plan_batches(c->h_order[side].data(), c->order_n[side], &c->cg_bstart);
+  rc = ensure(c, &c->d_cg_bstart, &c->cap_cg_bstart, c->cg_bstart.size());
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_cg_bstart, c->cg_bstart.data(),
+                            sizeof(int32_t) * c->cg_bstart.size(), hipMemcpyHostToDevice,
+                            c->stream));
+  a.bstart = c->d_cg_bstart;
+  a.n_batches = (int64_t)c->cg_bstart.size() - 1;
+  a.col = c->col[side];
+  a.X = p->from_snapshot ? c->snap[other] : c->emb[other];
+  a.n_other = c->n[other];
+  a.G = c->gram[other];
+  a.out = c->emb[side];
+  a.reg = p->reg;
+  a.reg_exp = p->reg_exp;
+  a.w = p->unobserved_weight;
+  a.alpha = p->alpha;
+  a.lambda_is_reg = p->lambda_is_reg;
+  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight : nullptr;
+  a.entity_reg = vkind ? c->d_entity_reg : nullptr;
+  a.other_weight = vkind ? c->d_other_weight : nullptr;
+  a.max_iter = cg->max_iterations;
+  a.tol = cg->tolerance;
+  a.iters = c->d_cg_iters;
+  a.stats = c->d_cg_stats;
+  a.fail = c->d_fail;
+  if (side < 2) emb_written(c, side);
+  c->dual_used[side] = false;
+  static const char* names[3] = {"solve_user", "solve_item", "solve_eval"};
+  const std::string pre = names[side];
+  {
+    ScopedTimer t(c, names[side]);
+    const size_t k = ktimer_begin(c, pre + ".cg", c->stream);
+    HIP_TRY(c, launch_cg(a, c->stream));
+    ktimer_end(c, k, c->stream);
+    t.stop();
+  }
+  unsigned long long f = ~0ull, st[2] = {0, 0};
+  std::vector<int32_t>& it = c->cg_iters[side];
+  it.assign((size_t)n, -1);
+  HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st, c->d_cg_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  if (n)
+    HIP_TRY(c, hipMemcpyAsync(it.data(), c->d_cg_iters, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
+                              c->stream));
+  if (side < 2 && (c->world > 1 || c->comm)) {
+    ScopedTimer t(c, "allgather");
+    rc = allgather_rows(c, c->emb[side], side, c->Dp);
+    if (rc) return rc;
+    t.stop();
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  flush_ktimers(c);
+  c->cg_iterations += (int64_t)st[0];
+  c->cg_unconverged += (int64_t)st[1];
+  {  // per entity and iteration: G p (2 d^2) + two passes of the history rows (4 h d)
+    const double d = c->dim;
+    const std::vector<QueueRec>& q = c->h_order[side];
+    double fl = 0.0, by = 0.0;
+    int64_t ne = 0;
+    for (const QueueRec& r : q) {
+      const int32_t i = it[(size_t)r.entity];
+      if (i < 0) continue;
+      ++ne;
+      fl += (double)i * (2.0 * d * d + 4.0 * (double)r.h * d);
+      by += (double)i * ((double)r.h * d * 4.0 + (double)r.h * 4.0);
+    }
+    add_work(c, pre + ".cg", fl, by, ne);
+  }
+  if (f != ~0ull) {
+    c->err_entity = (int64_t)f - 1;
+    return fail(c, FRECSYS_ERR_NAN,
+                "solve_cg: non-finite result row for entity " + std::to_string(c->err_entity));
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_cg_iterations(frecsys_ctx* c, int32_t side, int32_t* host) {
+  if (!c || !valid_side(side) || !host)
+    return fail(c, FRECSYS_ERR_INVALID, "cg_iterations: bad arguments");
+  const std::vector<int32_t>& it = c->cg_iters[side];
+  for (int64_t i = 0; i < c->n[side]; ++i) host[i] = (size_t)i < it.size() ? it[(size_t)i] : -1;
+  return FRECSYS_OK;
+}
+
 int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, float* host_out) {
   if (!c || (side != 0 && side != 2)) return fail(c, FRECSYS_ERR_INVALID, "loss: bad side");
   if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "loss: no CSR loaded");
@@ -2634,6 +2792,14 @@ int frecsys_counter(frecsys_ctx* c, const char* what, int64_t* value) {
   }
   if (!strcmp(what, "ws_shrinks")) {
     *value = c->ws_shrinks;
+    return FRECSYS_OK;
+  }
+  if (!strcmp(what, "cg_iterations")) {
+    *value = c->cg_iterations;
+    return FRECSYS_OK;
+  }
+  if (!strcmp(what, "cg_unconverged")) {
+    *value = c->cg_unconverged;
     return FRECSYS_OK;
   }
   if (!strcmp(what, "recommend_splits")) {

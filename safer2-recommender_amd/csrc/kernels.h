@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace frecsys_hip {
 
 // One entry of the solve queue: entity row, its history length and the
@@ -157,6 +159,45 @@ struct DualArgs {
 
 // Largest history-space tile count built (h_eff <= 32 * kDualMaxTiles).
 constexpr int kDualMaxTiles = 8;
+
+// Conjugate-gradient solve (cg.hip; Dp <= 256): workgroup b takes the queue
+// entities order[bstart[b] .. bstart[b + 1]), at most kCgE; history rows in
+// chunks of kCgU passes of 64 / GP rows (GP = the power of two >= Dp / 4
+// lanes per row).
+constexpr int kCgE = 16;
+constexpr int kCgU = 8;
+// An entity of more than kCgCoopRows (virtual) history rows is streamed by
+// all four waves of its workgroup; a batch holds as many entities (<= kCgE)
+// as fit kCgBatchRows history rows, at least one (cg_plan_batches).
+constexpr int kCgCoopRows = 256;
+constexpr int kCgBatchRows = 4096;
+struct CgArgs {
+  int kind;                 // FRECSYS_KIND_IALS / WEIGHTED_U / WEIGHTED_V
+  int quirk;                // WEIGHTED_V: the ProjectV tail double-count
+  int Dp, dim;
+  const QueueRec* order;    // LPT queue of the solved side
+  const int32_t* bstart;    // [n_batches + 1] queue position of every batch's first entity
+  int64_t n_batches;
+  const int32_t* col;       // CSR columns of the solved side
+  const float* X;           // other side's embeddings, ld = Dp
+  int64_t n_other;
+  const float* G;           // Dp x Dp Gramian of the other side
+  float* out;               // solved side's embeddings, ld = Dp
+  float reg, reg_exp, w, alpha;
+  int lambda_is_reg;
+  const float* entity_weight;
+  const float* entity_reg;
+  const float* other_weight;
+  int max_iter;
+  float tol;
+  int32_t* iters;             // [rows of side]: i of every solved entity
+  unsigned long long* stats;  // [2]: += sum of i, += entities stopped at the cap
+  unsigned long long* fail;   // atomicMin(entity + 1) on a non-finite result row
+};
+size_t cg_lds_bytes(int Dp);
+// Host: the batches of the queue order[0..n) (consecutive entities).
+void cg_plan_batches(const QueueRec* order, int64_t n, std::vector<int32_t>* bstart);
+hipError_t launch_cg(const CgArgs& a, hipStream_t s);
 
 hipError_t launch_solve(int Dp, const SolveArgs& a, hipStream_t s);
 // Diagnostics: n 32x32 tiles (row-major) -> L^-1 of each (blk: the

@@ -42,7 +42,8 @@ EXPORTS = (
     "frecsys_get_gram_groups", "frecsys_set_gram_groups", "frecsys_get_gramian",
     "frecsys_gram_plan", "frecsys_work", "frecsys_snapshot_residual", "frecsys_counter",
     "frecsys_pp_sync", "frecsys_release_workspaces", "frecsys_pp_get_predictions",
-    "frecsys_set_transport", "frecsys_recommend",
+    "frecsys_set_transport", "frecsys_recommend", "frecsys_solve_side_cg",
+    "frecsys_cg_iterations",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -88,6 +89,10 @@ class _SolveParams(ctypes.Structure):
                 ("other_weight", ctypes.c_void_p)]
 
 
+class _CgParams(ctypes.Structure):
+    _fields_ = [("max_iterations", ctypes.c_int32), ("tolerance", ctypes.c_float)]
+
+
 class _ModelConfig(ctypes.Structure):
     _fields_ = [("model_name", ctypes.c_char_p), ("dim", ctypes.c_int32),
                 ("l2_reg", ctypes.c_float), ("l2_reg_exp", ctypes.c_float),
@@ -100,7 +105,9 @@ class _ModelConfig(ctypes.Structure):
                 ("print_residual_stats", ctypes.c_int32), ("print_var_stats", ctypes.c_int32),
                 ("seed", ctypes.c_int64), ("device", ctypes.c_int32),
                 ("parity_quirks", ctypes.c_int32), ("world", ctypes.c_int32),
-                ("rank", ctypes.c_int32), ("comm_id", ctypes.c_void_p)]
+                ("rank", ctypes.c_int32), ("comm_id", ctypes.c_void_p),
+                ("use_cg", ctypes.c_int32), ("cg_error_tolerance", ctypes.c_float),
+                ("cg_max_iterations", ctypes.c_int32)]
 
 
 _lib = None
@@ -162,6 +169,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_pp_get_predictions": (ctypes.c_int, [P, I32, P]),
         "frecsys_set_transport": (ctypes.c_int, [P, P]),
         "frecsys_recommend": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
+        "frecsys_solve_side_cg": (ctypes.c_int, [P, I32, P, P]),
+        "frecsys_cg_iterations": (ctypes.c_int, [P, I32, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -408,6 +417,33 @@ class Context:
                          None if er is None else er.ctypes.data,
                          None if ow is None else ow.ctypes.data)
         self._check(self.lib.frecsys_solve_side(self.h, side, ctypes.byref(p)))
+
+    def solve_side_cg(self, side: int, kind: int, reg: float, unobserved_weight: float,
+                      max_iterations: int = 100, tolerance: float = 1e-10,
+                      reg_exp: float = 1.0, alpha: float = 0.0, from_snapshot: bool = False,
+                      lambda_is_reg: bool = False, entity_weight=None, entity_reg=None,
+                      other_weight=None):
+        """solve_side by Jacobi-preconditioned conjugate gradients from a zero
+        start (frecsys_solve_side_cg): stops at ||r||^2 < tolerance^2 ||b||^2
+        or after max_iterations."""
+        ew = None if entity_weight is None else np.ascontiguousarray(entity_weight, np.float32)
+        er = None if entity_reg is None else np.ascontiguousarray(entity_reg, np.float32)
+        ow = None if other_weight is None else np.ascontiguousarray(other_weight, np.float32)
+        p = _SolveParams(kind, reg, reg_exp, unobserved_weight, alpha, 0.0,
+                         1 if from_snapshot else 0, 1 if lambda_is_reg else 0,
+                         None if ew is None else ew.ctypes.data,
+                         None if er is None else er.ctypes.data,
+                         None if ow is None else ow.ctypes.data)
+        cg = _CgParams(max_iterations, tolerance)
+        self._check(self.lib.frecsys_solve_side_cg(self.h, side, ctypes.byref(p),
+                                                   ctypes.byref(cg)))
+
+    def cg_iterations(self, side: int) -> np.ndarray:
+        """int32 [rows of side]: the iteration count of the last solve_side_cg
+        per row; -1 for a row not solved here."""
+        out = np.full(max(self.n[side], 1), -1, dtype=np.int32)
+        self._check(self.lib.frecsys_cg_iterations(self.h, side, _ptr(out)))
+        return out[:self.n[side]]
 
     def user_loss(self, side: int, beta: float, half: bool, fetch: bool = True):
         out = np.zeros(self.n[side], dtype=np.float32) if fetch else None

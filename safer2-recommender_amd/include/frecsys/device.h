@@ -134,7 +134,23 @@ class DeviceContext {
   void InvalidateGramian(int side) { gram_valid_[side] = false; }
 
   // ---- the per-entity solve loop of one side ----
+  // use_cg: every Solve() runs the conjugate-gradient path
+  // (frecsys_solve_side_cg) with these settings -- the reference passes its
+  // use_cg_ / cg_error_tolerance_ / cg_max_iterations_ to every Project* call
+  // (ials.h:348-350, safer2.h:469-471, 535-537).
+  void SetCg(bool use_cg, float cg_error_tolerance, int cg_max_iterations) {
+    use_cg_ = use_cg;
+    cg_.tolerance = cg_error_tolerance;
+    cg_.max_iterations = cg_max_iterations;
+  }
+  bool use_cg() const { return use_cg_; }
+
   void Solve(int side, const frecsys_solve_params& p) {
+    if (use_cg_) {
+      check(frecsys_solve_side_cg(ctx_, side, &p, &cg_), "solve_side_cg");
+      if (side != EVAL) bump(side);
+      return;
+    }
     int rc = frecsys_solve_side(ctx_, side, &p);
     if (rc == FRECSYS_ERR_NOT_SPD) {
       // reference: assert(cholesky.info() == Eigen::Success), ials.h:141
@@ -268,6 +284,8 @@ class DeviceContext {
   int pp_tuples_ = -1;
   uint64_t gram_key_[2] = {0, 0};
   bool gram_valid_[2] = {false, false};
+  bool use_cg_ = false;
+  frecsys_cg_params cg_{100, 1e-10f};
 };
 
 inline frecsys_solve_params solve_params(int kind, float reg, float w) {

@@ -21,8 +21,7 @@ class ERMMFRecommender : public detail::DeviceModel {
                    float cg_error_tolerance, int cg_max_iterations,
                    const DeviceOptions& opts = DeviceOptions::FromEnv())
       : DeviceModel(embedding_dim, num_users, num_items, stdev, opts) {
-    if (use_cg)  // BiCGSTAB path (erm_mf.h:138-145): not built
-      LOG(FATAL) << "use_cg is not supported by the MI355X solve loop (LLT path only)";
+    RejectCg(use_cg);
     (void)cg_error_tolerance;
     (void)cg_max_iterations;
     regularization_ = reg;
@@ -42,12 +41,23 @@ class ERMMFRecommender : public detail::DeviceModel {
   static const VectorXf ProjectU(const SpVector& h, const MatrixXf& X, const MatrixXf& G,
                                  const float reg, const float w, const float weight, bool use_cg,
                                  const float = 1e-10, const int = 100) {
-    return SAFER2Recommender::ProjectU(h, X, G, reg, w, weight, use_cg);
+    RejectCg(use_cg);
+    return SAFER2Recommender::ProjectU(h, X, G, reg, w, weight, false);
   }
   static const VectorXf ProjectV(const SpVector& h, const MatrixXf& X, const MatrixXf& G,
                                  const float reg, const float w, const VectorXf& dw, bool use_cg,
                                  const float = 1e-10, const int = 100) {
-    return SAFER2Recommender::ProjectV(h, X, G, reg, w, dw, use_cg);
+    RejectCg(use_cg);
+    return SAFER2Recommender::ProjectV(h, X, G, reg, w, dw, false);
+  }
+  // the statics delegate to SAFER2's LLT form only: SAFER2's use_cg is
+  // conjugate gradients, not ERM-MF's BiCGSTAB (erm_mf.h:138-145, 197-204)
+  static void RejectCg(bool use_cg) {
+    if (use_cg)
+      LOG(FATAL) << "use_cg is not supported for ERM-MF: the reference runs BiCGSTAB there, on a "
+                    "matrix whose upper triangle lacks the rank updates (erm_mf.h:103-145) -- a "
+                    "different algorithm on a different matrix than the conjugate-gradient path "
+                    "of iALS / SAFER2";
   }
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,

@@ -67,6 +67,7 @@ inline Recommender* MakeRecommender(const std::string& name, int num_users, int 
                                 a.pd_iterations, a.use_epanechnikov, a.use_snr,
                                 a.sampling_ratio, a.block_size, o);
   } else if (name == "erm_mf") {
+    ERMMFRecommender::RejectCg(a.use_cg);  // before the device context exists
     r = new ERMMFRecommender(a.dim, num_users, num_items, a.l2_reg, a.uobs_weight, a.stdev,
                              a.alpha, a.use_cg, a.cg_error_tolerance, a.cg_max_iterations, o);
   } else if (name == "cvar_mf") {

@@ -21,10 +21,9 @@ class IALSRecommender : public detail::DeviceModel {
                   float cg_error_tolerance, int cg_max_iterations,
                   const DeviceOptions& opts = DeviceOptions::FromEnv())
       : DeviceModel(embedding_dim, num_users, num_items, stdev, opts) {
-    if (use_cg)  // Eigen ConjugateGradient path (ials.h:133-139): not built
-      LOG(FATAL) << "use_cg is not supported by the MI355X solve loop (LLT path only)";
-    (void)cg_error_tolerance;
-    (void)cg_max_iterations;
+    // Eigen ConjugateGradient path (ials.h:133-139): every Step, the fold-in
+    // included, passes use_cg_ (ials.h:348-350)
+    dev_->SetCg(use_cg, cg_error_tolerance, cg_max_iterations);
     regularization_ = reg;
     regularization_exp_ = reg_exp;
     unobserved_weight_ = unobserved_weight;
@@ -42,11 +41,9 @@ class IALSRecommender : public detail::DeviceModel {
                                 const float unobserved_weight, bool use_cg,
                                 const float cg_error_tolerance = 1e-10,
                                 const int cg_max_iterations = 100) {
-    (void)cg_error_tolerance;
-    (void)cg_max_iterations;
-    if (use_cg) LOG(FATAL) << "use_cg is not supported";
     return detail::ProjectOnDevice(FRECSYS_KIND_IALS, user_history, item_embeddings, gramian,
-                                   reg, unobserved_weight, 1.0f, nullptr);
+                                   reg, unobserved_weight, 1.0f, nullptr, use_cg,
+                                   cg_error_tolerance, cg_max_iterations);
   }
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,

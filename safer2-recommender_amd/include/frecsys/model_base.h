@@ -253,12 +253,14 @@ inline void check_ok(int rc) {
 // `reg` used as the final lambda.
 inline VectorXf ProjectOnDevice(int kind, const SpVector& history, const MatrixXf& X,
                                 const MatrixXf& G, float reg, float w, float weight,
-                                const VectorXf* nu) {
+                                const VectorXf* nu, bool use_cg = false,
+                                float cg_error_tolerance = 1e-10f, int cg_max_iterations = 100) {
   const int d = (int)X.cols();
   DeviceOptions o;
   o.world = 1;
   o.rank = 0;
   DeviceContext ctx(d, 1, X.rows(), o);
+  ctx.SetCg(use_cg, cg_error_tolerance, cg_max_iterations);
   Csr c;
   c.ptr = {0, (int64_t)history.size()};
   for (const auto& p : history) c.col.push_back(p.first);

@@ -158,9 +158,9 @@ class SAFER2Recommender : public detail::DeviceModel {
                     int cg_max_iterations, const DeviceOptions& opts = DeviceOptions::FromEnv())
       : DeviceModel(embedding_dim, num_users, num_items, stdev, opts),
         smoother_{alpha, bandwidth, use_epanechnikov} {
-    if (use_cg) LOG(FATAL) << "use_cg is not supported by the MI355X solve loop (LLT path only)";
-    (void)cg_error_tolerance;
-    (void)cg_max_iterations;
+    // Eigen ConjugateGradient path (safer2.h:152-157, 210-215): StepU (the
+    // fold-in included) and StepV pass use_cg_ (safer2.h:469-471, 535-537)
+    dev_->SetCg(use_cg, cg_error_tolerance, cg_max_iterations);
     regularization_ = reg;
     unobserved_weight_ = unobserved_weight;
     bandwidth_ = bandwidth;
@@ -186,18 +186,20 @@ class SAFER2Recommender : public detail::DeviceModel {
   static const VectorXf ProjectU(const SpVector& user_history, const MatrixXf& item_embeddings,
                                  const MatrixXf& gramian, const float reg,
                                  const float unobserved_weight, const float weight, bool use_cg,
-                                 const float = 1e-10, const int = 100) {
-    if (use_cg) LOG(FATAL) << "use_cg is not supported";
+                                 const float cg_error_tolerance = 1e-10,
+                                 const int cg_max_iterations = 100) {
     return detail::ProjectOnDevice(FRECSYS_KIND_WEIGHTED_U, user_history, item_embeddings,
-                                   gramian, reg, unobserved_weight, weight, nullptr);
+                                   gramian, reg, unobserved_weight, weight, nullptr, use_cg,
+                                   cg_error_tolerance, cg_max_iterations);
   }
   static const VectorXf ProjectV(const SpVector& item_history, const MatrixXf& user_embeddings,
                                  const MatrixXf& gramian, const float reg,
                                  const float unobserved_weight, const VectorXf& dual_weight,
-                                 bool use_cg, const float = 1e-10, const int = 100) {
-    if (use_cg) LOG(FATAL) << "use_cg is not supported";
+                                 bool use_cg, const float cg_error_tolerance = 1e-10,
+                                 const int cg_max_iterations = 100) {
     return detail::ProjectOnDevice(FRECSYS_KIND_WEIGHTED_V, item_history, user_embeddings,
-                                   gramian, reg, unobserved_weight, 1.0f, &dual_weight);
+                                   gramian, reg, unobserved_weight, 1.0f, &dual_weight, use_cg,
+                                   cg_error_tolerance, cg_max_iterations);
   }
 
   EvaluationResult EvaluateDataset(const VectorXi& k_list, const VectorXf& alpha_list,

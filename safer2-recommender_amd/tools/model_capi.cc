@@ -55,6 +55,9 @@ void frecsys_model_config_default(frecsys_model_config* c) {
   c->world = 0;
   c->rank = -1;
   c->comm_id = nullptr;
+  c->use_cg = p.use_cg;
+  c->cg_error_tolerance = p.cg_error_tolerance;
+  c->cg_max_iterations = p.cg_max_iterations;
 }
 
 int frecsys_model_create(const frecsys_model_config* c, const int32_t* users, const int32_t* items,
@@ -70,6 +73,18 @@ int frecsys_model_create(const frecsys_model_config* c, const int32_t* users, co
   for (int64_t k = 0; k < n_tuples; ++k)
     if (users[k] < 0 || items[k] < 0)
       return model_fail(FRECSYS_ERR_INVALID, "negative id in tuple " + std::to_string(k));
+  const bool cg_model = name == "ials" || name == "safer2";
+  if (c->use_cg && name == "erm_mf")  // fatal in the C++ constructor; before any device call
+    return model_fail(FRECSYS_ERR_UNSUPPORTED,
+                      "erm_mf: use_cg is not supported (the reference's BiCGSTAB path, "
+                      "erm_mf.h:103-145, is not built)");
+  if (c->use_cg && cg_model &&
+      (c->cg_max_iterations < 0 || !(c->cg_error_tolerance >= 0.0f)))
+    return model_fail(FRECSYS_ERR_INVALID,
+                      "cg_max_iterations and cg_error_tolerance must be >= 0 (and not NaN)");
+  if (c->use_cg && cg_model && c->dim > 256)
+    return model_fail(FRECSYS_ERR_UNSUPPORTED,
+                      "use_cg: the conjugate-gradient path is built for dim <= 256");
   int32_t ndev = 0;  // the C++ layer aborts on a missing device; report it instead
   if (frecsys_device_count(&ndev) != FRECSYS_OK || ndev == 0)
     return model_fail(FRECSYS_ERR_NO_DEVICE, "no HIP device visible");
@@ -91,6 +106,9 @@ int frecsys_model_create(const frecsys_model_config* c, const int32_t* users, co
   p.print_train_stats = c->print_train_stats != 0;
   p.print_residual_stats = c->print_residual_stats != 0;
   p.print_var_stats = c->print_var_stats != 0;
+  p.use_cg = c->use_cg != 0;
+  p.cg_error_tolerance = c->cg_error_tolerance;
+  p.cg_max_iterations = c->cg_max_iterations;
   frecsys::DeviceOptions o;
   o.seed = c->seed;
   o.device = c->device;
