@@ -345,6 +345,60 @@ int frecsys_eval_topk(frecsys_ctx* ctx, int32_t k, int32_t* topk);
 int frecsys_recommend(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                       int32_t k, int32_t flags, const uint8_t* item_mask, int32_t* items,
                       float* scores);
+/* Recall@K and NDCG@K of ranked lists on the host: the reference's
+ * RankMetrics (recommender.h:152-182), once for every caller.  No context and
+ * no HIP call: works on a machine without a GPU, like frecsys_partition.
+ * Row i has the ranked list lists[i*list_k .. i*list_k+list_k) (-1: an empty
+ * slot, never a hit) and the ground truth = the DISTINCT ids of
+ * gt_items[gt_ptr[i] .. gt_ptr[i+1]), g of them.  For cut-off k = k_list[q]:
+ * hits and dcg are double sums over the positions j < min(k, list_k) in
+ * ascending j (dcg adds 1.0 / log2(j + 2.0)), norm the double sum of the same
+ * terms for j < min(k, g), recall[i*nk+q] = (float)(hits / min((float)k,
+ * (float)g)), ndcg[i*nk+q] = (float)(dcg / norm).  1 <= nk <= 32,
+ * 1 <= k_list[q] <= 1024, any order, repeats allowed.  FRECSYS_ERR_INVALID: a
+ * null pointer, gt_ptr[0] != 0 or a non-monotone gt_ptr, a negative
+ * ground-truth id, a row with no ground truth (the reference's eval_by_user
+ * holds none; 0 / 0 would poison the CVaR sort), list_k < max k_list. */
+int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                         float* recall, float* ndcg);
+/* Lower-tail CVaR of n per-user metric values at each of na alphas:
+ * EvaluationResult::cvar (evaluation.h:83-102) verbatim, host only.  The
+ * values are sorted ascending and summed sequentially in fp32; at sorted
+ * position i, for j = counter .. na-1: where (int)((float)n * alphas[j]) == i,
+ * out[counter++] = sum / (float)(i + 1).  The reference's quirks follow and
+ * stay: results fill out[] in match order, not at index j; an alpha whose
+ * position is >= n (alpha = 1) leaves its slot 0; with unsorted alphas the
+ * later slots stay 0.  out: [na]. */
+int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int32_t na,
+                        float* out);
+/* Evaluation on the device: frecsys_list_metrics of frecsys_recommend's
+ * ranking with k = max(k_list), bitwise, without the lists leaving the
+ * device.  side, rows, flags and item_mask mean what they mean for
+ * frecsys_recommend; ground-truth row i (gt_items[gt_ptr[i] .. gt_ptr[i+1]))
+ * belongs to query row i (not to side row rows[i]); recall, ndcg: host
+ * [n_rows * nk].  An excluded or masked item is never listed, so never a hit.
+ * Per row batch the fused scan of frecsys_recommend runs, then one kernel
+ * (one wave per row: binary search of each rank in the row's sorted distinct
+ * ground truth, one ballot per 64 ranks, one lane per cut-off) reads the lists
+ * where the scan left them, and 2 nk floats per row are copied back.  Equality
+ * with the host function holds because every device operation is an IEEE
+ * double add, divide or convert on the host's own operands (the 1/log2 terms
+ * and their prefix sums are uploaded from the host) in the host's order.
+ * Workspace: frecsys_recommend's, the batch sized by FRECSYS_RECOMMEND_WS_MB
+ * with 8 nk more bytes per row, and outside that budget 8 (n_rows + 1) +
+ * 4 (ground-truth ids) + 16,392 (tables) + 4 nk bytes: the ground truth,
+ * sorted and de-duplicated per row on host threads while the first batch is
+ * scanned, and uploaded once per call.  FRECSYS_RECOMMEND_WS_MB / _SPLITS are read per call and change no
+ * result bit.  Rank-local at any world size.  FRECSYS_ERR_INVALID:
+ * frecsys_recommend's cases, frecsys_list_metrics' cases, a ground-truth id
+ * >= n_items.  Timer key "rank_metrics": the metric kernel only (the scan
+ * keeps "recommend"); frecsys_work("rank_metrics"): 2 rows nk flops (the
+ * divisions), bytes = lists and ground truth read, metric rows written. */
+int frecsys_rank_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                         int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                         float* recall, float* ndcg);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,

@@ -109,6 +109,36 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                     const int32_t* hist_items, int64_t n, int32_t k,
                                     int32_t exclude_seen, const uint8_t* item_mask,
                                     int32_t* items, float* scores);
+/* Ranking quality of n trained users (users[i]: a row of U) against their
+ * ground truth (gt_items[gt_ptr[i] .. gt_ptr[i+1]): the held-out items of
+ * users[i]; not empty): Recall@K and NDCG@K of frecsys_model_recommend's
+ * ranking at each of the nk cut-offs of k_list, computed on the device
+ * (frecsys_rank_metrics, frecsys_hip.h: the reference's RankMetrics,
+ * recommender.h:152-182), recall / ndcg: host [n * nk].  summary: host
+ * [(2 + 2 na) * nk] or NULL -- mean recall [nk], mean ndcg [nk], recall CVaR
+ * [na][nk], ndcg CVaR [na][nk]: what EvaluationResult::show() logs, from its
+ * own colwise().mean() (double sum in row order) and cvar()
+ * (evaluation.h:83-102, quirks included: see frecsys_metric_cvar).
+ * exclude_seen != 0 drops each user's training history from the ranking.
+ * Errors are frecsys_rank_metrics', reported before any device call. */
+int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
+                           const int64_t* gt_ptr, const int32_t* gt_items,
+                           const int32_t* k_list, int32_t nk, const float* alpha_list,
+                           int32_t na, int32_t exclude_seen, float* recall, float* ndcg,
+                           float* summary);
+/* The same for n unseen users given by their histories (as
+ * frecsys_model_recommend_fold_in): the model's fold-in projection into the
+ * EVAL side of its context, where the projected rows stay, then the metrics
+ * of those rows; ground-truth row i belongs to history row i; exclude_seen
+ * drops the given history.  This is the reference's EvaluateDataset
+ * (recommender.h:78-199) with the ranking and the metrics on the device. */
+int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                   const int32_t* hist_items, int64_t n,
+                                   const int64_t* gt_ptr, const int32_t* gt_items,
+                                   const int32_t* k_list, int32_t nk,
+                                   const float* alpha_list, int32_t na,
+                                   int32_t exclude_seen, float* recall, float* ndcg,
+                                   float* summary);
 void frecsys_model_destroy(frecsys_model* m);
 const char* frecsys_model_last_error(void);
 

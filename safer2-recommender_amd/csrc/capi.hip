@@ -823,9 +823,15 @@ struct ScopedTimer {
   ScopedTimer(frecsys_ctx* c_, const char* n_) : c(c_), name(n_) {
     (void)hipEventRecord(c->ev0, c->stream);
   }
+  // The end of the timed work, for a caller that has host work to do while
+  // the device runs: mark(), the host work, then finish().
+  void mark() { (void)hipEventRecord(c->ev1, c->stream); }
   // Stops the timer: synchronises on the end event and accumulates.
   void stop() {
-    (void)hipEventRecord(c->ev1, c->stream);
+    mark();
+    finish();
+  }
+  void finish() {
     (void)hipEventSynchronize(c->ev1);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) {
@@ -2272,32 +2278,158 @@ int frecsys_eval_topk(frecsys_ctx* c, int32_t k, int32_t* topk) {
   return FRECSYS_OK;
 }
 
-int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
-                      int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
+}  // extern "C"
+
+namespace {
+
+// gain[j] = 1 / log2(j + 2) and its sequential prefix idcg[m] = gain[0] + ...
+// + gain[m-1] (idcg[0] = 0), in double with the host's std::log2: the terms
+// and the norm of RankMetrics (recommender.h:152-182) in its own order.
+struct MetricTables {
+  double gain[kMetricMaxK];
+  double idcg[kMetricMaxK + 1];
+};
+const MetricTables& metric_tables() {
+  static const MetricTables tab = [] {
+    MetricTables t;
+    t.idcg[0] = 0.0;
+    for (int j = 0; j < kMetricMaxK; ++j) {
+      t.gain[j] = 1.0 / std::log2(j + 2.0);
+      t.idcg[j + 1] = t.idcg[j] + t.gain[j];
+    }
+    return t;
+  }();
+  return tab;
+}
+
+// The argument checks frecsys_list_metrics and frecsys_rank_metrics share;
+// "" when fine.  n_items < 0: no upper bound on the ground-truth ids.
+std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
+                              const int32_t* k_list, int32_t nk, int64_t n_items,
+                              int32_t* max_k) {
+  if (n < 0 || !gt_ptr || !k_list) return "bad arguments (null gt_ptr / k_list, n < 0)";
+  if (nk < 1 || nk > kMetricMaxCutoffs)
+    return "nk must be in [1, " + std::to_string(kMetricMaxCutoffs) + "]";
+  int32_t mk = 0;
+  for (int32_t q = 0; q < nk; ++q) {
+    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
+      return "k_list[" + std::to_string(q) + "] must be in [1, " + std::to_string(kMetricMaxK) +
+             "]";
+    mk = std::max(mk, k_list[q]);
+  }
+  *max_k = mk;
+  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
+  for (int64_t i = 0; i < n; ++i) {
+    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
+    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
+  }
+  if (n > 0 && !gt_items) return "null gt_items";
+  for (int64_t p = 0; p < gt_ptr[n]; ++p)
+    if (gt_items[p] < 0 || (n_items >= 0 && gt_items[p] >= n_items))
+      return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
+  return "";
+}
+
+// The ground truth as sets: every row ascending and distinct.  Rows are sorted
+// in place in a copy (a row already strictly ascending is left alone), on host
+// threads over nnz-balanced row ranges when there is enough of it, then
+// closed up over the dropped repeats; the result does not depend on the
+// thread count.
+void sorted_ground_truth(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
+                         std::vector<int64_t>* sp, std::vector<int32_t>* sg) {
+  const int64_t total = gt_ptr[n];
+  sg->assign(gt_items, gt_items + total);
+  sp->assign((size_t)n + 1, 0);
+  std::vector<int64_t> cnt((size_t)n);
+  int32_t* base = sg->data();
+  auto work = [&](int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) {
+      int32_t* p = base + gt_ptr[i];
+      int32_t* e = base + gt_ptr[i + 1];
+      bool ascending = true;
+      for (int32_t* q = p + 1; q < e; ++q)
+        if (q[-1] >= q[0]) {
+          ascending = false;
+          break;
+        }
+      if (!ascending) {
+        std::sort(p, e);
+        e = std::unique(p, e);
+      }
+      cnt[(size_t)i] = e - p;
+    }
+  };
+  const int nt = total < (1 << 16)
+                     ? 1
+                     : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  if (nt == 1) {
+    work(0, n);
+  } else {
+    std::vector<int64_t> bounds((size_t)nt + 1);
+    partition_rows(n, gt_ptr, nt, bounds.data());
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, bounds[(size_t)t], bounds[(size_t)t + 1]);
+    for (auto& t : th) t.join();
+  }
+  int64_t w = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (w != gt_ptr[i]) std::memmove(base + w, base + gt_ptr[i], sizeof(int32_t) * (size_t)cnt[(size_t)i]);
+    w += cnt[(size_t)i];
+    (*sp)[(size_t)i + 1] = w;
+  }
+  sg->resize((size_t)w);
+}
+
+// What frecsys_rank_metrics adds to the ranking of frecsys_recommend.
+struct MetricsRequest {
+  const int64_t* gt_ptr;
+  const int32_t* gt_items;
+  const int32_t* k_list;
+  int32_t nk;
+  float* recall;
+  float* ndcg;
+};
+
+// The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
+// to the host) and frecsys_rank_metrics (mt given: every batch's lists stay on
+// the device, the metric kernel reads them there and n x nk x 2 floats go to
+// the host).  The scan is the same launch with the same workspace layout in
+// both; the ground truth, the tables and the metric outputs lie behind it.
+int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
+                   int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
+                   int32_t* items, float* scores, const MetricsRequest* mt) {
+  const std::string w = std::string(what) + ": ";
   if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: side must be USER or EVAL");
-  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, "recommend: k must be in [1, 1024]");
+    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
+  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
   if (flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: unknown flag");
-  if (n_rows < 0 || (n_rows > 0 && !items))
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: bad arguments (null outputs)");
+    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  if (n_rows < 0 || (n_rows > 0 && (mt ? (!mt->recall || !mt->ndcg) : !items)))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
   const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
   if (exclude && !c->rp[side])
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: exclude flag on a side with no CSR loaded");
+    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
   if (!c->emb[side] || !c->emb[1])
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: side has no embeddings yet");
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
   const int64_t ns = c->n[side], m = c->n[1], n = n_rows;
   if (rows) {
     for (int64_t i = 0; i < n; ++i)
       if (rows[i] < 0 || rows[i] >= ns)
         return fail(c, FRECSYS_ERR_INVALID,
-                    "recommend: row id " + std::to_string(rows[i]) + " out of range");
+                    w + "row id " + std::to_string(rows[i]) + " out of range");
   } else if (n > ns) {
-    return fail(c, FRECSYS_ERR_INVALID, "recommend: more rows than the side has");
+    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
   }
-  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, "recommend: no items");
+  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
+  std::vector<int64_t> gt_sp;
+  std::vector<int32_t> gt_sg;
+  if (mt) {
+    int32_t mk = 0;
+    const std::string e = metric_args_error(n, mt->gt_ptr, mt->gt_items, mt->k_list, mt->nk, m, &mk);
+    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  }
   if (n == 0) return FRECSYS_OK;
+  const size_t nk = mt ? (size_t)mt->nk : 0;
   HIP_TRY(c, hipSetDevice(c->device));
   // knobs, read per call
   int64_t ws_mb = 256;
@@ -2315,9 +2447,10 @@ int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t
   const int cap = recommend_cap(k);
   const int64_t W = recommend_words(m);
   auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  // per row of a batch: candidates, counts, history bits, outputs
+  // per row of a batch: candidates, counts, history bits, outputs (and the
+  // two metric rows)
   const size_t per_row = (size_t)splits * cap * 8 + (size_t)splits * 4 +
-                         (exclude ? (size_t)W * 4 : 0) + (size_t)k * 8;
+                         (exclude ? (size_t)W * 4 : 0) + (size_t)k * 8 + nk * 8;
   int64_t nb = std::max<int64_t>(1, (int64_t)(((size_t)ws_mb << 20) / per_row));
   if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
   nb = std::min(nb, n);
@@ -2328,7 +2461,19 @@ int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t
   const size_t o_scores = up16(o_items + (size_t)nb * k * 4);
   const size_t o_mask = up16(o_scores + (size_t)nb * k * 4);
   const size_t o_qrows = up16(o_mask + (size_t)W * 4);
-  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
+  size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
+  // behind the ranking's workspace: ground truth, tables, cut-offs, metric rows
+  size_t o_gtptr = 0, o_gt = 0, o_gain = 0, o_idcg = 0, o_klist = 0, o_recall = 0, o_ndcg = 0;
+  if (mt) {
+    o_gtptr = up16(total);
+    o_gt = up16(o_gtptr + ((size_t)n + 1) * 8);
+    o_gain = up16(o_gt + (size_t)mt->gt_ptr[n] * 4);  // room for every id; repeats are dropped
+    o_idcg = up16(o_gain + sizeof(double) * kMetricMaxK);
+    o_klist = up16(o_idcg + sizeof(double) * (kMetricMaxK + 1));
+    o_recall = up16(o_klist + nk * 4);
+    o_ndcg = up16(o_recall + (size_t)nb * nk * 4);
+    total = o_ndcg + (size_t)nb * nk * 4;
+  }
   int rc = ensure(c, &c->d_rec, &c->cap_rec, total);
   if (rc) return rc;
   // eligibility bits of the items: the mask and id < n_items
@@ -2358,12 +2503,57 @@ int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t
   a.counts = (int32_t*)(c->d_rec + o_counts);
   a.out_items = (int32_t*)(c->d_rec + o_items);
   a.out_scores = (float*)(c->d_rec + o_scores);
+  RankMetricsArgs ma{};
+  if (mt) {
+    ma.lists = a.out_items;
+    ma.k = k;
+    ma.gt_ptr = (const int64_t*)(c->d_rec + o_gtptr);
+    ma.gt = (const int32_t*)(c->d_rec + o_gt);
+    ma.k_list = (const int32_t*)(c->d_rec + o_klist);
+    ma.nk = (int)nk;
+    ma.gain = (const double*)(c->d_rec + o_gain);
+    ma.idcg = (const double*)(c->d_rec + o_idcg);
+    ma.recall = (float*)(c->d_rec + o_recall);
+    ma.ndcg = (float*)(c->d_rec + o_ndcg);
+  }
   for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
     a.r0 = r0;
     a.n = std::min(nb, n - r0);
     ScopedTimer t(c, "recommend");
     HIP_TRY(c, launch_recommend(a, c->stream));
-    t.stop();
+    if (mt && r0 == 0) {
+      // the ground truth is sorted on the host while the first batch is
+      // scanned, and uploaded behind it with the tables and the cut-offs
+      t.mark();
+      sorted_ground_truth(n, mt->gt_ptr, mt->gt_items, &gt_sp, &gt_sg);
+      const MetricTables& tab = metric_tables();
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gtptr, gt_sp.data(), sizeof(int64_t) * ((size_t)n + 1),
+                                hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gt, gt_sg.data(), sizeof(int32_t) * gt_sg.size(),
+                                hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gain, tab.gain, sizeof(tab.gain),
+                                hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_idcg, tab.idcg, sizeof(tab.idcg),
+                                hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_klist, mt->k_list, sizeof(int32_t) * nk,
+                                hipMemcpyHostToDevice, c->stream));
+      t.finish();
+    } else {
+      t.stop();
+    }
+    if (mt) {  // the lists stay on the device: only the metric rows come back
+      ma.r0 = r0;
+      ma.n = a.n;
+      ScopedTimer tm(c, "rank_metrics");
+      HIP_TRY(c, launch_rank_metrics(ma, c->stream));
+      tm.stop();
+      HIP_TRY(c, hipMemcpyAsync(mt->recall + r0 * nk, ma.recall, sizeof(float) * a.n * nk,
+                                hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(mt->ndcg + r0 * nk, ma.ndcg, sizeof(float) * a.n * nk,
+                                hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      continue;
+    }
     HIP_TRY(c, hipMemcpyAsync(items + r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
                               hipMemcpyDeviceToHost, c->stream));
     if (scores)
@@ -2375,6 +2565,105 @@ int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t
   const double dd = c->dim;
   add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
            ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  // metrics: two double divisions per (row, cut-off); bytes: the lists and the
+  // ground truth read, the metric rows written
+  if (mt)
+    add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
+             (double)n * k * 4.0 + (double)gt_sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
+                 (double)n * (double)nk * 8.0,
+             n);
+  return FRECSYS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
+                      int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
+  return recommend_impl(c, "recommend", side, rows, n_rows, k, flags, item_mask, items, scores,
+                        nullptr);
+}
+
+int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                         int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
+                         float* ndcg) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: null context");
+  // the list length is the largest cut-off
+  if (!k_list || nk < 1 || nk > kMetricMaxCutoffs)
+    return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: k_list must hold 1 to " +
+                                            std::to_string(kMetricMaxCutoffs) + " cut-offs");
+  int32_t k = 0;
+  for (int32_t q = 0; q < nk; ++q) {
+    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
+      return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: cut-offs must be in [1, 1024]");
+    k = std::max(k, k_list[q]);
+  }
+  const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
+  return recommend_impl(c, "rank_metrics", side, rows, n_rows, k, flags, item_mask, nullptr, nullptr,
+                        &mt);
+}
+
+int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
+                         float* ndcg) {
+  int32_t mk = 0;
+  const std::string e = metric_args_error(n, gt_ptr, gt_items, k_list, nk, -1, &mk);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: " + e);
+  if (list_k < mk)
+    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: list_k is below the largest cut-off");
+  if (n > 0 && (!lists || !recall || !ndcg))
+    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: bad arguments (null lists / outputs)");
+  const MetricTables& tab = metric_tables();
+  std::vector<int64_t> sp;
+  std::vector<int32_t> sg;
+  sorted_ground_truth(n, gt_ptr, gt_items, &sp, &sg);
+  std::vector<uint8_t> hit((size_t)mk);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t* g0 = sg.data() + sp[(size_t)i];
+    const int32_t* g1 = sg.data() + sp[(size_t)i + 1];
+    const int64_t g = g1 - g0;
+    const int32_t* list = lists + i * list_k;
+    for (int32_t j = 0; j < mk; ++j)  // -1: an empty slot, never a hit
+      hit[(size_t)j] = list[j] >= 0 && std::binary_search(g0, g1, list[j]);
+    for (int32_t q = 0; q < nk; ++q) {
+      const int32_t kq = k_list[q];  // <= mk <= list_k
+      double hits = 0.0, dcg = 0.0;
+      for (int32_t j = 0; j < kq; ++j)
+        if (hit[(size_t)j]) {
+          hits += 1.0;
+          dcg += tab.gain[j];
+        }
+      const double norm = tab.idcg[std::min<int64_t>(kq, g)];
+      recall[i * nk + q] = (float)(hits / std::min<float>((float)kq, (float)g));
+      ndcg[i * nk + q] = (float)(dcg / norm);
+    }
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int32_t na,
+                        float* out) {
+  if (n < 0 || na < 0 || (n > 0 && !values) || (na > 0 && (!alphas || !out)))
+    return fail(nullptr, FRECSYS_ERR_INVALID, "metric_cvar: bad arguments");
+  // EvaluationResult::cvar (evaluation.h:83-102), verbatim
+  std::vector<float> ms(values, values + n);
+  std::sort(ms.begin(), ms.end());
+  for (int32_t j = 0; j < na; ++j) out[j] = 0.0f;
+  int64_t counter = 0;
+  float acc = 0.0f;
+  for (int64_t i = 0; i < n; ++i) {
+    acc += ms[(size_t)i];
+    for (int64_t j = counter; j < na; ++j) {
+      const int pos = (int)((float)n * alphas[j]);
+      if (pos == i) {
+        out[counter] = acc / (float)(i + 1);
+        counter++;
+      }
+    }
+  }
   return FRECSYS_OK;
 }
 

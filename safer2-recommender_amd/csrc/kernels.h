@@ -360,6 +360,29 @@ int64_t recommend_words(int64_t m);
 int recommend_max_splits(int k, int64_t m);
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
 
+// Recall@K / NDCG@K of ranked lists in device memory (metrics.hip): query row
+// i of the batch has the list lists[i*k .. i*k+k) (-1 = empty slot, never a
+// hit) and the ground truth gt[gt_ptr[r0+i] .. gt_ptr[r0+i+1]) -- ascending,
+// distinct, not empty.  gain[j] = 1 / log2(j + 2) and its sequential prefix
+// idcg[m] = gain[0] + ... + gain[m-1] are the host's tables (double), so that
+// the results are frecsys_list_metrics' bit for bit.
+constexpr int kMetricMaxK = 1024;      // largest cut-off (frecsys_recommend's k limit)
+constexpr int kMetricMaxCutoffs = 32;  // cut-offs per call (one lane each)
+struct RankMetricsArgs {
+  const int32_t* lists;     // [n][k]
+  int64_t r0, n;            // this batch: query rows r0 .. r0 + n - 1
+  int k;                    // list length = max k_list, 1 .. kMetricMaxK
+  const int64_t* gt_ptr;    // [rows of the call + 1]
+  const int32_t* gt;
+  const int32_t* k_list;    // [nk], each 1 .. k
+  int nk;                   // 1 .. kMetricMaxCutoffs
+  const double* gain;       // [kMetricMaxK]
+  const double* idcg;       // [kMetricMaxK + 1]
+  float* recall;            // [n][nk]
+  float* ndcg;              // [n][nk]
+};
+hipError_t launch_rank_metrics(const RankMetricsArgs& a, hipStream_t s);
+
 // Wide dims, Dp = 512 / 1024 (wide.hip).  d-space solve with A in an HBM
 // workspace ([batch][wide_slot_floats(Dp)]), entities a.order[0..n_rows)
 // in batches; Gramian by 128x128 block pairs; per-step tridiagonalisation

@@ -19,6 +19,9 @@ import numpy as np
 
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
 REC_EXCLUDE_HISTORY = 1
+# the cut-offs and tail levels run_model evaluates (run_model.cc:97-100)
+EVAL_K_LIST = (5, 10, 20, 50, 100)
+EVAL_ALPHA_LIST = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
 KIND_IALS, KIND_WEIGHTED_U, KIND_WEIGHTED_V, KIND_CVAR_GRAD_U, KIND_CVAR_GRAD_V = range(5)
 
 OK = 0
@@ -43,7 +46,8 @@ EXPORTS = (
     "frecsys_gram_plan", "frecsys_work", "frecsys_snapshot_residual", "frecsys_counter",
     "frecsys_pp_sync", "frecsys_release_workspaces", "frecsys_pp_get_predictions",
     "frecsys_set_transport", "frecsys_recommend", "frecsys_solve_side_cg",
-    "frecsys_cg_iterations",
+    "frecsys_cg_iterations", "frecsys_list_metrics", "frecsys_metric_cvar",
+    "frecsys_rank_metrics",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -52,6 +56,7 @@ MODEL_EXPORTS = (
     "frecsys_model_train", "frecsys_model_context", "frecsys_model_mean_weight",
     "frecsys_model_destroy", "frecsys_model_last_error", "frecsys_model_dual_state",
     "frecsys_model_recommend", "frecsys_model_recommend_fold_in",
+    "frecsys_model_evaluate", "frecsys_model_evaluate_fold_in",
 )
 
 
@@ -171,6 +176,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_recommend": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
         "frecsys_solve_side_cg": (ctypes.c_int, [P, I32, P, P]),
         "frecsys_cg_iterations": (ctypes.c_int, [P, I32, P]),
+        "frecsys_list_metrics": (ctypes.c_int, [P, I64, I32, P, P, P, I32, P, P]),
+        "frecsys_metric_cvar": (ctypes.c_int, [P, I64, P, I32, P]),
+        "frecsys_rank_metrics": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, I32, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -202,6 +210,10 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_dual_state": (ctypes.c_int, [P, P, P, P, P]),
         "frecsys_model_recommend": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
         "frecsys_model_recommend_fold_in": (ctypes.c_int, [P, P, P, I64, I32, I32, P, P, P]),
+        "frecsys_model_evaluate": (ctypes.c_int,
+                                   [P, P, I64, P, P, P, I32, P, I32, I32, P, P, P]),
+        "frecsys_model_evaluate_fold_in": (ctypes.c_int,
+                                           [P, P, P, I64, P, P, P, I32, P, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -248,6 +260,45 @@ def gram_plan(dim: int, n_rows: int, world: int = 1, rank: int = 0):
     if rc:
         raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
     return int(rpl.value), int(nl.value), int(ng.value), int(lo.value), int(hi.value)
+
+
+def _ground_truth(gt_ptr, gt_items):
+    gp = np.ascontiguousarray(gt_ptr, dtype=np.int64).reshape(-1)
+    gi = np.ascontiguousarray(gt_items, dtype=np.int32).reshape(-1)
+    return gp, gi
+
+
+def list_metrics(lists, gt_ptr, gt_items, k_list) -> Tuple[np.ndarray, np.ndarray]:
+    """(recall, ndcg) float32 [n, len(k_list)] of ranked lists (int32 [n,
+    list_k]; -1 = empty slot) against a CSR ground truth: the reference's
+    RankMetrics on the host (frecsys_list_metrics; no GPU needed)."""
+    lib = load_library()
+    ls = np.ascontiguousarray(lists, dtype=np.int32)
+    assert ls.ndim == 2, ls.shape
+    gp, gi = _ground_truth(gt_ptr, gt_items)
+    assert len(gp) == ls.shape[0] + 1, (len(gp), ls.shape)
+    ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+    rec = np.zeros((ls.shape[0], len(ks)), dtype=np.float32)
+    ndcg = np.zeros_like(rec)
+    rc = lib.frecsys_list_metrics(_ptr(ls), ls.shape[0], ls.shape[1], _ptr(gp), _ptr(gi),
+                                  _ptr(ks), len(ks), _ptr(rec), _ptr(ndcg))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    return rec, ndcg
+
+
+def metric_cvar(values, alphas) -> np.ndarray:
+    """float32 [len(alphas)]: the reference's lower-tail CVaR of per-user
+    metric values (EvaluationResult::cvar verbatim, quirks included --
+    frecsys_metric_cvar; no GPU needed)."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    a = np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
+    out = np.zeros(len(a), dtype=np.float32)
+    rc = lib.frecsys_metric_cvar(_ptr(v), len(v), _ptr(a), len(a), _ptr(out))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    return out
 
 
 def unique_id() -> bytes:
@@ -505,6 +556,30 @@ class Context:
                                                _ptr(mk), _ptr(items), _ptr(scores)))
         return items, scores
 
+    def rank_metrics(self, side: int, k_list, gt_ptr, gt_items, rows=None,
+                     exclude_history: bool = True,
+                     item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(recall, ndcg) float32 [n, len(k_list)]: list_metrics of
+        recommend(side, max(k_list), ...)'s ranking, bitwise, computed on the
+        GPU without the lists leaving it (frecsys_rank_metrics).  Ground-truth
+        row i (CSR gt_ptr / gt_items; not empty) belongs to query row i."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        rec = np.zeros((n, len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        self._check(self.lib.frecsys_rank_metrics(self.h, side, _ptr(r), n,
+                                                  REC_EXCLUDE_HISTORY if exclude_history else 0,
+                                                  _ptr(mk), _ptr(gp), _ptr(gi), _ptr(ks), len(ks),
+                                                  _ptr(rec), _ptr(ndcg)))
+        return rec, ndcg
+
     def pp_set_rating_index(self, side: int, rix: np.ndarray):
         r = np.ascontiguousarray(rix, dtype=np.int32)
         self._check(self.lib.frecsys_pp_set_rating_index(self.h, side, _ptr(r)))
@@ -705,6 +780,62 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return items, scores
+
+    @staticmethod
+    def _evaluation(n, ks, al, rec, ndcg, summary):
+        nk, na = len(ks), len(al)
+        return {"recall": rec, "ndcg": ndcg, "k_list": ks, "alpha_list": al,
+                "mean_recall": summary[:nk].copy(), "mean_ndcg": summary[nk:2 * nk].copy(),
+                "recall_cvar": summary[2 * nk:(2 + na) * nk].reshape(na, nk).copy(),
+                "ndcg_cvar": summary[(2 + na) * nk:].reshape(na, nk).copy()}
+
+    def evaluate(self, users, gt_ptr, gt_items, k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
+                 exclude_seen: bool = True):
+        """Ranking quality of trained users (frecsys_model_evaluate): a dict of
+        per-user "recall" and "ndcg" float32 [n, nk] and the summary the
+        reference logs -- "mean_recall", "mean_ndcg" [nk], "recall_cvar",
+        "ndcg_cvar" [na, nk] (EvaluationResult's means and cvar()).  Row i of
+        the CSR ground truth belongs to users[i]; the defaults are run_model's
+        (run_model.cc:97-100)."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == len(u) + 1, (len(gp), len(u))
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
+        rec = np.zeros((len(u), len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
+        rc = self.lib.frecsys_model_evaluate(self.h, _ptr(u), len(u), _ptr(gp), _ptr(gi),
+                                             _ptr(ks), len(ks), _ptr(al), len(al),
+                                             int(bool(exclude_seen)), _ptr(rec), _ptr(ndcg),
+                                             _ptr(summary))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return self._evaluation(len(u), ks, al, rec, ndcg, summary)
+
+    def evaluate_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items, k_list=EVAL_K_LIST,
+                         alpha_list=EVAL_ALPHA_LIST, exclude_seen: bool = True):
+        """The same for unseen users given by their histories (CSR hist_ptr /
+        hist_items): the model's fold-in projection, then the metrics of the
+        projected rows (frecsys_model_evaluate_fold_in) -- the reference's
+        EvaluateDataset.  The projected rows stay in the EVAL side."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
+        rec = np.zeros((n, len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
+        rc = self.lib.frecsys_model_evaluate_fold_in(self.h, _ptr(hp), _ptr(hi), n, _ptr(gp),
+                                                     _ptr(gi), _ptr(ks), len(ks), _ptr(al),
+                                                     len(al), int(bool(exclude_seen)), _ptr(rec),
+                                                     _ptr(ndcg), _ptr(summary))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return self._evaluation(n, ks, al, rec, ndcg, summary)
 
     def close(self):
         if getattr(self, "h", None):

@@ -222,6 +222,30 @@ class DeviceContext {
     return r;
   }
 
+  // Recall@K / NDCG@K of the ranking Recommend would return with
+  // k = max(k_list), computed on the device (frecsys_rank_metrics): recall,
+  // ndcg: host [n * nk]; ground-truth row i belongs to query row i.  The
+  // status code, for callers that report errors.
+  int TryRankMetrics(int side, const int64_t* rows, int64_t n, int flags, const uint8_t* mask,
+                     const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list, int nk,
+                     float* recall, float* ndcg) {
+    return frecsys_rank_metrics(ctx_, side, rows, n, flags, mask, gt_ptr, gt_items, k_list, nk,
+                                recall, ndcg);
+  }
+  struct Metrics {
+    MatrixXf recall, ndcg;  // rows x |k_list|
+  };
+  Metrics RankMetrics(int side, const std::vector<int64_t>& rows, int flags, const Csr& gt,
+                      const std::vector<int32_t>& k_list, const uint8_t* mask = nullptr) {
+    Metrics r{MatrixXf((int64_t)rows.size(), (int64_t)k_list.size()),
+              MatrixXf((int64_t)rows.size(), (int64_t)k_list.size())};
+    check(TryRankMetrics(side, rows.data(), (int64_t)rows.size(), flags, mask, gt.ptr.data(),
+                         gt.col.data(), k_list.data(), (int)k_list.size(), r.recall.data(),
+                         r.ndcg.data()),
+          "rank_metrics");
+    return r;
+  }
+
   // Per-user loss of `side` (USER or EVAL) against ITEM / G[ITEM].
   void UserLoss(int side, float beta, bool half, float* host_out) {
     check(frecsys_user_loss(ctx_, side, beta, half ? 1 : 0, host_out), "user_loss");

@@ -81,7 +81,38 @@ class DeviceModel : public Recommender {
                            exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
   }
 
+  // Ranking quality of trained users on the device (frecsys_rank_metrics):
+  // row i of `gt` is the ground truth of users[i]; Recall@K / NDCG@K of
+  // Recommend's ranking at every cut-off of k_list, per user, in the
+  // reference's EvaluationResult (show() prints its lines; cvar() its tail
+  // means).  Only the users x |k_list| metric rows leave the device.
+  EvaluationResult Evaluate(const std::vector<int64_t>& users, const Csr& gt,
+                            const VectorXi& k_list, const VectorXf& alpha_list,
+                            bool exclude_seen) {
+    return RankMetricsOf(DeviceContext::USER, users, gt, k_list, alpha_list, exclude_seen);
+  }
+  // The same for unseen users given by their histories: FoldIn, then the
+  // metrics of the EVAL rows (row i of `gt` belongs to row i of `csr`).  The
+  // projected rows stay in the EVAL side, as with RecommendFoldIn.
+  EvaluationResult EvaluateFoldIn(const Csr& csr, const Csr& gt, const VectorXi& k_list,
+                                  const VectorXf& alpha_list, bool exclude_seen) {
+    FoldIn(csr);
+    std::vector<int64_t> rows((size_t)csr.rows());
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = (int64_t)i;
+    return RankMetricsOf(DeviceContext::EVAL, rows, gt, k_list, alpha_list, exclude_seen);
+  }
+
  protected:
+  EvaluationResult RankMetricsOf(int side, const std::vector<int64_t>& rows, const Csr& gt,
+                                 const VectorXi& k_list, const VectorXf& alpha_list,
+                                 bool exclude_seen) {
+    std::vector<int32_t> ks((size_t)k_list.size());
+    for (size_t i = 0; i < ks.size(); ++i) ks[i] = k_list[(int64_t)i];
+    DeviceContext::Metrics m = dev_->RankMetrics(
+        side, rows, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, gt, ks);
+    return EvaluationResult{k_list, alpha_list, std::move(m.recall), std::move(m.ndcg)};
+  }
+
   virtual void OnEmbeddingsSet() {}
 
   // FoldIn of the models that project with one solve (ials.h:148-185 and its

@@ -223,6 +223,117 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
   return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The argument checks of the two evaluate entry points, before any device
+// call (the C++ layer treats a failed device call as fatal); "" when fine.
+std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
+                                const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                const float* alpha_list, int32_t na, const float* recall,
+                                const float* ndcg) {
+  if (n < 0 || !gt_ptr || gt_ptr[0] != 0) return "bad arguments (n < 0, gt_ptr)";
+  if (!k_list || nk < 1 || nk > 32) return "k_list must hold 1 to 32 cut-offs";
+  for (int32_t q = 0; q < nk; ++q)
+    if (k_list[q] < 1 || k_list[q] > 1024) return "cut-offs must be in [1, 1024]";
+  if (na < 0 || (na > 0 && !alpha_list)) return "bad alpha_list";
+  if (n > 0 && (!recall || !ndcg || !gt_items)) return "null gt_items / recall / ndcg";
+  for (int64_t i = 0; i < n; ++i)
+    if (gt_ptr[i + 1] <= gt_ptr[i])
+      return "gt_ptr not monotone or no ground truth at row " + std::to_string(i);
+  for (int64_t p = 0; p < gt_ptr[n]; ++p)
+    if (gt_items[p] < 0 || gt_items[p] >= n_items)
+      return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
+  return "";
+}
+
+// Metrics of `n` query rows of `side` into recall / ndcg, then the summary
+// [(2 + 2 na) nk]: mean recall, mean ndcg, recall CVaR [na][nk], ndcg CVaR
+// [na][nk] -- EvaluationResult's own colwise().mean() and cvar().
+int evaluate_rows(frecsys::DeviceContext& dev, int side, const int64_t* rows, int64_t n,
+                  int32_t exclude_seen, const int64_t* gt_ptr, const int32_t* gt_items,
+                  const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
+                  float* recall, float* ndcg, float* summary) {
+  const int rc = dev.TryRankMetrics(side, rows, n, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
+                                    nullptr, gt_ptr, gt_items, k_list, nk, recall, ndcg);
+  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
+  if (!summary) return FRECSYS_OK;
+  frecsys::EvaluationResult er{frecsys::VectorXi(nk), frecsys::VectorXf(na),
+                               frecsys::MatrixXf(n, nk), frecsys::MatrixXf(n, nk)};
+  for (int32_t q = 0; q < nk; ++q) er.k_list[q] = k_list[q];
+  for (int32_t j = 0; j < na; ++j) er.alpha_list[j] = alpha_list[j];
+  if (n > 0) {
+    std::memcpy(er.recall.data(), recall, sizeof(float) * (size_t)(n * nk));
+    std::memcpy(er.ndcg.data(), ndcg, sizeof(float) * (size_t)(n * nk));
+  }
+  const frecsys::VectorXf mr = er.recall.colwise().mean(), mn = er.ndcg.colwise().mean();
+  std::vector<float> col((size_t)n);
+  for (int32_t q = 0; q < nk; ++q) {
+    summary[q] = mr[q];
+    summary[nk + q] = mn[q];
+    for (int64_t i = 0; i < n; ++i) col[(size_t)i] = er.recall(i, q);
+    const frecsys::VectorXf rc_q = er.cvar(col);
+    for (int64_t i = 0; i < n; ++i) col[(size_t)i] = er.ndcg(i, q);
+    const frecsys::VectorXf nc_q = er.cvar(col);
+    for (int32_t j = 0; j < na; ++j) {
+      summary[(size_t)(2 + j) * nk + q] = rc_q[j];
+      summary[(size_t)(2 + na + j) * nk + q] = nc_q[j];
+    }
+  }
+  return FRECSYS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
+                           const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list,
+                           int32_t nk, const float* alpha_list, int32_t na, int32_t exclude_seen,
+                           float* recall, float* ndcg, float* summary) {
+  if (!m || (n > 0 && !users))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate: bad arguments");
+  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const std::string e =
+      evaluate_args_error(n, dev.rows(frecsys::DeviceContext::ITEM), gt_ptr, gt_items, k_list, nk,
+                          alpha_list, na, recall, ndcg);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate: " + e);
+  return evaluate_rows(dev, FRECSYS_SIDE_USER, users, n, exclude_seen, gt_ptr, gt_items, k_list,
+                       nk, alpha_list, na, recall, ndcg, summary);
+}
+
+int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                   const int32_t* hist_items, int64_t n, const int64_t* gt_ptr,
+                                   const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   float* recall, float* ndcg, float* summary) {
+  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0)
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: bad arguments");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
+  // checked here: the C++ layer treats a bad EVAL CSR as fatal
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i])
+      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: hist_ptr not monotone");
+  if (hist_ptr[n] > 0 && !hist_items)
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: null hist_items");
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: item id " +
+                                                 std::to_string(hist_items[p]) + " out of range");
+  const std::string e = evaluate_args_error(n, n_items, gt_ptr, gt_items, k_list, nk, alpha_list,
+                                            na, recall, ndcg);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: " + e);
+  if (n == 0) return FRECSYS_OK;
+  frecsys::Csr csr;
+  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+  dm->FoldIn(csr);
+  return evaluate_rows(dm->device(), FRECSYS_SIDE_EVAL, nullptr, n, exclude_seen, gt_ptr, gt_items,
+                       k_list, nk, alpha_list, na, recall, ndcg, summary);
+}
+
 void frecsys_model_destroy(frecsys_model* m) { delete m; }
 
 const char* frecsys_model_last_error(void) { return g_model_error.c_str(); }
