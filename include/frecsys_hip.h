@@ -399,6 +399,59 @@ int frecsys_rank_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows, in
                          int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
                          const int32_t* gt_items, const int32_t* k_list, int32_t nk,
                          float* recall, float* ndcg);
+/* Scores of caller-supplied pairs (no reference counterpart): scores[i] =
+ * V[items[i]] . X[rows[i]] for the n_pairs pairs, X the table of `side` (USER
+ * or EVAL), rows / items / scores host arrays [n_pairs]; any order, repeats
+ * allowed.  A score is bit for bit the one frecsys_recommend lists for that
+ * row and item: the fp32 chain acc = fma(v[c], x[c], acc) over the padded dim
+ * in ascending c from +0 (pad columns add +0; never -0.0), whatever the pair's
+ * position, the batch, or whether frecsys_rank_candidates computed it.  One
+ * wave per 64 pairs gathers both rows in 32-column slabs through LDS; pairs
+ * are scored in batches whose workspace (16 bytes per pair: ids and score)
+ * stays within FRECSYS_RECOMMEND_WS_MB (default 256), which changes no result
+ * bit.  Rank-local at any world size: no collective.  n_pairs == 0 returns
+ * FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID, before any device
+ * call: a null context, side ITEM, a null pointer, a row id or an item id out
+ * of range.  Timer key "score_pairs" (one launch per batch);
+ * frecsys_work("score_pairs"): 2 pairs d flops, bytes = pairs Dp 4 (one padded
+ * item row per pair) + 12 pairs (ids) + 4 pairs (scores). */
+int frecsys_score_pairs(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
+                        const int32_t* items, int64_t n_pairs, float* scores);
+/* Ranking of caller-supplied candidate lists (the second stage of a
+ * retrieve-then-rank pipeline; no reference counterpart): query row i --
+ * rows[i] of `side`, or row i when rows is NULL -- ranks the DISTINCT eligible
+ * ids of its own list cand_items[cand_ptr[i] .. cand_ptr[i+1]) (list i belongs
+ * to query row i, as gt_ptr does in frecsys_rank_metrics; any length, 0 and
+ * more than n_items included; any order, repeats allowed and counted once).
+ * side, rows, flags (FRECSYS_REC_EXCLUDE_HISTORY), item_mask, the order (score
+ * descending, ties by ascending item id), the outputs items / scores
+ * [n_rows * k] (scores may be NULL) and the -1 / -FLT_MAX fill beyond the
+ * eligible distinct count mean what they mean for frecsys_recommend, and every
+ * score is that function's bit for bit (the chain of frecsys_score_pairs).
+ * 1 <= k <= 1024.  One workgroup per query row keeps the row of X in LDS,
+ * gathers the list in chunks of 256 item rows, and keeps at most 2048
+ * candidate words (score key << 32 | ~id) in LDS, sorted and cut to the best
+ * k distinct before a chunk might not fit; once k are known a candidate below
+ * the k-th key is dropped, one that ties it is kept (a list is in no id
+ * order).  Rows are ranked in batches (cut in row order, at least one row
+ * each) whose workspace -- 4 bytes per candidate id, 8 k bytes of outputs and,
+ * with the exclude flag, 4 * 4 * ceil(n_items / 128) bytes of history bits per
+ * row -- stays within FRECSYS_RECOMMEND_WS_MB (default 256); outside that
+ * budget lie 8 (n_rows + 1) bytes of cand_ptr, 8 n_rows of row ids and the
+ * mask bits.  The knob changes no result bit.  Rank-local at any world size:
+ * no collective.  n_rows == 0 returns FRECSYS_OK and touches nothing.
+ * FRECSYS_ERR_INVALID, before any device call: a null context, side ITEM, k
+ * out of range, an unknown flag, a row id out of range, a null cand_ptr /
+ * items (cand_items too unless every list is empty), cand_ptr[0] != 0 or a
+ * non-monotone cand_ptr, a candidate id < 0 or >= n_items, the exclude flag on
+ * a side with no CSR loaded.  Timer key "rank_candidates" (one launch group
+ * per row batch); frecsys_work("rank_candidates"): 2 pairs d flops with
+ * pairs = cand_ptr[n_rows], bytes = pairs Dp 4 + 4 pairs (ids) + 8 k n_rows
+ * (lists). */
+int frecsys_rank_candidates(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                            const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                            int32_t flags, const uint8_t* item_mask, int32_t* items,
+                            float* scores);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,

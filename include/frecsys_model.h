@@ -109,6 +109,33 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                     const int32_t* hist_items, int64_t n, int32_t k,
                                     int32_t exclude_seen, const uint8_t* item_mask,
                                     int32_t* items, float* scores);
+/* scores[i] = the model's score of items[i] for trained user users[i] (a row
+ * of U), n pairs, any order, repeats allowed; host arrays [n].  Bit for bit
+ * the score frecsys_model_recommend lists for that user and item
+ * (frecsys_score_pairs, frecsys_hip.h; its errors). */
+int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
+                        float* scores);
+/* The k best of each trained user's own candidate list (users[i]: a row of U;
+ * cand_items[cand_ptr[i] .. cand_ptr[i+1]): the candidates of users[i],
+ * cand_ptr[0] = 0; repeats count once) with their scores, items / scores:
+ * host [n * k] (scores may be NULL).  exclude_seen and item_mask as in
+ * frecsys_model_recommend; ranking, ties, the -1 / -FLT_MAX fill and the
+ * errors are frecsys_rank_candidates' (frecsys_hip.h). */
+int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_t n,
+                                  const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                                  int32_t exclude_seen, const uint8_t* item_mask,
+                                  int32_t* items, float* scores);
+/* The same for n unseen users given by their histories (as
+ * frecsys_model_recommend_fold_in): the model's fold-in projection into the
+ * EVAL side of its context, where the projected rows stay, then the ranking
+ * of candidate list i for history row i; exclude_seen drops the given
+ * history. */
+int frecsys_model_rank_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                          const int32_t* hist_items, int64_t n,
+                                          const int64_t* cand_ptr, const int32_t* cand_items,
+                                          int32_t k, int32_t exclude_seen,
+                                          const uint8_t* item_mask, int32_t* items,
+                                          float* scores);
 /* Ranking quality of n trained users (users[i]: a row of U) against their
  * ground truth (gt_items[gt_ptr[i] .. gt_ptr[i+1]): the held-out items of
  * users[i]; not empty): Recall@K and NDCG@K of frecsys_model_recommend's

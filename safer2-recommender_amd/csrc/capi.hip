@@ -2606,6 +2606,186 @@ int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int6
                         &mt);
 }
 
+int frecsys_score_pairs(frecsys_ctx* c, int32_t side, const int64_t* rows, const int32_t* items,
+                        int64_t n_pairs, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "score_pairs: null context");
+  const std::string w = "score_pairs: ";
+  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
+    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
+  if (n_pairs < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative pair count");
+  if (n_pairs == 0) return FRECSYS_OK;
+  if (!rows || !items || !scores) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->emb[side] || !c->emb[1])
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t ns = c->n[side], m = c->n[1], n = n_pairs;
+  for (int64_t i = 0; i < n; ++i) {
+    if (rows[i] < 0 || rows[i] >= ns)
+      return fail(c, FRECSYS_ERR_INVALID, w + "row id " + std::to_string(rows[i]) + " out of range");
+    if (items[i] < 0 || items[i] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "item id " + std::to_string(items[i]) + " out of range");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  // per pair: row id, item id, score
+  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(64, (ws_mb << 20) / 16));
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_rows = 0, o_items = up16((size_t)nb * 8), o_out = up16(o_items + (size_t)nb * 4);
+  int rc = ensure(c, &c->d_rec, &c->cap_rec, o_out + (size_t)nb * 4);
+  if (rc) return rc;
+  ScorePairsArgs a{};
+  a.X = c->emb[side];
+  a.Y = c->emb[1];
+  a.Dp = c->Dp;
+  a.rows = (const int64_t*)(c->d_rec + o_rows);
+  a.items = (const int32_t*)(c->d_rec + o_items);
+  a.out = (float*)(c->d_rec + o_out);
+  for (int64_t p0 = 0; p0 < n; p0 += nb) {  // one timed launch per pair batch
+    a.n = std::min(nb, n - p0);
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_rows, rows + p0, sizeof(int64_t) * a.n,
+                              hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_items, items + p0, sizeof(int32_t) * a.n,
+                              hipMemcpyHostToDevice, c->stream));
+    ScopedTimer t(c, "score_pairs");
+    HIP_TRY(c, launch_score_pairs(a, c->stream));
+    t.stop();
+    HIP_TRY(c, hipMemcpyAsync(scores + p0, a.out, sizeof(float) * a.n, hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // flops at the logical dim; bytes: one padded item row per pair, ids, scores
+  add_work(c, "score_pairs", 2.0 * (double)n * c->dim,
+           (double)n * c->Dp * 4.0 + (double)n * 12.0 + (double)n * 4.0, n);
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                            const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                            int32_t flags, const uint8_t* item_mask, int32_t* items,
+                            float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates: null context");
+  const std::string w = "rank_candidates: ";
+  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
+    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
+  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
+  if (flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
+    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n_rows == 0) return FRECSYS_OK;
+  if (!cand_ptr || !items) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  if (exclude && !c->rp[side])
+    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
+  if (!c->emb[side] || !c->emb[1])
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t ns = c->n[side], m = c->n[1], n = n_rows;
+  if (rows) {
+    for (int64_t i = 0; i < n; ++i)
+      if (rows[i] < 0 || rows[i] >= ns)
+        return fail(c, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(rows[i]) + " out of range");
+  } else if (n > ns) {
+    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
+  }
+  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
+  if (cand_ptr[0] != 0) return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr[0] must be 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (cand_ptr[i + 1] < cand_ptr[i])
+      return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr not monotone at row " + std::to_string(i));
+  const int64_t pairs = cand_ptr[n];
+  if (pairs > 0 && !cand_items) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_items");
+  for (int64_t p = 0; p < pairs; ++p)
+    if (cand_items[p] < 0 || cand_items[p] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  const int64_t W = recommend_words(m);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  // per row of a batch: its candidate ids, its outputs, its history bits.
+  // Batches are cut greedily in row order (at least one row each); the
+  // workspace is sized for the largest.
+  const size_t row_fixed = (size_t)k * 8 + (exclude ? (size_t)W * 4 : 0);
+  const size_t budget = (size_t)ws_mb << 20;
+  std::vector<int64_t> cuts{0};
+  int64_t max_rows = 0, max_ids = 0;
+  for (int64_t r0 = 0; r0 < n;) {
+    size_t bytes = 0;
+    int64_t r1 = r0;
+    while (r1 < n) {
+      const size_t add = row_fixed + (size_t)(cand_ptr[r1 + 1] - cand_ptr[r1]) * 4;
+      if (r1 > r0 && bytes + add > budget) break;
+      bytes += add;
+      ++r1;
+    }
+    max_rows = std::max(max_rows, r1 - r0);
+    max_ids = std::max(max_ids, cand_ptr[r1] - cand_ptr[r0]);
+    cuts.push_back(r1);
+    r0 = r1;
+  }
+  const size_t o_ids = 0;
+  const size_t o_bitmap = up16(o_ids + (size_t)max_ids * 4);
+  const size_t o_items = up16(o_bitmap + (exclude ? (size_t)max_rows * W * 4 : 0));
+  const size_t o_scores = up16(o_items + (size_t)max_rows * k * 4);
+  const size_t o_mask = up16(o_scores + (size_t)max_rows * k * 4);
+  const size_t o_ptr = up16(o_mask + (size_t)W * 4);
+  const size_t o_qrows = up16(o_ptr + ((size_t)n + 1) * 8);
+  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
+  int rc = ensure(c, &c->d_rec, &c->cap_rec, total);
+  if (rc) return rc;
+  std::vector<uint32_t> maskw((size_t)W, 0u);
+  for (int64_t j = 0; j < m; ++j)
+    if (!item_mask || item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
+                            hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr, cand_ptr, sizeof(int64_t) * ((size_t)n + 1),
+                            hipMemcpyHostToDevice, c->stream));
+  if (rows)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  RankCandArgs a{};
+  a.X = c->emb[side];
+  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
+  a.Y = c->emb[1];
+  a.m = m;
+  a.Dp = c->Dp;
+  a.k = k;
+  a.cand_ptr = (const int64_t*)(c->d_rec + o_ptr);
+  a.cand = (const int32_t*)(c->d_rec + o_ids);
+  a.row_ptr = exclude ? c->rp[side] : nullptr;
+  a.col = exclude ? c->col[side] : nullptr;
+  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
+  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
+  a.out_items = (int32_t*)(c->d_rec + o_items);
+  a.out_scores = scores ? (float*)(c->d_rec + o_scores) : nullptr;
+  for (size_t b = 0; b + 1 < cuts.size(); ++b) {  // one timed launch group per row batch
+    a.r0 = cuts[b];
+    a.n = cuts[b + 1] - cuts[b];
+    a.cand_base = cand_ptr[a.r0];
+    const int64_t ids = cand_ptr[a.r0 + a.n] - a.cand_base;
+    if (ids > 0)
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ids, cand_items + a.cand_base, sizeof(int32_t) * ids,
+                                hipMemcpyHostToDevice, c->stream));
+    ScopedTimer t(c, "rank_candidates");
+    HIP_TRY(c, launch_rank_candidates(a, c->stream));
+    t.stop();
+    HIP_TRY(c, hipMemcpyAsync(items + a.r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
+                              hipMemcpyDeviceToHost, c->stream));
+    if (scores)
+      HIP_TRY(c, hipMemcpyAsync(scores + a.r0 * k, a.out_scores, sizeof(float) * a.n * k,
+                                hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // flops at the logical dim; bytes: one padded item row per candidate, the
+  // ids read, the lists written
+  add_work(c, "rank_candidates", 2.0 * (double)pairs * c->dim,
+           (double)pairs * c->Dp * 4.0 + (double)pairs * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
 int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
                          const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
                          float* ndcg) {

@@ -360,6 +360,48 @@ int64_t recommend_words(int64_t m);
 int recommend_max_splits(int k, int64_t m);
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
 
+// Scores of caller-supplied pairs and rankings of caller-supplied candidate
+// lists (rerank.hip).  Every score is the chain acc = fmaf(y[c], x[c], acc),
+// c ascending from +0 over the padded dim: recommend.hip's score of that row
+// and item, bit for bit.
+struct ScorePairsArgs {
+  const float* X;        // query table, ld = Dp
+  const float* Y;        // items, ld = Dp
+  int Dp;
+  int64_t n;             // pairs of this batch
+  const int64_t* rows;   // [n] table row of X per pair
+  const int32_t* items;  // [n] item per pair
+  float* out;            // [n]
+};
+hipError_t launch_score_pairs(const ScorePairsArgs& a, hipStream_t s);
+// Query row i of the batch (row qrows[r0 + i] of X, or r0 + i) ranks the
+// DISTINCT eligible ids of cand[cand_ptr[r0 + i] - cand_base ..
+// cand_ptr[r0 + i + 1] - cand_base): the k best by (score descending, id
+// ascending), -1 / -FLT_MAX beyond their count.  Eligibility as in
+// RecommendArgs: maskw, and bitmap (filled here from row_ptr / col) if given.
+struct RankCandArgs {
+  const float* X;
+  const int64_t* qrows;
+  int64_t r0, n;
+  const float* Y;
+  int64_t m;
+  int Dp;
+  int k;                     // 1 .. 1024
+  const int64_t* cand_ptr;   // [rows of the call + 1]
+  const int32_t* cand;       // the batch's candidate ids, each in [0, m)
+  int64_t cand_base;         // cand_ptr[r0]: cand[0] is the first id of the batch
+  const int64_t* row_ptr;    // CSR of the query table's side (with bitmap), or nullptr
+  const int32_t* col;
+  const uint32_t* maskw;     // [recommend_words(m)]
+  uint32_t* bitmap;          // [n][recommend_words(m)] (workspace), or nullptr
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k], or nullptr
+};
+hipError_t launch_rank_candidates(const RankCandArgs& a, hipStream_t s);
+// Candidates per chunk and candidate words kept in LDS by rank_cand_kernel.
+int rank_cand_chunk();
+int rank_cand_slots();
+
 // Recall@K / NDCG@K of ranked lists in device memory (metrics.hip): query row
 // i of the batch has the list lists[i*k .. i*k+k) (-1 = empty slot, never a
 // hit) and the ground truth gt[gt_ptr[r0+i] .. gt_ptr[r0+i+1]) -- ascending,

@@ -47,7 +47,7 @@ EXPORTS = (
     "frecsys_pp_sync", "frecsys_release_workspaces", "frecsys_pp_get_predictions",
     "frecsys_set_transport", "frecsys_recommend", "frecsys_solve_side_cg",
     "frecsys_cg_iterations", "frecsys_list_metrics", "frecsys_metric_cvar",
-    "frecsys_rank_metrics",
+    "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -57,6 +57,8 @@ MODEL_EXPORTS = (
     "frecsys_model_destroy", "frecsys_model_last_error", "frecsys_model_dual_state",
     "frecsys_model_recommend", "frecsys_model_recommend_fold_in",
     "frecsys_model_evaluate", "frecsys_model_evaluate_fold_in",
+    "frecsys_model_score", "frecsys_model_rank_candidates",
+    "frecsys_model_rank_candidates_fold_in",
 )
 
 
@@ -179,6 +181,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_list_metrics": (ctypes.c_int, [P, I64, I32, P, P, P, I32, P, P]),
         "frecsys_metric_cvar": (ctypes.c_int, [P, I64, P, I32, P]),
         "frecsys_rank_metrics": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, I32, P, P]),
+        "frecsys_score_pairs": (ctypes.c_int, [P, I32, P, P, I64, P]),
+        "frecsys_rank_candidates": (ctypes.c_int, [P, I32, P, I64, P, P, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -214,6 +218,10 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
                                    [P, P, I64, P, P, P, I32, P, I32, I32, P, P, P]),
         "frecsys_model_evaluate_fold_in": (ctypes.c_int,
                                            [P, P, P, I64, P, P, P, I32, P, I32, I32, P, P, P]),
+        "frecsys_model_score": (ctypes.c_int, [P, P, P, I64, P]),
+        "frecsys_model_rank_candidates": (ctypes.c_int, [P, P, I64, P, P, I32, I32, P, P, P]),
+        "frecsys_model_rank_candidates_fold_in": (ctypes.c_int,
+                                                  [P, P, P, I64, P, P, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -580,6 +588,43 @@ class Context:
                                                   _ptr(rec), _ptr(ndcg)))
         return rec, ndcg
 
+    def score_pairs(self, side: int, rows, items) -> np.ndarray:
+        """float32 [n]: the score of item items[i] for row rows[i] of `side`
+        (SIDE_USER or SIDE_EVAL) -- frecsys_score_pairs; bit for bit the score
+        recommend lists for that row and item."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        it = np.ascontiguousarray(items, dtype=np.int32).reshape(-1)
+        assert r.shape == it.shape, (r.shape, it.shape)
+        out = np.zeros(len(r), dtype=np.float32)
+        self._check(self.lib.frecsys_score_pairs(self.h, side, _ptr(r), _ptr(it), len(r),
+                                                 _ptr(out)))
+        return out
+
+    def rank_candidates(self, side: int, k: int, cand_ptr, cand_items, rows=None,
+                        exclude_history: bool = True,
+                        item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(items int32 [n, k], scores float32 [n, k]): the k best distinct
+        eligible ids of each query row's own candidate list (CSR cand_ptr
+        int64 [n + 1] / cand_items int32; list i belongs to query row i) by
+        score descending, item id ascending -- frecsys_rank_candidates.  rows,
+        exclude_history, item_mask and the -1 / -FLT_MAX fill as in
+        recommend; the scores are recommend's bit for bit."""
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        n = len(cp) - 1
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        assert r is None or len(r) == n, (len(r), n)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        items = np.full((n, k) if k > 0 else (n, 0), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        self._check(self.lib.frecsys_rank_candidates(
+            self.h, side, _ptr(r), n, _ptr(cp), _ptr(ci), k,
+            REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk), _ptr(items), _ptr(scores)))
+        return items, scores
+
     def pp_set_rating_index(self, side: int, rix: np.ndarray):
         r = np.ascontiguousarray(rix, dtype=np.int32)
         self._check(self.lib.frecsys_pp_set_rating_index(self.h, side, _ptr(r)))
@@ -777,6 +822,61 @@ class Model:
         rc = self.lib.frecsys_model_recommend_fold_in(self.h, _ptr(hp), _ptr(hi), n, k,
                                                       int(bool(exclude_seen)), _ptr(mk),
                                                       _ptr(items), _ptr(scores))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return items, scores
+
+    def score(self, users, items) -> np.ndarray:
+        """float32 [n]: the model's score of items[i] for trained user
+        users[i] (frecsys_model_score); recommend's scores bit for bit."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        it = np.ascontiguousarray(items, dtype=np.int32).reshape(-1)
+        assert u.shape == it.shape, (u.shape, it.shape)
+        out = np.zeros(len(u), dtype=np.float32)
+        rc = self.lib.frecsys_model_score(self.h, _ptr(u), _ptr(it), len(u), _ptr(out))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return out
+
+    def rank_candidates(self, users, cand_ptr, cand_items, k: int, exclude_seen: bool = True,
+                        item_mask=None):
+        """(items int32 [n, k], scores float32 [n, k]): the k best distinct
+        ids of each trained user's own candidate list (CSR cand_ptr /
+        cand_items; list i belongs to users[i]) -- frecsys_model_rank_candidates;
+        exclude_seen, item_mask and the fill as in recommend."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        assert len(cp) == len(u) + 1, (len(cp), len(u))
+        mk = self._mask(item_mask)
+        items = np.full((len(u), max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        rc = self.lib.frecsys_model_rank_candidates(self.h, _ptr(u), len(u), _ptr(cp), _ptr(ci), k,
+                                                    int(bool(exclude_seen)), _ptr(mk),
+                                                    _ptr(items), _ptr(scores))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return items, scores
+
+    def rank_candidates_fold_in(self, hist_ptr, hist_items, cand_ptr, cand_items, k: int,
+                                exclude_seen: bool = True, item_mask=None):
+        """The same for unseen users given by their histories (CSR hist_ptr /
+        hist_items): the model's fold-in projection, then the ranking of
+        candidate list i for history row i
+        (frecsys_model_rank_candidates_fold_in).  The projected rows stay in
+        the EVAL side of the model's context."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        assert len(cp) == n + 1, (len(cp), n)
+        mk = self._mask(item_mask)
+        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        rc = self.lib.frecsys_model_rank_candidates_fold_in(
+            self.h, _ptr(hp), _ptr(hi), n, _ptr(cp), _ptr(ci), k, int(bool(exclude_seen)),
+            _ptr(mk), _ptr(items), _ptr(scores))
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return items, scores

@@ -222,6 +222,20 @@ class DeviceContext {
     return r;
   }
 
+  // Scores of (row, item) pairs and rankings of per-row candidate lists
+  // (frecsys_score_pairs / frecsys_rank_candidates).  The status code, for
+  // callers that report errors.
+  int TryScorePairs(int side, const int64_t* rows, const int32_t* items, int64_t n,
+                    float* scores) {
+    return frecsys_score_pairs(ctx_, side, rows, items, n, scores);
+  }
+  int TryRankCandidates(int side, const int64_t* rows, int64_t n, const int64_t* cand_ptr,
+                        const int32_t* cand_items, int k, int flags, const uint8_t* mask,
+                        int32_t* items, float* scores) {
+    return frecsys_rank_candidates(ctx_, side, rows, n, cand_ptr, cand_items, k, flags, mask,
+                                   items, scores);
+  }
+
   // Recall@K / NDCG@K of the ranking Recommend would return with
   // k = max(k_list), computed on the device (frecsys_rank_metrics): recall,
   // ndcg: host [n * nk]; ground-truth row i belongs to query row i.  The

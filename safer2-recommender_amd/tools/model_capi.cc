@@ -223,6 +223,67 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
   return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
 }
 
+int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
+                        float* scores) {
+  if (!m || n < 0 || (n > 0 && (!users || !items || !scores)))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_score: bad arguments");
+  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const int rc = dev.TryScorePairs(FRECSYS_SIDE_USER, users, items, n, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_t n,
+                                  const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                                  int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                                  float* scores) {
+  if (!m || n < 0 || (n > 0 && !users))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_rank_candidates: bad arguments");
+  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const int rc = dev.TryRankCandidates(FRECSYS_SIDE_USER, users, n, cand_ptr, cand_items, k,
+                                       exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
+                                       items, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_rank_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                          const int32_t* hist_items, int64_t n,
+                                          const int64_t* cand_ptr, const int32_t* cand_items,
+                                          int32_t k, int32_t exclude_seen,
+                                          const uint8_t* item_mask, int32_t* items,
+                                          float* scores) {
+  const std::string w = "frecsys_model_rank_candidates_fold_in: ";
+  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0 || !cand_ptr || cand_ptr[0] != 0)
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  // checked here: the C++ layer treats a bad EVAL CSR as fatal, and the
+  // candidate lists are checked before the projection runs
+  if (k < 1 || k > 1024 || (n > 0 && !items))
+    return model_fail(FRECSYS_ERR_INVALID, w + "k must be in [1, 1024], items non-null");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i] || cand_ptr[i + 1] < cand_ptr[i])
+      return model_fail(FRECSYS_ERR_INVALID, w + "hist_ptr / cand_ptr not monotone");
+  if ((hist_ptr[n] > 0 && !hist_items) || (cand_ptr[n] > 0 && !cand_items))
+    return model_fail(FRECSYS_ERR_INVALID, w + "null hist_items / cand_items");
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return model_fail(FRECSYS_ERR_INVALID,
+                        w + "item id " + std::to_string(hist_items[p]) + " out of range");
+  for (int64_t p = 0; p < cand_ptr[n]; ++p)
+    if (cand_items[p] < 0 || cand_items[p] >= n_items)
+      return model_fail(FRECSYS_ERR_INVALID,
+                        w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
+  if (n == 0) return FRECSYS_OK;
+  frecsys::Csr csr;
+  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+  dm->FoldIn(csr);
+  const int rc = dm->device().TryRankCandidates(
+      FRECSYS_SIDE_EVAL, nullptr, n, cand_ptr, cand_items, k,
+      exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask, items, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
 }  // extern "C"
 
 namespace {
