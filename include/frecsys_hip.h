@@ -480,8 +480,11 @@ int frecsys_snapshot_residual(frecsys_ctx* ctx, int32_t side, double* sq);
  *   "cg_iterations"   sum of the CG iteration counts of every entity solved
  *                     by frecsys_solve_side_cg;
  *   "cg_unconverged"  entities whose CG stopped at max_iterations.
- * And one value that is no sum: "recommend_splits", the item splits the last
- * frecsys_recommend call ran with.
+ * And two values that are no sums: "recommend_splits", the item splits the
+ * last frecsys_recommend call ran with; "live_device_bytes", the device
+ * memory every context of the process holds now in buffers of its own
+ * (process-wide, so what a destroyed context gave back can be read through
+ * any other: it returns to its earlier value when nothing leaked).
  * No reference counterpart (diagnostics of the MI355X path). */
 int frecsys_counter(frecsys_ctx* ctx, const char* what, int64_t* value);
 /* Block until all queued device work is done (all calls already do). */

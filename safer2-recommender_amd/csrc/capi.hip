@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/frecsys_hip.h"
+#include "device_buf.h"
 #include "kernels.h"
 #include "wide.h"
 
@@ -33,7 +34,6 @@ using namespace frecsys_hip;
 namespace {
 
 std::string g_last_error;
-unsigned long long* g_dual_prof = nullptr;  // FRECSYS_DUAL_PROF diagnostics
 
 struct Timer {
   double total_ms = 0.0;
@@ -47,47 +47,58 @@ struct Work {
   int64_t entities = 0, launches = 0;
 };
 
+// A per-entity vector the host hands over on every call: its device copy
+// and the pinned staging buffer upload() fills it through.
+struct UploadBuf {
+  DevBuf<float> dev;
+  PinnedBuf<float> stage;
+};
+
 }  // namespace
 
+// Members are destroyed last to first: the streams and events are declared
+// before every buffer, so they outlive them (frecsys_ctx_destroy
+// synchronises the streams, then deletes the context with its device
+// current).
 struct frecsys_ctx {
   int dim = 0, Dp = 0, device = 0, quirks = 1;
   int64_t n[3] = {0, 0, 0};
-  hipStream_t stream = nullptr;
-  float* emb[3] = {nullptr, nullptr, nullptr};
-  float* snap[2] = {nullptr, nullptr};
-  float* gram[2] = {nullptr, nullptr};
-  int64_t* rp[3] = {nullptr, nullptr, nullptr};
-  int32_t* col[3] = {nullptr, nullptr, nullptr};
+  Stream stream;
+  // history-space (dual) path: a second stream for the concurrent d-space
+  // solve of the long histories, and a second lane of history-space buckets
+  Stream stream2, stream3;
+  hipStream_t stream5 = nullptr;  // early basis builds: an alias of stream3
+  Event ev0, ev1;
+  Event ev_fork, ev_join, ev_fork3, ev_join3;
+  Event ev_pre5, ev_eager[2];
+  std::vector<Event> events;  // owner of every pooled event (pool_event)
+  DevBuf<float> emb[3];
+  DevBuf<float> snap[2];
+  DevBuf<float> gram[2];
+  DevBuf<int64_t> rp[3];
+  DevBuf<int32_t> col[3];
   int64_t nnz[3] = {0, 0, 0};
   std::vector<int64_t> host_rp[2];
   std::vector<int64_t> bounds[2];
   // per-entity vectors (device)
-  float* d_entity_weight = nullptr;
-  size_t cap_entity_weight = 0;
-  float* d_entity_reg = nullptr;
-  size_t cap_entity_reg = 0;
-  float* d_other_weight = nullptr;
-  size_t cap_other_weight = 0;
-  float* d_gram_w = nullptr;
-  size_t cap_gram_w = 0;
-  float* d_partials = nullptr;   // Gramian leaf workspace
-  size_t cap_partials = 0;
-  float* d_gslabs[3] = {nullptr, nullptr, nullptr};  // Gramian group slabs per side (2: train stats)
-  size_t cap_gslabs[3] = {0, 0, 0};
+  UploadBuf d_entity_weight, d_entity_reg, d_other_weight, d_gram_w;
+  DevBuf<float> d_partials;   // Gramian leaf workspace
+  DevBuf<float> d_gslabs[3];  // Gramian group slabs per side (2: train stats)
   GramPlan gplan[2];             // plan of the last Gramian formed per side
   int gram_own[2][2] = {{0, 0}, {0, 0}};  // ... and the groups this rank computed
-  float* d_loss = nullptr;
-  size_t cap_loss = 0;
-  float* d_quad = nullptr;
-  size_t cap_quad = 0;
-  unsigned long long* d_fail = nullptr;
-  unsigned int* d_counter = nullptr;
+  DevBuf<float> d_loss;
+  DevBuf<float> d_quad;
+  DevBuf<unsigned long long> d_fail;
+  DevBuf<unsigned int> d_counter;
   // cumulative event counters (frecsys_counter): [0] tagged-word polls that
   // timed out on the device (common.h tpoll); history-space reruns on host
-  unsigned int* d_events = nullptr;
+  DevBuf<unsigned int> d_events;
   int64_t hspace_reruns = 0;
+  // FRECSYS_DUAL_PROF diagnostics: cycle counters of the wide / tiled
+  // d-space solve and of the history-space buckets
+  DevBuf<unsigned long long> w_prof, d_prof, dual_prof;
   // per side: the rank's entities in decreasing-history order (LPT queue)
-  QueueRec* d_order[3] = {nullptr, nullptr, nullptr};
+  DevBuf<QueueRec> d_order[3];
   int64_t order_n[3] = {0, 0, 0};
   bool order_stale[3] = {true, true, true};
   std::vector<int64_t> host_rp_eval;
@@ -95,88 +106,59 @@ struct frecsys_ctx {
   int world = 1, rank = 0;
   std::string err;
   int64_t err_entity = -1;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::map<std::string, Timer> timers;
   std::map<std::string, Work> work;
-  std::map<float**, std::pair<float*, size_t>> pinned;  // upload() staging per destination
-  // history-space (dual) path: a second stream for the concurrent d-space
-  // solve of the long histories, the basis of each side's Gramian, the
-  // rotated copy of each side, and the solved rows in the rotated basis
-  hipStream_t stream2 = nullptr;
-  hipStream_t stream3 = nullptr;  // second lane of history-space buckets
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_fork3 = nullptr, ev_join3 = nullptr;
-  float* q[2] = {nullptr, nullptr};      // Dp x Dp
-  float* tri[2] = {nullptr, nullptr};    // [2 * Dp]: diagonal, subdiagonal
-  float* refl[2] = {nullptr, nullptr};   // Dp x Dp reflectors + [Dp] tau
-  float* xrot[2] = {nullptr, nullptr};   // n_s x Dp
-  void* qsplit[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // split images of Q, Q^T
-  void* gsplit = nullptr;  // split image of G[ITEM] for the wide user loss
-  float* out_rot[3] = {nullptr, nullptr, nullptr};
-  size_t cap_xrot[2] = {0, 0};
-  size_t cap_out_rot[3] = {0, 0, 0};
-  float* dual_table = nullptr;  // [entities][3][Dp] LDL^T factors
-  size_t cap_dual_table = 0;
+  // history-space (dual) path: the basis of each side's Gramian, the rotated
+  // copy of each side, and the solved rows in the rotated basis
+  DevBuf<float> q[2];      // Dp x Dp
+  DevBuf<float> tri[2];    // [2 * Dp]: diagonal, subdiagonal
+  DevBuf<float> refl[2];   // Dp x Dp reflectors + [Dp] tau
+  DevBuf<float> xrot[2];   // n_s x Dp
+  DevBuf<char> qsplit[2][2];  // split images of Q, Q^T
+  DevBuf<char> gsplit;  // split image of G[ITEM] for the wide user loss
+  DevBuf<float> out_rot[3];
+  DevBuf<float> dual_table;  // [entities][3][Dp] LDL^T factors
   // wide dims (Dp = 512 / 1024): tridiagonalisation work, d-space workspace
-  float* tri_work = nullptr;
-  size_t cap_tri_work = 0;
-  int32_t* d_rix[2] = {nullptr, nullptr};  // iALS++: rating index per CSR entry
-  float* d_pred[2] = {nullptr, nullptr};   // iALS++: training / EVAL prediction vectors
-  size_t cap_pred[2] = {0, 0};
-  float* d_resid = nullptr;
-  size_t cap_resid = 0;
+  DevBuf<float> tri_work;
+  DevBuf<int32_t> d_rix[2];  // iALS++: rating index per CSR entry
+  DevBuf<float> d_pred[2];   // iALS++: training / EVAL prediction vectors
+  DevBuf<float> d_resid;
   // sharded iALS++ / SAFER2++ block steps: the block columns of the side's
   // rows before the step ([n][bw]), for the prediction refresh of the rows
   // other ranks solve (frecsys_pp_step with RCCL; frecsys_pp_sync without)
-  float* d_pp_old = nullptr;
-  size_t cap_pp_old = 0;
+  DevBuf<float> d_pp_old;
   int pp_old_side = -1, pp_old_start = 0, pp_old_bw = 0;
   // external-exchange transport (frecsys_set_transport): the in-call
   // exchanges of a sharded call without a communicator
   frecsys_transport transport{};
   bool has_transport = false;
   std::vector<int32_t> pp_order_all[2];  // every row of the side by decreasing h (stable)
-  float* d_resid_e = nullptr;            // per-entity residuals [n] of a sharded pp_step
-  size_t cap_resid_e = 0;
-  float* d_rows = nullptr;       // train stats: per-row values
-  size_t cap_rows = 0;
-  float* d_gstat = nullptr;      // train stats: U^T U, V^T V
-  size_t cap_gstat = 0;
-  double* d_dot = nullptr;
-  size_t cap_dot = 0;
-  float* d_scores = nullptr;     // evaluation: [batch][items] scores
-  size_t cap_scores = 0;
-  int32_t* d_topk = nullptr;     // [eval rows][k]
-  size_t cap_topk = 0;
-  char* d_rec = nullptr;         // frecsys_recommend: candidates, counts, bitmaps, outputs
-  size_t cap_rec = 0;
-  int64_t rec_splits = 0;        // item splits of the last call (frecsys_counter "recommend_splits")
+  DevBuf<float> d_resid_e;       // per-entity residuals [n] of a sharded pp_step
+  DevBuf<float> d_rows;          // train stats: per-row values
+  DevBuf<float> d_gstat;         // train stats: U^T U, V^T V
+  DevBuf<double> d_dot;
+  DevBuf<float> d_scores;        // evaluation: [batch][items] scores
+  DevBuf<int32_t> d_topk;        // [eval rows][k]
+  DevBuf<char> d_rec;            // frecsys_recommend: candidates, counts, bitmaps, outputs
+  int64_t rec_splits = 0;       // item splits of the last call (frecsys_counter "recommend_splits")
   // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
   // per row of each side (device scratch + host copy; -1: not solved here),
   // the kernel's {sum of i, entities at the cap} and the cumulative counters
-  int32_t* d_cg_iters = nullptr;
-  size_t cap_cg_iters = 0;
-  unsigned long long* d_cg_stats = nullptr;
-  size_t cap_cg_stats = 0;
-  int32_t* d_cg_bstart = nullptr;  // batches of the queue (cg_plan_batches)
-  size_t cap_cg_bstart = 0;
+  DevBuf<int32_t> d_cg_iters;
+  DevBuf<unsigned long long> d_cg_stats;
+  DevBuf<int32_t> d_cg_bstart;  // batches of the queue (cg_plan_batches)
   std::vector<int32_t> cg_bstart;
   std::vector<int32_t> cg_iters[3];
   int64_t cg_iterations = 0, cg_unconverged = 0;
-  float* wide_ws = nullptr;      // [wide batch][wide_slot_floats(Dp)]
-  size_t cap_wide_ws = 0;
+  DevBuf<float> wide_ws;         // [wide batch][wide_slot_floats(Dp)]
   // the pre-split copy of the other side for the wide d-space SYRK
   // (wide_syrk.hip; FRECSYS_WIDE_PRESPLIT=0: the register-staged SYRK)
-  char* wide_xs = nullptr;
-  size_t cap_wide_xs = 0;
+  DevBuf<char> wide_xs;
   // the history-space wide bucket (dual.hip, 256 < h_eff <= 512): split Z
   // fragments, Cholesky slots of S, z
-  char* dw_zs = nullptr;
-  size_t cap_dw_zs = 0;
-  float* dw_slots = nullptr;
-  size_t cap_dw_slots = 0;
-  float* dw_z = nullptr;
-  size_t cap_dw_z = 0;
+  DevBuf<char> dw_zs;
+  DevBuf<float> dw_slots;
+  DevBuf<float> dw_z;
   bool wide_presplit = true;
   // FRECSYS_WIDE_WS_MB: the budget of EACH of the wide workspaces (the batch
   // workspace of A tiles, the long-history slabs, the history-space wide
@@ -196,13 +178,10 @@ struct frecsys_ctx {
   int split_rows = 4096;         // rows per partial SYRK (FRECSYS_SPLIT_ROWS, 0 = off; swept 512..4096 at ML-20M d=256: 4096 best)
   std::vector<int2> h_split;
   std::vector<SplitWork> h_work;
-  int2* d_split = nullptr;
-  size_t cap_split = 0;
-  SplitWork* d_work = nullptr;
-  size_t cap_work = 0;
-  float* d_slabs = nullptr;
-  size_t cap_slabs = 0;
-  std::vector<int32_t> order_h[3];       // history lengths in queue order
+  DevBuf<int2> d_split;
+  DevBuf<SplitWork> d_work;
+  DevBuf<float> d_slabs;
+  std::vector<int32_t> order_h[3];      // history lengths in queue order
   std::vector<QueueRec> h_order[3];      // host copy of each side's queue (source of its upload)
   int dual_on = 1;
   // Content versions (every write of a side's embeddings or Gramian takes a
@@ -226,8 +205,7 @@ struct frecsys_ctx {
   // [key0, key1)).  At N ranks a shard's short histories touch a fraction of
   // the other side, so the replicated rotation shrinks with N.  Built once
   // per (queue, split point) -- the histories do not change between epochs.
-  QueueRec* d_hrows[3] = {nullptr, nullptr, nullptr};
-  size_t cap_hrows[3] = {0, 0, 0};
+  DevBuf<QueueRec> d_hrows[3];
   int64_t n_hrows[3] = {-1, -1, -1};  // rows in the subset; -1: none (every row)
   int64_t hrows_key[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
   // Prefix sums over each side's queue of h_eff, h_eff^2, h_eff^3 and the
@@ -241,8 +219,7 @@ struct frecsys_ctx {
   };
   WorkPrefix wprefix[3][2];
   uint64_t hrows_gen[3] = {0, 0, 0};  // subset id (0: every row)
-  uint8_t* d_mark = nullptr;
-  size_t cap_mark = 0;
+  DevBuf<uint8_t> d_mark;
   bool dual_used[3] = {false, false, false};  // the side's last solve took history space
   int eager_on = 1;                 // FRECSYS_EAGER=0: no early basis builds (A/B)
   // Basis kind per side: 0 = tridiagonal (G = Q T Q^T, any mu / lambda per
@@ -254,11 +231,7 @@ struct frecsys_ctx {
   int want_mode[2] = {0, 0};
   float want_mu[2] = {0.f, 0.f}, want_lam[2] = {0.f, 0.f};
   int chol_basis_on = 1;            // FRECSYS_CHOL_BASIS=0: always tridiagonal (A/B, tests)
-  float* chol_work = nullptr;
-  size_t cap_chol_work = 0;
-  hipStream_t stream5 = nullptr;  // early basis builds: an alias of stream3
-  hipEvent_t ev_pre5 = nullptr;
-  hipEvent_t ev_eager[2] = {nullptr, nullptr};
+  DevBuf<float> chol_work;
   bool eager_pending[2] = {false, false};
   int dual_max_h = 256;  // longest h_eff on the history-space path (set per Dp at create)
   int dual_max_h_side[3] = {256, 256, 256};  // per solved side (FRECSYS_DUAL_MAX_H_USER / _ITEM)
@@ -270,7 +243,7 @@ struct frecsys_ctx {
     hipEvent_t a, b;
   };
   std::vector<Pending> pending;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<hipEvent_t> event_pool;  // idle handles of `events`
 };
 
 namespace {
@@ -313,38 +286,34 @@ void add_work(frecsys_ctx* c, const std::string& key, double flops, double bytes
 // heff_sums below.)
 double dspace_solve_flops(double d) { return d * d * d / 3.0 + 2.0 * d * d; }
 
+// DevBuf::reserve as a call's status.  A buffer that still holds memory
+// after a failure is one whose hipFree failed.
 template <typename T>
-int ensure(frecsys_ctx* c, T** p, size_t* cap, size_t count) {
-  if (*cap >= count && *p) return FRECSYS_OK;
-  if (*p) HIP_TRY(c, hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(c, hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)));
-  *cap = count;
-  return FRECSYS_OK;
+int ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count) {
+  const hipError_t e = b.reserve(count);
+  if (e == hipSuccess) return FRECSYS_OK;
+  return fail(c, FRECSYS_ERR_HIP,
+              std::string(b ? "hipFree(*p): "
+                            : "hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)): ") +
+                  hipGetErrorString(e));
 }
 
-// ensure() that reports an out-of-memory hipMalloc instead of failing: *oom
-// is set, *p left null and HIP's sticky last error cleared (the next launch
-// check would otherwise see it).
+// ensure() that reports an out-of-memory hipMalloc instead of failing
+// (DevBuf::try_reserve): *oom is set and the buffer left empty.
 template <typename T>
-int try_ensure(frecsys_ctx* c, T** p, size_t* cap, size_t count, bool* oom) {
-  *oom = false;
-  if (*cap >= count && *p) return FRECSYS_OK;
-  if (*p) HIP_TRY(c, hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1));
-  if (e == hipSuccess) {
-    *cap = count;
-    return FRECSYS_OK;
-  }
-  *p = nullptr;
-  (void)hipGetLastError();
-  if (e != hipErrorOutOfMemory)
-    return fail(c, FRECSYS_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  *oom = true;
-  return FRECSYS_OK;
+int try_ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count, bool* oom) {
+  const hipError_t e = b.try_reserve(count, oom);
+  if (e == hipSuccess) return FRECSYS_OK;
+  return fail(c, FRECSYS_ERR_HIP,
+              std::string(b ? "hipFree(*p): " : "hipMalloc: ") + hipGetErrorString(e));
+}
+
+// A fresh allocation of `count` elements whatever the buffer held (a table
+// replaced as a whole: CSR arrays, queues).
+template <typename T>
+hipError_t renew(DevBuf<T>& b, size_t count) {
+  const hipError_t e = b.release();
+  return e != hipSuccess ? e : b.reserve(count);
 }
 
 // Bytes one wide workspace may take now: FRECSYS_WIDE_WS_MB, capped at a
@@ -367,10 +336,10 @@ size_t ws_budget(frecsys_ctx* c, size_t held) {
 // the batch (counted in ws_shrinks) until one slot does not fit either.
 // Entities are independent, so the batch size never changes a result.
 template <typename T>
-int ensure_batch(frecsys_ctx* c, T** p, size_t* cap, size_t per, int64_t* batch) {
+int ensure_batch(frecsys_ctx* c, DevBuf<T>& b, size_t per, int64_t* batch) {
   while (true) {
     bool oom = false;
-    int rc = try_ensure(c, p, cap, per * (size_t)*batch, &oom);
+    int rc = try_ensure(c, b, per * (size_t)*batch, &oom);
     if (rc || !oom) return rc;
     if (*batch <= 1)
       return fail(c, FRECSYS_ERR_HIP, "hipMalloc: out of memory for one workspace slot");
@@ -438,13 +407,7 @@ int build_order(frecsys_ctx* c, int side) {
     recs[i].h = (int32_t)(rp[e + 1] - rp[e]);
     recs[i].p0 = rp[e];
   }
-  if (c->d_order[side]) {
-    hipError_t err = hipFree(c->d_order[side]);
-    (void)err;
-  }
-  c->d_order[side] = nullptr;
-  if (hipMalloc((void**)&c->d_order[side], sizeof(QueueRec) * std::max<size_t>(recs.size(), 1)) !=
-      hipSuccess)
+  if (renew(c->d_order[side], recs.size()) != hipSuccess)
     return fail(c, FRECSYS_ERR_HIP, "hipMalloc failed (order)");
   if (!recs.empty() && hipMemcpyAsync(c->d_order[side], recs.data(),
                                       sizeof(QueueRec) * recs.size(), hipMemcpyHostToDevice,
@@ -524,22 +487,22 @@ int plan_split(frecsys_ctx* c, const std::vector<int32_t>& hs, int64_t n,
     }
     if (c->h_split.empty()) return FRECSYS_OK;
     if (!shrink) {
-      int rc = ensure(c, &c->d_slabs, &c->cap_slabs, (size_t)slab * slab_floats);
+      int rc = ensure(c, c->d_slabs, (size_t)slab * slab_floats);
       if (rc) return rc;
       break;
     }
     // the wide dims (split and unsplit SYRKs are bit-identical there): fewer
     // slabs when the allocation fails
     bool oom = false;
-    int rc = try_ensure(c, &c->d_slabs, &c->cap_slabs, (size_t)slab * slab_floats, &oom);
+    int rc = try_ensure(c, c->d_slabs, (size_t)slab * slab_floats, &oom);
     if (rc) return rc;
     if (!oom) break;
     ++c->ws_shrinks;
     max_slabs = slab / 2;
   }
-  int rc = ensure(c, &c->d_split, &c->cap_split, c->h_split.size());
+  int rc = ensure(c, c->d_split, c->h_split.size());
   if (rc) return rc;
-  rc = ensure(c, &c->d_work, &c->cap_work, c->h_work.size());
+  rc = ensure(c, c->d_work, c->h_work.size());
   if (rc) return rc;
   // on the solve's own stream: a blocking hipMemcpy went through a queue that
   // could be FIFO-behind the basis chain, holding the d-space launch back
@@ -576,17 +539,10 @@ int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int 
                   float mu = 0.f, float lam = 0.f, const QueueRec* rows = nullptr,
                   int64_t nrows = 0, uint64_t sub = 0) {
   const int Dp = c->Dp;
-  size_t cap = 0;
-  if (!c->q[other]) {
-    int rc = ensure(c, &c->q[other], &cap, (size_t)Dp * Dp);
-    if (rc) return rc;
-    cap = 0;
-    rc = ensure(c, &c->tri[other], &cap, (size_t)2 * Dp);
-    if (rc) return rc;
-    cap = 0;
-    rc = ensure(c, &c->refl[other], &cap, (size_t)Dp * Dp + Dp);
-    if (rc) return rc;
-  }
+  int rc = ensure(c, c->q[other], (size_t)Dp * Dp);
+  if (!rc) rc = ensure(c, c->tri[other], (size_t)2 * Dp);
+  if (!rc) rc = ensure(c, c->refl[other], (size_t)Dp * Dp + Dp);
+  if (rc) return rc;
   if (mode == 0) mu = lam = 0.f;
   const bool same_kind = c->basis_mode[other] == mode && c->basis_mu[other] == mu &&
                          c->basis_lam[other] == lam;
@@ -600,12 +556,11 @@ int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int 
   const int64_t nrot = rows ? nrows : c->n[other];
   if (s != c->stream5) {
     // an early build of this basis (or one sharing tri_work) may still run
-    int rc = join_eager(c, 3, s);
+    rc = join_eager(c, 3, s);
     if (rc) return rc;
   }
   if (!need_rot) return FRECSYS_OK;
-  int rc = ensure(c, &c->xrot[other], &c->cap_xrot[other],
-                  (size_t)std::max<int64_t>(c->n[other], 1) * Dp);
+  rc = ensure(c, c->xrot[other], (size_t)std::max<int64_t>(c->n[other], 1) * Dp);
   if (rc) return rc;
   c->xrot_emb[other] = xkey;
   c->xrot_gram[other] = c->gram_ver[other];
@@ -625,10 +580,10 @@ int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int 
   c->basis_mu[other] = mu;
   c->basis_lam[other] = lam;
   for (int t = 0; t < 2; ++t)  // bf16-piece images of the forward and back rotations
-    if (!c->qsplit[other][t]) HIP_TRY(c, hipMalloc(&c->qsplit[other][t], basis_split_bytes(Dp)));
+    HIP_TRY(c, c->qsplit[other][t].reserve(basis_split_bytes(Dp)));
   if (mode == 1) {
     // q = L^-T: forward X L^-T (image of q), back x' L^-1 (image of q^T)
-    rc = ensure(c, &c->chol_work, &c->cap_chol_work, chol_basis_work_floats(Dp));
+    rc = ensure(c, c->chol_work, chol_basis_work_floats(Dp));
     if (rc) return rc;
     HIP_TRY(c, launch_chol_basis(c->gram[other], Dp, mu, lam, c->chol_work, c->q[other],
                                  c->tri[other], s));
@@ -641,7 +596,7 @@ int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int 
   float* tau = c->refl[other] + (size_t)Dp * Dp;
   const bool qpipe = tridiag_forms_q(Dp);
   if (wide_dim(Dp) || qpipe) {
-    rc = ensure(c, &c->tri_work, &c->cap_tri_work, tridiag_work_floats(Dp));
+    rc = ensure(c, c->tri_work, tridiag_work_floats(Dp));
     if (rc) return rc;
   }
   if (qpipe) {
@@ -677,7 +632,7 @@ int hspace_rows(frecsys_ctx* c, int side, int other, int64_t q0, int64_t q1,
     int rc = join_eager(c, 3, c->stream);
     if (rc) return rc;
     const int64_t no = c->n[other];
-    rc = ensure(c, &c->d_mark, &c->cap_mark, (size_t)no);
+    rc = ensure(c, c->d_mark, (size_t)no);
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_mark, 0, (size_t)no, c->stream));
     HIP_TRY(c, launch_mark_rows(c->d_order[side] + q0, q1 - q0, c->col[side], c->d_mark,
@@ -695,7 +650,7 @@ int hspace_rows(frecsys_ctx* c, int side, int other, int64_t q0, int64_t q1,
     if ((double)list.size() > 0.7 * (double)no) {
       c->n_hrows[side] = -1;  // most of the table: one plain pass over it
     } else {
-      rc = ensure(c, &c->d_hrows[side], &c->cap_hrows[side], std::max<size_t>(list.size(), 1));
+      rc = ensure(c, c->d_hrows[side], std::max<size_t>(list.size(), 1));
       if (rc) return rc;
       if (!list.empty())
         HIP_TRY(c, hipMemcpy(c->d_hrows[side], list.data(), sizeof(QueueRec) * list.size(),
@@ -800,20 +755,13 @@ int xchg_min_u64(frecsys_ctx* c, unsigned long long* dval) {
 // (observed waiting for work queued on other streams).  Every call that
 // uploads synchronises its stream before returning, so a staging buffer is
 // never rewritten while its copy is in flight.
-int upload(frecsys_ctx* c, float** dptr, size_t* cap, const float* host, size_t n) {
-  int rc = ensure(c, dptr, cap, n);
+int upload(frecsys_ctx* c, UploadBuf& b, const float* host, size_t n) {
+  int rc = ensure(c, b.dev, n);
   if (rc) return rc;
-  auto& pin = c->pinned[dptr];
-  if (pin.second < n) {
-    if (pin.first) HIP_TRY(c, hipHostFree(pin.first));
-    pin.first = nullptr;
-    pin.second = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&pin.first, sizeof(float) * std::max<size_t>(n, 1),
-                             hipHostMallocDefault));
-    pin.second = n;
-  }
-  if (n) std::memcpy(pin.first, host, sizeof(float) * n);
-  HIP_TRY(c, hipMemcpyAsync(*dptr, pin.first, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, b.stage.reserve(n));
+  if (n) std::memcpy(b.stage.get(), host, sizeof(float) * n);
+  HIP_TRY(c, hipMemcpyAsync(b.dev, b.stage.get(), sizeof(float) * n, hipMemcpyHostToDevice,
+                            c->stream));
   return FRECSYS_OK;
 }
 
@@ -850,9 +798,9 @@ hipEvent_t pool_event(frecsys_ctx* c) {
     c->event_pool.pop_back();
     return e;
   }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
+  c->events.emplace_back();
+  (void)hipEventCreate(&c->events.back().h);
+  return c->events.back();
 }
 size_t ktimer_begin(frecsys_ctx* c, const std::string& name, hipStream_t s) {
   frecsys_ctx::Pending p{name, pool_event(c), pool_event(c)};
@@ -906,10 +854,9 @@ int form_gramian(frecsys_ctx* c, int slot, const float* X, int64_t n, const floa
   const GramPlan pl = gram_plan(c->Dp, n);
   int g_lo = 0, g_hi = pl.ngroup;
   if (!all_groups) gram_owned_groups(pl, c->world, c->rank, &g_lo, &g_hi);
-  int rc = ensure(c, &c->d_partials, &c->cap_partials, gram_leaf_floats(pl, g_lo, g_hi));
+  int rc = ensure(c, c->d_partials, gram_leaf_floats(pl, g_lo, g_hi));
   if (rc) return rc;
-  rc = ensure(c, &c->d_gslabs[slot], &c->cap_gslabs[slot],
-              std::max<size_t>((size_t)pl.ngroup * pl.slab_floats, 1));
+  rc = ensure(c, c->d_gslabs[slot], std::max<size_t>((size_t)pl.ngroup * pl.slab_floats, 1));
   if (rc) return rc;
   if (!all_groups && c->world > 1 && !c->comm && pl.ngroup > 0)
     HIP_TRY(c, hipMemsetAsync(c->d_gslabs[slot], 0, sizeof(float) * pl.ngroup * pl.slab_floats,
@@ -1103,20 +1050,20 @@ int frecsys_ctx_create(const frecsys_config* cfg, frecsys_ctx** out) {
   {  // the history-space chain (basis -> buckets) runs on the high-priority stream
     int lo_pri = 0, hi_pri = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri);
-    if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi_pri) != hipSuccess)
+    if (hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, hi_pri) != hipSuccess)
       return bail(fail(c, FRECSYS_ERR_HIP, "hipStreamCreate failed"));
   }
-  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess)
+  if (hipEventCreate(&c->ev0.h) != hipSuccess || hipEventCreate(&c->ev1.h) != hipSuccess)
     return bail(fail(c, FRECSYS_ERR_HIP, "hipEventCreate failed"));
   // the second bucket lane / early builds at normal priority (high priority
   // measured no better)
   const int s3_pri = 0;
-  if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, s3_pri) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_fork3, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join3, hipEventDisableTiming) != hipSuccess)
+  if (hipStreamCreateWithFlags(&c->stream2.h, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->stream3.h, hipStreamNonBlocking, s3_pri) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_join.h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_fork3.h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_join3.h, hipEventDisableTiming) != hipSuccess)
     return bail(fail(c, FRECSYS_ERR_HIP, "hipStreamCreate failed (stream2/3)"));
   // the early basis builds share stream3 with the second bucket lane: with
   // GPU_MAX_HW_QUEUES = 4 a fifth stream shared a hardware queue with the
@@ -1124,10 +1071,10 @@ int frecsys_ctx_create(const frecsys_config* cfg, frecsys_ctx** out) {
   // basis chain queued before it -- 0.5 ms per ML-20M epoch.  stream3 is idle
   // when a Gramian triggers an early build, and the buckets it runs later
   // need that basis anyway.
-  c->stream5 = c->stream3;
-  if (hipEventCreateWithFlags(&c->ev_pre5, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_eager[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_eager[1], hipEventDisableTiming) != hipSuccess)
+  c->stream5 = c->stream3.h;
+  if (hipEventCreateWithFlags(&c->ev_pre5.h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_eager[0].h, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_eager[1].h, hipEventDisableTiming) != hipSuccess)
     return bail(fail(c, FRECSYS_ERR_HIP, "hipEventCreate failed (early builds)"));
   if (const char* v = getenv("FRECSYS_DUAL")) c->dual_on = atoi(v);
   if (const char* v = getenv("FRECSYS_EAGER")) c->eager_on = atoi(v);
@@ -1172,15 +1119,14 @@ int frecsys_ctx_create(const frecsys_config* cfg, frecsys_ctx** out) {
     c->dual_max_h_side[1] = std::min(atoi(v), max_h_cap);
   for (int s = 0; s < 2; ++s) {
     const size_t rows = (size_t)std::max<int64_t>(c->n[s], 1);
-    if (hipMalloc((void**)&c->emb[s], sizeof(float) * rows * Dp) != hipSuccess ||
-        hipMalloc((void**)&c->gram[s], sizeof(float) * Dp * Dp) != hipSuccess)
+    if (c->emb[s].reserve(rows * Dp) != hipSuccess ||
+        c->gram[s].reserve((size_t)Dp * Dp) != hipSuccess)
       return bail(fail(c, FRECSYS_ERR_HIP, "hipMalloc failed (embeddings)"));
     (void)hipMemsetAsync(c->emb[s], 0, sizeof(float) * rows * Dp, c->stream);
     (void)hipMemsetAsync(c->gram[s], 0, sizeof(float) * Dp * Dp, c->stream);
   }
-  if (hipMalloc((void**)&c->d_fail, sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void**)&c->d_counter, sizeof(unsigned int)) != hipSuccess ||
-      hipMalloc((void**)&c->d_events, 4 * sizeof(unsigned int)) != hipSuccess)
+  if (c->d_fail.reserve(1) != hipSuccess || c->d_counter.reserve(1) != hipSuccess ||
+      c->d_events.reserve(4) != hipSuccess)
     return bail(fail(c, FRECSYS_ERR_HIP, "hipMalloc failed"));
   (void)hipMemsetAsync(c->d_events, 0, 4 * sizeof(unsigned int), c->stream);
   c->bounds[0] = {0, c->n[0]};
@@ -1194,87 +1140,11 @@ int frecsys_ctx_create(const frecsys_config* cfg, frecsys_ctx** out) {
 void frecsys_ctx_destroy(frecsys_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream5) (void)hipStreamSynchronize(c->stream5);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  // every stream idle before the members go: the buffers first, then the
+  // events and streams (stream5 is stream3)
+  for (hipStream_t s : {c->stream5, c->stream.h, c->stream2.h})
+    if (s) (void)hipStreamSynchronize(s);
   if (c->comm) ncclCommDestroy(c->comm);
-  for (int s = 0; s < 3; ++s) {
-    if (c->emb[s]) (void)hipFree(c->emb[s]);
-    if (c->rp[s]) (void)hipFree(c->rp[s]);
-    if (c->col[s]) (void)hipFree(c->col[s]);
-  }
-  for (int s = 0; s < 2; ++s) {
-    if (c->snap[s]) (void)hipFree(c->snap[s]);
-    if (c->gram[s]) (void)hipFree(c->gram[s]);
-  }
-  for (float* p : {c->d_entity_weight, c->d_entity_reg, c->d_other_weight, c->d_gram_w,
-                   c->d_partials, c->d_loss, c->d_quad, c->d_gslabs[0], c->d_gslabs[1],
-                   c->d_gslabs[2]})
-    if (p) (void)hipFree(p);
-  if (c->d_fail) (void)hipFree(c->d_fail);
-  if (c->d_counter) (void)hipFree(c->d_counter);
-  if (c->d_events) (void)hipFree(c->d_events);
-  for (int s = 0; s < 3; ++s)
-    if (c->d_order[s]) (void)hipFree(c->d_order[s]);
-  for (int s = 0; s < 2; ++s) {
-    for (float* p : {c->q[s], c->tri[s], c->refl[s], c->xrot[s]})
-      if (p) (void)hipFree(p);
-    for (void* p : c->qsplit[s])
-      if (p) (void)hipFree(p);
-  }
-  if (c->gsplit) (void)hipFree(c->gsplit);
-  for (int s = 0; s < 3; ++s)
-    if (c->out_rot[s]) (void)hipFree(c->out_rot[s]);
-  for (int s = 0; s < 3; ++s)
-    if (c->d_hrows[s]) (void)hipFree(c->d_hrows[s]);
-  if (c->d_mark) (void)hipFree(c->d_mark);
-  if (c->dual_table) (void)hipFree(c->dual_table);
-  if (c->tri_work) (void)hipFree(c->tri_work);
-  if (c->chol_work) (void)hipFree(c->chol_work);
-  if (c->wide_ws) (void)hipFree(c->wide_ws);
-  if (c->wide_xs) (void)hipFree(c->wide_xs);
-  if (c->dw_zs) (void)hipFree(c->dw_zs);
-  if (c->dw_slots) (void)hipFree(c->dw_slots);
-  if (c->dw_z) (void)hipFree(c->dw_z);
-  if (c->d_scores) (void)hipFree(c->d_scores);
-  if (c->d_rows) (void)hipFree(c->d_rows);
-  for (int s = 0; s < 2; ++s) {
-    if (c->d_rix[s]) (void)hipFree(c->d_rix[s]);
-    if (c->d_pred[s]) (void)hipFree(c->d_pred[s]);
-  }
-  if (c->d_resid) (void)hipFree(c->d_resid);
-  if (c->d_resid_e) (void)hipFree(c->d_resid_e);
-  if (c->d_gstat) (void)hipFree(c->d_gstat);
-  if (c->d_dot) (void)hipFree(c->d_dot);
-  if (c->d_topk) (void)hipFree(c->d_topk);
-  if (c->d_rec) (void)hipFree(c->d_rec);
-  if (c->d_cg_iters) (void)hipFree(c->d_cg_iters);
-  if (c->d_cg_stats) (void)hipFree(c->d_cg_stats);
-  if (c->d_cg_bstart) (void)hipFree(c->d_cg_bstart);
-  if (c->d_split) (void)hipFree(c->d_split);
-  if (c->d_work) (void)hipFree(c->d_work);
-  if (c->d_slabs) (void)hipFree(c->d_slabs);
-  for (auto& kv : c->pinned)
-    if (kv.second.first) (void)hipHostFree(kv.second.first);
-  for (auto& p : c->pending) c->event_pool.insert(c->event_pool.end(), {p.a, p.b});
-  for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-  if (c->ev_fork3) (void)hipEventDestroy(c->ev_fork3);
-  if (c->ev_join3) (void)hipEventDestroy(c->ev_join3);
-  if (c->stream3) {
-    (void)hipStreamSynchronize(c->stream3);
-    (void)hipStreamDestroy(c->stream3);
-  }
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->stream2) {
-    (void)hipStreamSynchronize(c->stream2);
-    (void)hipStreamDestroy(c->stream2);
-  }
-  for (hipEvent_t e : {c->ev_pre5, c->ev_eager[0], c->ev_eager[1]})
-    if (e) (void)hipEventDestroy(e);
-  c->stream5 = nullptr;  // = stream3, destroyed above
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -1347,12 +1217,8 @@ int frecsys_load_csr(frecsys_ctx* c, int32_t side, int64_t n_rows, const int64_t
   }
   c->gram_src[0] = c->gram_src[1] = 0;
   if (side == 2) emb_written(c, 2);
-  if (c->rp[side]) HIP_TRY(c, hipFree(c->rp[side]));
-  if (c->col[side]) HIP_TRY(c, hipFree(c->col[side]));
-  c->rp[side] = nullptr;
-  c->col[side] = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&c->rp[side], sizeof(int64_t) * (n_rows + 1)));
-  HIP_TRY(c, hipMalloc((void**)&c->col[side], sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
+  HIP_TRY(c, renew(c->rp[side], (size_t)n_rows + 1));
+  HIP_TRY(c, renew(c->col[side], (size_t)nnz));
   HIP_TRY(c, hipMemcpyAsync(c->rp[side], row_ptr, sizeof(int64_t) * (n_rows + 1),
                             hipMemcpyHostToDevice, c->stream));
   if (nnz)
@@ -1363,10 +1229,7 @@ int frecsys_load_csr(frecsys_ctx* c, int32_t side, int64_t n_rows, const int64_t
   if (side == 2) {
     c->host_rp_eval.assign(row_ptr, row_ptr + n_rows + 1);
     c->n[2] = n_rows;
-    if (c->emb[2]) HIP_TRY(c, hipFree(c->emb[2]));
-    c->emb[2] = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&c->emb[2],
-                         sizeof(float) * std::max<int64_t>(n_rows, 1) * c->Dp));
+    HIP_TRY(c, renew(c->emb[2], (size_t)std::max<int64_t>(n_rows, 1) * c->Dp));
     HIP_TRY(c, hipMemsetAsync(c->emb[2], 0, sizeof(float) * std::max<int64_t>(n_rows, 1) * c->Dp,
                               c->stream));
   } else {
@@ -1429,7 +1292,7 @@ int frecsys_snapshot(frecsys_ctx* c, int32_t side) {
   if (!c || side < 0 || side > 1) return fail(c, FRECSYS_ERR_INVALID, "snapshot: bad side");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = sizeof(float) * std::max<int64_t>(c->n[side], 1) * c->Dp;
-  if (!c->snap[side]) HIP_TRY(c, hipMalloc((void**)&c->snap[side], bytes));
+  HIP_TRY(c, c->snap[side].reserve(bytes / sizeof(float)));
   HIP_TRY(c, hipMemcpyAsync(c->snap[side], c->emb[side], bytes, hipMemcpyDeviceToDevice,
                             c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1460,9 +1323,9 @@ int frecsys_gramian(frecsys_ctx* c, int32_t side, const float* weights, int32_t 
   if (rc) return rc;
   const float* dw = nullptr;
   if (weights) {
-    rc = upload(c, &c->d_gram_w, &c->cap_gram_w, weights, (size_t)c->n[side]);
+    rc = upload(c, c->d_gram_w, weights, (size_t)c->n[side]);
     if (rc) return rc;
-    dw = c->d_gram_w;
+    dw = c->d_gram_w.dev;
   }
   {
     ScopedTimer t(c, "gramian");
@@ -1528,8 +1391,7 @@ int frecsys_set_gram_groups(frecsys_ctx* c, int32_t side, const float* host) {
   int rc = join_eager(c, 1 << side, c->stream);
   if (rc) return rc;
   const GramPlan pl = gram_plan(c->Dp, c->n[side]);
-  rc = ensure(c, &c->d_gslabs[side], &c->cap_gslabs[side],
-              std::max<size_t>((size_t)pl.ngroup * pl.slab_floats, 1));
+  rc = ensure(c, c->d_gslabs[side], std::max<size_t>((size_t)pl.ngroup * pl.slab_floats, 1));
   if (rc) return rc;
   if (pl.ngroup)
     HIP_TRY(c, hipMemcpyAsync(c->d_gslabs[side], host, sizeof(float) * pl.ngroup * pl.slab_floats,
@@ -1585,29 +1447,29 @@ int launch_dspace(frecsys_ctx* c, SolveArgs ap, const std::vector<int32_t>& hs,
   if (wide_dim(c->Dp)) {
     const size_t slot = wide_slot_floats(c->Dp);
     const int64_t budget =
-        (int64_t)(ws_budget(c, c->cap_wide_ws * sizeof(float)) / (slot * sizeof(float)));
+        (int64_t)(ws_budget(c, c->wide_ws.cap() * sizeof(float)) / (slot * sizeof(float)));
     int64_t batch = std::max<int64_t>(1, std::min<int64_t>(ap.n_rows, budget));
-    int rc = ensure_batch(c, &c->wide_ws, &c->cap_wide_ws, slot, &batch);
+    int rc = ensure_batch(c, c->wide_ws, slot, &batch);
     if (rc) return rc;
     if (can_split) {  // long histories of the first batch cut into slabs (a budget of their own)
       const size_t sf = wide_slab_floats(c->Dp);
       rc = plan_split(c, hs, batch, heff, &ap, wide_slab_rows(), sf,
-                      (int64_t)(ws_budget(c, c->cap_slabs * sizeof(float)) / (sf * sizeof(float))),
+                      (int64_t)(ws_budget(c, c->d_slabs.cap() * sizeof(float)) / (sf * sizeof(float))),
                       s, true);
       if (rc) return rc;
     }
     static const bool wprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-    static unsigned long long* w_prof = nullptr;
+    DevBuf<unsigned long long>& w_prof = c->w_prof;
     if (wprof && !w_prof) {
-      HIP_TRY(c, hipMalloc((void**)&w_prof, sizeof(unsigned long long) * 16));
+      HIP_TRY(c, w_prof.reserve(16));
       HIP_TRY(c, hipMemset(w_prof, 0, sizeof(unsigned long long) * 16));
     }
-    ap.prof = wprof ? w_prof : nullptr;
+    ap.prof = wprof ? w_prof.get() : nullptr;
     char* xs = nullptr;
     if (c->wide_presplit && ap.n_rows > 0) {
       // no room for the table: the register-staged SYRK (bit-identical)
       bool oom = false;
-      rc = try_ensure(c, &c->wide_xs, &c->cap_wide_xs, wide_xsplit_bytes(c->Dp, ap.n_other), &oom);
+      rc = try_ensure(c, c->wide_xs, wide_xsplit_bytes(c->Dp, ap.n_other), &oom);
       if (rc) return rc;
       if (oom) ++c->ws_shrinks;
       xs = c->wide_xs;
@@ -1657,12 +1519,12 @@ int launch_dspace(frecsys_ctx* c, SolveArgs ap, const std::vector<int32_t>& hs,
     ktimer_end(c, k, s);
   }
   static const bool dprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-  static unsigned long long* d_prof = nullptr;
+  DevBuf<unsigned long long>& d_prof = c->d_prof;
   if (dprof && !d_prof) {
-    HIP_TRY(c, hipMalloc((void**)&d_prof, sizeof(unsigned long long) * 16));
+    HIP_TRY(c, d_prof.reserve(16));
     HIP_TRY(c, hipMemset(d_prof, 0, sizeof(unsigned long long) * 16));
   }
-  ap.prof = dprof ? d_prof : nullptr;
+  ap.prof = dprof ? d_prof.get() : nullptr;
   const size_t k = ktimer_begin(c, pre + ".dspace", s);
   if (side_split) {
     SolveArgs af = ap;  // queue positions [0, n_split): the split entities
@@ -1710,37 +1572,79 @@ int launch_dspace(frecsys_ctx* c, SolveArgs ap, const std::vector<int32_t>& hs,
   return FRECSYS_OK;
 }
 
-int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
-                    bool force_dspace) {
-  if (!c || !valid_side(side) || !p) return fail(c, FRECSYS_ERR_INVALID, "solve: bad arguments");
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "solve: no CSR loaded for side");
+// The argument checks frecsys_solve_side and frecsys_solve_side_cg share
+// (pre: the call's message prefix; frecsys_pp_step has texts of its own).
+int check_solve_args(frecsys_ctx* c, const std::string& pre, int side,
+                     const frecsys_solve_params* p) {
+  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, pre + "no CSR loaded for side");
   const int kind = p->kind;
   if (kind < FRECSYS_KIND_IALS || kind > FRECSYS_KIND_CVAR_GRAD_V)
-    return fail(c, FRECSYS_ERR_INVALID, "solve: bad kind");
+    return fail(c, FRECSYS_ERR_INVALID, pre + "bad kind");
   const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U || kind == FRECSYS_KIND_CVAR_GRAD_U;
   const bool grad = kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V;
   if (vkind && (!p->entity_reg || !p->other_weight))
-    return fail(c, FRECSYS_ERR_INVALID, "solve: V kinds need entity_reg and other_weight");
-  if (grad && side == 2) return fail(c, FRECSYS_ERR_INVALID, "solve: CVaR step on EVAL side");
-  const int other = side == 1 ? 0 : 1;
-  if (p->from_snapshot && !c->snap[other])
-    return fail(c, FRECSYS_ERR_INVALID, "solve: from_snapshot without a snapshot");
+    return fail(c, FRECSYS_ERR_INVALID, pre + "V kinds need entity_reg and other_weight");
+  if (grad && side == 2) return fail(c, FRECSYS_ERR_INVALID, pre + "CVaR step on EVAL side");
+  if (p->from_snapshot && !c->snap[side == 1 ? 0 : 1])
+    return fail(c, FRECSYS_ERR_INVALID, pre + "from_snapshot without a snapshot");
+  return FRECSYS_OK;
+}
+
+// What every solve entry point does before its launches: the device, the
+// early basis builds of `eager_mask` joined, the per-entity vectors the kind
+// reads uploaded, the failure word reset.
+int begin_solve(frecsys_ctx* c, int side, const frecsys_solve_params* p, int eager_mask) {
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = join_eager(c, side < 2 ? 1 << side : 0, c->stream);  // a build still reading emb[side]
+  int rc = join_eager(c, eager_mask, c->stream);
   if (rc) return rc;
+  const int kind = p->kind, other = side == 1 ? 0 : 1;
+  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
+  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U || kind == FRECSYS_KIND_CVAR_GRAD_U;
   if (ukind && p->entity_weight) {
-    rc = upload(c, &c->d_entity_weight, &c->cap_entity_weight, p->entity_weight,
-                (size_t)c->n[side]);
+    rc = upload(c, c->d_entity_weight, p->entity_weight, (size_t)c->n[side]);
     if (rc) return rc;
   }
   if (vkind) {
-    rc = upload(c, &c->d_entity_reg, &c->cap_entity_reg, p->entity_reg, (size_t)c->n[side]);
+    rc = upload(c, c->d_entity_reg, p->entity_reg, (size_t)c->n[side]);
     if (rc) return rc;
-    rc = upload(c, &c->d_other_weight, &c->cap_other_weight, p->other_weight,
-                (size_t)c->n[other]);
+    rc = upload(c, c->d_other_weight, p->other_weight, (size_t)c->n[other]);
     if (rc) return rc;
   }
+  // ~0ull by a device-side fill: an H2D copy from host memory at this point
+  // was observed starting only after the early basis build queued on another
+  // stream had finished, holding back the fork of the d-space solve
+  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
+  return FRECSYS_OK;
+}
+
+// ... and after them: the failure word read back into *f (~0ull: none), the
+// solved rows all-gathered (gather: the call has not exchanged them itself),
+// the stream synchronised and the kernel timers resolved.
+int end_solve(frecsys_ctx* c, int side, bool gather, unsigned long long* f) {
+  HIP_TRY(c, hipMemcpyAsync(f, c->d_fail, sizeof(*f), hipMemcpyDeviceToHost, c->stream));
+  if (gather && side < 2 && (c->world > 1 || c->comm)) {
+    ScopedTimer t(c, "allgather");
+    int rc = allgather_rows(c, c->emb[side], side, c->Dp);
+    if (rc) return rc;
+    t.stop();
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  flush_ktimers(c);
+  return FRECSYS_OK;
+}
+
+int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
+                    bool force_dspace) {
+  if (!c || !valid_side(side) || !p) return fail(c, FRECSYS_ERR_INVALID, "solve: bad arguments");
+  int rc = check_solve_args(c, "solve: ", side, p);
+  if (rc) return rc;
+  const int kind = p->kind;
+  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
+  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U || kind == FRECSYS_KIND_CVAR_GRAD_U;
+  const bool grad = kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V;
+  const int other = side == 1 ? 0 : 1;
+  rc = begin_solve(c, side, p, side < 2 ? 1 << side : 0);  // a build still reading emb[side]
+  if (rc) return rc;
   int64_t lo, hi;
   shard(c, side, &lo, &hi);
   rc = build_order(c, side);
@@ -1765,9 +1669,9 @@ int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
   a.alpha = p->alpha;
   a.eta = p->stepsize;
   a.lambda_is_reg = p->lambda_is_reg;
-  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight : nullptr;
-  a.entity_reg = vkind ? c->d_entity_reg : nullptr;
-  a.other_weight = vkind ? c->d_other_weight : nullptr;
+  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
+  a.entity_reg = vkind ? c->d_entity_reg.dev.get() : nullptr;
+  a.other_weight = vkind ? c->d_other_weight.dev.get() : nullptr;
   a.fail = c->d_fail;
   a.split = nullptr;
   a.n_split = 0;
@@ -1776,10 +1680,6 @@ int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
   a.n_work = 0;
   a.debug_skip = c->debug_skip;
   const unsigned long long none = ~0ull;
-  // ~0ull by a device-side fill: an H2D copy from host memory at this point
-  // was observed starting only after the early basis build queued on another
-  // stream had finished, holding back the fork of the d-space solve
-  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(none), c->stream));
   // Queue split: the queue is sorted by decreasing history, and h_eff (the
   // rows the assembly reads, tail-quirk rows included) is monotone in h, so
   // the d-space entities are a prefix, then the history-space buckets
@@ -1882,16 +1782,16 @@ int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
       d.fail = a.fail;
       d.debug_skip = a.debug_skip;
       static const bool dprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-      unsigned long long*& d_prof = g_dual_prof;
+      DevBuf<unsigned long long>& d_prof = c->dual_prof;
       if (dprof && !d_prof) {
-        HIP_TRY(c, hipMalloc((void**)&d_prof, sizeof(unsigned long long) * 16 * 9));
+        HIP_TRY(c, d_prof.reserve(16 * 9));
         HIP_TRY(c, hipMemset(d_prof, 0, sizeof(unsigned long long) * 16 * 9));
       }
       const int64_t n_hs = n_nonempty - n_dspace;
       const size_t n_blk = (size_t)((n_hs + 63) / 64) * 64;  // position-blocked buffers
-      rc = ensure(c, &c->dual_table, &c->cap_dual_table, n_blk * 3 * c->Dp);
+      rc = ensure(c, c->dual_table, n_blk * 3 * c->Dp);
       if (rc) return rc;
-      rc = ensure(c, &c->out_rot[side], &c->cap_out_rot[side], n_blk * c->Dp);
+      rc = ensure(c, c->out_rot[side], n_blk * c->Dp);
       if (rc) return rc;
       d.out_rot = c->out_rot[side];
       k = ktimer_begin(c, pre + ".hspace", c->stream);
@@ -1912,15 +1812,15 @@ int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
         // the wide bucket, 256 < h_eff <= 512, in batches of its workspace
         const int64_t hi = std::min(n_nonempty, first_le(32 * kDualMaxTiles));
         const size_t per = dual_wide_zs_bytes(c->Dp) + sizeof(float) * (dual_wide_slot_floats() + 512);
-        const size_t held = c->cap_dw_zs + sizeof(float) * (c->cap_dw_slots + c->cap_dw_z);
+        const size_t held = c->dw_zs.cap() + sizeof(float) * (c->dw_slots.cap() + c->dw_z.cap());
         int64_t nbat = std::max<int64_t>(
             1, std::min<int64_t>(hi - lo, (int64_t)(ws_budget(c, held) / per)));
         if (hi > lo) {
-          rc = ensure_batch(c, &c->dw_zs, &c->cap_dw_zs, dual_wide_zs_bytes(c->Dp), &nbat);
+          rc = ensure_batch(c, c->dw_zs, dual_wide_zs_bytes(c->Dp), &nbat);
           if (rc) return rc;
-          rc = ensure_batch(c, &c->dw_slots, &c->cap_dw_slots, dual_wide_slot_floats(), &nbat);
+          rc = ensure_batch(c, c->dw_slots, dual_wide_slot_floats(), &nbat);
           if (rc) return rc;
-          rc = ensure_batch(c, &c->dw_z, &c->cap_dw_z, (size_t)512, &nbat);
+          rc = ensure_batch(c, c->dw_z, (size_t)512, &nbat);
           if (rc) return rc;
         }
         for (int64_t b0 = lo; b0 < hi; b0 += nbat) {
@@ -1978,20 +1878,13 @@ int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
     NCCL_TRY(c, ncclAllReduce(c->d_fail, c->d_fail, 1, ncclUint64, ncclMin, c->comm, c->stream));
   }
   unsigned long long f = none;
-  HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
-  if (side < 2 && (c->world > 1 || c->comm)) {
-    ScopedTimer t(c, "allgather");
-    rc = allgather_rows(c, c->emb[side], side, c->Dp);
-    if (rc) return rc;
-    t.stop();
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  flush_ktimers(c);
-  if (getenv("FRECSYS_DUAL_PROF") && dual && g_dual_prof) {
+  rc = end_solve(c, side, true, &f);
+  if (rc) return rc;
+  if (getenv("FRECSYS_DUAL_PROF") && dual && c->dual_prof) {
     // diagnostics: mean cycles per entity and phase of the workgroup kernel
     unsigned long long hp[16 * 9];
-    HIP_TRY(c, hipMemcpy(hp, g_dual_prof, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemset(g_dual_prof, 0, sizeof(hp)));
+    HIP_TRY(c, hipMemcpy(hp, c->dual_prof, sizeof(hp), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemset(c->dual_prof, 0, sizeof(hp)));
     for (int t = 1; t <= 8; ++t) {
       const unsigned long long n = hp[16 * t + 4];
       if (!n) continue;
@@ -2041,8 +1934,6 @@ int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_para
     return fail(c, FRECSYS_ERR_INVALID,
                 "solve_cg: max_iterations and tolerance must be >= 0 (and not NaN)");
   const int kind = p->kind;
-  if (kind < FRECSYS_KIND_IALS || kind > FRECSYS_KIND_CVAR_GRAD_V)
-    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: bad kind");
   if (kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V)
     return fail(c, FRECSYS_ERR_INVALID,
                 "solve_cg: the CVaR gradient kinds have no conjugate-gradient form");
@@ -2050,39 +1941,23 @@ int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_para
     return fail(c, FRECSYS_ERR_UNSUPPORTED,
                 "solve_cg: the conjugate-gradient path is built for dim <= 256 (dim " +
                     std::to_string(c->dim) + ")");
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "solve_cg: no CSR loaded for side");
+  int rc = check_solve_args(c, "solve_cg: ", side, p);
+  if (rc) return rc;
   const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V;
   const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U;
-  if (vkind && (!p->entity_reg || !p->other_weight))
-    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: V kinds need entity_reg and other_weight");
   const int other = side == 1 ? 0 : 1;
-  if (p->from_snapshot && !c->snap[other])
-    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: from_snapshot without a snapshot");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc = join_eager(c, side < 2 ? 1 << side : 0, c->stream);  // a build still reading emb[side]
+  rc = begin_solve(c, side, p, side < 2 ? 1 << side : 0);  // a build still reading emb[side]
   if (rc) return rc;
-  if (ukind && p->entity_weight) {
-    rc = upload(c, &c->d_entity_weight, &c->cap_entity_weight, p->entity_weight,
-                (size_t)c->n[side]);
-    if (rc) return rc;
-  }
-  if (vkind) {
-    rc = upload(c, &c->d_entity_reg, &c->cap_entity_reg, p->entity_reg, (size_t)c->n[side]);
-    if (rc) return rc;
-    rc = upload(c, &c->d_other_weight, &c->cap_other_weight, p->other_weight, (size_t)c->n[other]);
-    if (rc) return rc;
-  }
   rc = build_order(c, side);
   if (rc) return rc;
   const int64_t n = c->n[side];
-  rc = ensure(c, &c->d_cg_iters, &c->cap_cg_iters, (size_t)std::max<int64_t>(n, 1));
+  rc = ensure(c, c->d_cg_iters, (size_t)std::max<int64_t>(n, 1));
   if (rc) return rc;
-  rc = ensure(c, &c->d_cg_stats, &c->cap_cg_stats, (size_t)2);
+  rc = ensure(c, c->d_cg_stats, (size_t)2);
   if (rc) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_cg_iters, 0xFF, sizeof(int32_t) * std::max<int64_t>(n, 1),
                             c->stream));
   HIP_TRY(c, hipMemsetAsync(c->d_cg_stats, 0, sizeof(unsigned long long) * 2, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
   CgArgs a{};
   a.kind = kind;
   a.quirk = c->quirks;
@@ -2090,7 +1965,7 @@ int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_para
   a.dim = c->dim;
   a.order = c->d_order[side];
   cg_plan_batches(c->h_order[side].data(), c->order_n[side], &c->cg_bstart);
-  rc = ensure(c, &c->d_cg_bstart, &c->cap_cg_bstart, c->cg_bstart.size());
+  rc = ensure(c, c->d_cg_bstart, c->cg_bstart.size());
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_cg_bstart, c->cg_bstart.data(),
                             sizeof(int32_t) * c->cg_bstart.size(), hipMemcpyHostToDevice,
@@ -2107,9 +1982,9 @@ int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_para
   a.w = p->unobserved_weight;
   a.alpha = p->alpha;
   a.lambda_is_reg = p->lambda_is_reg;
-  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight : nullptr;
-  a.entity_reg = vkind ? c->d_entity_reg : nullptr;
-  a.other_weight = vkind ? c->d_other_weight : nullptr;
+  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
+  a.entity_reg = vkind ? c->d_entity_reg.dev.get() : nullptr;
+  a.other_weight = vkind ? c->d_other_weight.dev.get() : nullptr;
   a.max_iter = cg->max_iterations;
   a.tol = cg->tolerance;
   a.iters = c->d_cg_iters;
@@ -2129,19 +2004,12 @@ int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_para
   unsigned long long f = ~0ull, st[2] = {0, 0};
   std::vector<int32_t>& it = c->cg_iters[side];
   it.assign((size_t)n, -1);
-  HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(st, c->d_cg_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
   if (n)
     HIP_TRY(c, hipMemcpyAsync(it.data(), c->d_cg_iters, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
                               c->stream));
-  if (side < 2 && (c->world > 1 || c->comm)) {
-    ScopedTimer t(c, "allgather");
-    rc = allgather_rows(c, c->emb[side], side, c->Dp);
-    if (rc) return rc;
-    t.stop();
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  flush_ktimers(c);
+  rc = end_solve(c, side, true, &f);
+  if (rc) return rc;
   c->cg_iterations += (int64_t)st[0];
   c->cg_unconverged += (int64_t)st[1];
   {  // per entity and iteration: G p (2 d^2) + two passes of the history rows (4 h d)
@@ -2179,8 +2047,8 @@ int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, fl
   if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "loss: no CSR loaded");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t rows = (size_t)c->n[side];
-  const bool fresh = c->cap_loss < rows || !c->d_loss;
-  int rc = ensure(c, &c->d_loss, &c->cap_loss, rows);
+  const bool fresh = c->d_loss.cap() < rows || !c->d_loss;
+  int rc = ensure(c, c->d_loss, rows);
   if (rc) return rc;
   if (fresh || side == 2)
     HIP_TRY(c, hipMemsetAsync(c->d_loss, 0, sizeof(float) * std::max<size_t>(rows, 1), c->stream));
@@ -2189,8 +2057,7 @@ int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, fl
   // Dp = 64..256: u^T G u by the rotation kernel (column-block partials; it
   // measured faster than quad_kernel's f32 MFMA, which keeps the other widths)
   const bool qr = !wide_dim(c->Dp) && c->Dp >= 64 && c->Dp % 32 == 0;
-  rc = ensure(c, &c->d_quad, &c->cap_quad,
-              std::max<size_t>(wide_dim(c->Dp) ? wide_quad_floats(c->Dp, hi - lo)
+  rc = ensure(c, c->d_quad, std::max<size_t>(wide_dim(c->Dp) ? wide_quad_floats(c->Dp, hi - lo)
                                : qr ? (size_t)rotate_quad_parts(c->Dp) * (size_t)(hi - lo)
                                     : rows,
                                1));
@@ -2199,7 +2066,7 @@ int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, fl
   a.quad = c->d_quad;
   a.quad_parts = qr ? rotate_quad_parts(c->Dp) : 0;
   if (wide_dim(c->Dp) || qr) {
-    if (!c->gsplit) HIP_TRY(c, hipMalloc(&c->gsplit, basis_split_bytes(c->Dp)));
+    HIP_TRY(c, c->gsplit.reserve(basis_split_bytes(c->Dp)));
     a.gsplit = c->gsplit;
   }
   a.row_ptr = c->rp[side];
@@ -2259,9 +2126,9 @@ int frecsys_eval_topk(frecsys_ctx* c, int32_t k, int32_t* topk) {
   HIP_TRY(c, hipSetDevice(c->device));
   // scores in batches of rows bounded to 1 GiB of workspace
   const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)1 << 28) / m));
-  int rc = ensure(c, &c->d_scores, &c->cap_scores, (size_t)nb * m);
+  int rc = ensure(c, c->d_scores, (size_t)nb * m);
   if (rc) return rc;
-  rc = ensure(c, &c->d_topk, &c->cap_topk, (size_t)n * k);
+  rc = ensure(c, c->d_topk, (size_t)n * k);
   if (rc) return rc;
   {
     ScopedTimer t(c, "eval_topk");
@@ -2474,7 +2341,7 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     o_ndcg = up16(o_recall + (size_t)nb * nk * 4);
     total = o_ndcg + (size_t)nb * nk * 4;
   }
-  int rc = ensure(c, &c->d_rec, &c->cap_rec, total);
+  int rc = ensure(c, c->d_rec, total);
   if (rc) return rc;
   // eligibility bits of the items: the mask and id < n_items
   std::vector<uint32_t> maskw((size_t)W, 0u);
@@ -2632,7 +2499,7 @@ int frecsys_score_pairs(frecsys_ctx* c, int32_t side, const int64_t* rows, const
   const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(64, (ws_mb << 20) / 16));
   auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
   const size_t o_rows = 0, o_items = up16((size_t)nb * 8), o_out = up16(o_items + (size_t)nb * 4);
-  int rc = ensure(c, &c->d_rec, &c->cap_rec, o_out + (size_t)nb * 4);
+  int rc = ensure(c, c->d_rec, o_out + (size_t)nb * 4);
   if (rc) return rc;
   ScorePairsArgs a{};
   a.X = c->emb[side];
@@ -2733,7 +2600,7 @@ int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, i
   const size_t o_ptr = up16(o_mask + (size_t)W * 4);
   const size_t o_qrows = up16(o_ptr + ((size_t)n + 1) * 8);
   const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
-  int rc = ensure(c, &c->d_rec, &c->cap_rec, total);
+  int rc = ensure(c, c->d_rec, total);
   if (rc) return rc;
   std::vector<uint32_t> maskw((size_t)W, 0u);
   for (int64_t j = 0; j < m; ++j)
@@ -2856,12 +2723,10 @@ int frecsys_pp_set_rating_index(frecsys_ctx* c, int32_t side, const int32_t* rix
   for (int64_t k = 0; k < nnz; ++k)
     if (rix[k] < 0 || rix[k] >= nnz)
       return fail(c, FRECSYS_ERR_INVALID, "pp_set_rating_index: index out of range");
-  if (c->d_rix[side]) HIP_TRY(c, hipFree(c->d_rix[side]));
-  c->d_rix[side] = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&c->d_rix[side], sizeof(int32_t) * std::max<int64_t>(nnz, 1)));
+  HIP_TRY(c, renew(c->d_rix[side], (size_t)nnz));
   if (nnz)
     HIP_TRY(c, hipMemcpy(c->d_rix[side], rix, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
-  return ensure(c, &c->d_pred[0], &c->cap_pred[0], (size_t)std::max<int64_t>(nnz, 1));
+  return ensure(c, c->d_pred[0], (size_t)std::max<int64_t>(nnz, 1));
 }
 
 namespace {
@@ -2890,7 +2755,7 @@ int frecsys_pp_predict(frecsys_ctx* c, int32_t side) {
     return fail(c, FRECSYS_ERR_INVALID, "pp_predict: pp_sync pending for the last sharded block step");
   HIP_TRY(c, hipSetDevice(c->device));
   if (side == 2) {
-    int rc = ensure(c, &c->d_pred[1], &c->cap_pred[1], (size_t)std::max<int64_t>(c->nnz[2], 1));
+    int rc = ensure(c, c->d_pred[1], (size_t)std::max<int64_t>(c->nnz[2], 1));
     if (rc) return rc;
   }
   PPArgs a = pp_args(c, side);
@@ -2921,25 +2786,9 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
   // from, and this rank's predictions would drift from theirs
   if (c->pp_old_side != -1)
     return fail(c, FRECSYS_ERR_INVALID, "pp_step: pp_sync pending for the last sharded block step");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int other = side == 1 ? 0 : 1;
-  {
-    int rc = join_eager(c, 3, c->stream);
-    if (rc) return rc;
-  }
+  int rc = begin_solve(c, side, p, 3);
+  if (rc) return rc;
   if (side < 2) emb_written(c, side);
-  if (kind == FRECSYS_KIND_WEIGHTED_U && p->entity_weight) {
-    int rc = upload(c, &c->d_entity_weight, &c->cap_entity_weight, p->entity_weight,
-                    (size_t)c->n[side]);
-    if (rc) return rc;
-  }
-  if (kind == FRECSYS_KIND_WEIGHTED_V) {
-    int rc = upload(c, &c->d_entity_reg, &c->cap_entity_reg, p->entity_reg, (size_t)c->n[side]);
-    if (rc) return rc;
-    rc = upload(c, &c->d_other_weight, &c->cap_other_weight, p->other_weight,
-                (size_t)c->n[other]);
-    if (rc) return rc;
-  }
   // world > 1 (USER / ITEM): this rank's shard of the rows -- the per-row
   // block steps are independent given the predictions, which every rank then
   // brings up to date for the other ranks' rows (pp_refresh_kernel, bitwise
@@ -2950,8 +2799,7 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
   if (sharded) shard(c, side, &lo, &hi);
   const int bw = end - start;
   if (sharded) {  // the block columns before the step: the refresh replays Delta from them
-    int rc = ensure(c, &c->d_pp_old, &c->cap_pp_old,
-                    (size_t)std::max<int64_t>(c->n[side], 1) * bw);
+    rc = ensure(c, c->d_pp_old, (size_t)std::max<int64_t>(c->n[side], 1) * bw);
     if (rc) return rc;
     if (c->n[side])
       HIP_TRY(c, hipMemcpy2DAsync(c->d_pp_old, sizeof(float) * bw, c->emb[side] + start,
@@ -2963,11 +2811,11 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
   for (int64_t i = lo; i < hi; ++i) recs[i - lo] = QueueRec{(int32_t)i, (int32_t)(rp[i + 1] - rp[i]), rp[i]};
   std::stable_sort(recs.begin(), recs.end(),
                    [](const QueueRec& x, const QueueRec& y) { return x.h > y.h; });
-  QueueRec* d_q = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_q, sizeof(QueueRec) * std::max<size_t>(recs.size(), 1)));
+  DevBuf<QueueRec> d_q;
+  HIP_TRY(c, d_q.reserve(recs.size()));
   HIP_TRY(c, hipMemcpyAsync(d_q, recs.data(), sizeof(QueueRec) * recs.size(), hipMemcpyHostToDevice,
                             c->stream));
-  int rc = ensure(c, &c->d_resid, &c->cap_resid, std::max<size_t>(recs.size(), 1));
+  rc = ensure(c, c->d_resid, std::max<size_t>(recs.size(), 1));
   if (rc) return rc;
   PPArgs a = pp_args(c, side);
   a.order = d_q;
@@ -2980,15 +2828,11 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
   a.w = p->unobserved_weight;
   a.alpha = p->alpha;
   a.entity_weight =
-      (kind == FRECSYS_KIND_WEIGHTED_U && p->entity_weight) ? c->d_entity_weight : nullptr;
-  a.entity_reg = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_entity_reg : nullptr;
-  a.other_weight = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_other_weight : nullptr;
+      (kind == FRECSYS_KIND_WEIGHTED_U && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
+  a.entity_reg = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_entity_reg.dev.get() : nullptr;
+  a.other_weight = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_other_weight.dev.get() : nullptr;
   a.resid = c->d_resid;
   const unsigned long long none = ~0ull;
-  // ~0ull by a device-side fill: an H2D copy from host memory at this point
-  // was observed starting only after the early basis build queued on another
-  // stream had finished, holding back the fork of the d-space solve
-  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(none), c->stream));
   {
     ScopedTimer t(c, "pp_step");
     HIP_TRY(c, launch_pp_step(a, c->stream));
@@ -3011,12 +2855,12 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
   }
   std::vector<float> res(recs.size());
   unsigned long long f = none;
-  HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
   if ((residual || xchg) && !recs.empty())
     HIP_TRY(c, hipMemcpyAsync(res.data(), c->d_resid, sizeof(float) * recs.size(),
                               hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipFree(d_q));
+  rc = end_solve(c, side, false, &f);  // the rows were exchanged under the step's timer
+  if (rc) return rc;
+  HIP_TRY(c, d_q.release());
   if (f != none) {
     c->err_entity = (int64_t)(f - 1);
     return fail(c, FRECSYS_ERR_NOT_SPD, "pp_step: block matrix not SPD");
@@ -3038,7 +2882,7 @@ int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
     }
     std::vector<float> ent((size_t)std::max<int64_t>(n, 1), 0.0f);
     for (size_t i = 0; i < recs.size(); ++i) ent[recs[i].entity] = res[i];
-    rc = ensure(c, &c->d_resid_e, &c->cap_resid_e, (size_t)std::max<int64_t>(n, 1));
+    rc = ensure(c, c->d_resid_e, (size_t)std::max<int64_t>(n, 1));
     if (rc) return rc;
     if (n) HIP_TRY(c, hipMemcpyAsync(c->d_resid_e, ent.data(), sizeof(float) * n,
                                      hipMemcpyHostToDevice, c->stream));
@@ -3102,7 +2946,7 @@ int frecsys_train_stats(frecsys_ctx* c, double* observed, double* unobserved,
   HIP_TRY(c, hipSetDevice(c->device));
   const int64_t nu = c->n[0], ni = c->n[1];
   const int Dp = c->Dp;
-  int rc = ensure(c, &c->d_rows, &c->cap_rows, (size_t)std::max<int64_t>(std::max(nu, ni), 1));
+  int rc = ensure(c, c->d_rows, (size_t)std::max<int64_t>(std::max(nu, ni), 1));
   if (rc) return rc;
   ScopedTimer t(c, "train_stats");
   if (observed) {
@@ -3128,9 +2972,9 @@ int frecsys_train_stats(frecsys_ctx* c, double* observed, double* unobserved,
     *observed = s;
   }
   if (unobserved) {
-    rc = ensure(c, &c->d_gstat, &c->cap_gstat, (size_t)2 * Dp * Dp);
+    rc = ensure(c, c->d_gstat, (size_t)2 * Dp * Dp);
     if (rc) return rc;
-    rc = ensure(c, &c->d_dot, &c->cap_dot, 1);
+    rc = ensure(c, c->d_dot, 1);
     if (rc) return rc;
     for (int s = 0; s < 2; ++s) {
       rc = form_gramian(c, 2, c->emb[s], c->n[s], nullptr, c->d_gstat + (size_t)s * Dp * Dp, true);
@@ -3166,19 +3010,13 @@ int frecsys_release_workspaces(frecsys_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream5));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  auto rel = [&](auto** p, size_t* cap) -> int {
-    if (*p) HIP_TRY(c, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    return FRECSYS_OK;
-  };
-  int rc = rel(&c->wide_ws, &c->cap_wide_ws);
-  if (!rc) rc = rel(&c->wide_xs, &c->cap_wide_xs);
-  if (!rc) rc = rel(&c->d_slabs, &c->cap_slabs);
-  if (!rc) rc = rel(&c->dw_zs, &c->cap_dw_zs);
-  if (!rc) rc = rel(&c->dw_slots, &c->cap_dw_slots);
-  if (!rc) rc = rel(&c->dw_z, &c->cap_dw_z);
-  return rc;
+  HIP_TRY(c, c->wide_ws.release());
+  HIP_TRY(c, c->wide_xs.release());
+  HIP_TRY(c, c->d_slabs.release());
+  HIP_TRY(c, c->dw_zs.release());
+  HIP_TRY(c, c->dw_slots.release());
+  HIP_TRY(c, c->dw_z.release());
+  return FRECSYS_OK;
 }
 
 int frecsys_timing(const frecsys_ctx* c, const char* what, double* total_ms, int64_t* launches) {
@@ -3207,21 +3045,18 @@ int frecsys_debug_diag_factor(frecsys_ctx* c, int32_t blocked, int32_t n_tiles, 
     return fail(c, FRECSYS_ERR_INVALID, "debug_diag_factor: bad arguments");
   if (n_tiles == 0) return FRECSYS_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  float *dA = nullptr, *dL = nullptr;
-  int* dok = nullptr;
+  DevBuf<float> dA, dL;
+  DevBuf<int> dok;
   const size_t bytes = sizeof(float) * 1024 * (size_t)n_tiles;
-  HIP_TRY(c, hipMalloc((void**)&dA, bytes));
-  HIP_TRY(c, hipMalloc((void**)&dL, bytes));
-  HIP_TRY(c, hipMalloc((void**)&dok, sizeof(int) * (size_t)n_tiles));
+  HIP_TRY(c, dA.reserve((size_t)1024 * n_tiles));
+  HIP_TRY(c, dL.reserve((size_t)1024 * n_tiles));
+  HIP_TRY(c, dok.reserve((size_t)n_tiles));
   HIP_TRY(c, hipMemcpyAsync(dA, a, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, launch_debug_diag(dA, dL, dok, n_tiles, blocked ? 1 : 0, c->stream));
   HIP_TRY(c, hipMemcpyAsync(linv, dL, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(ok, dok, sizeof(int) * (size_t)n_tiles, hipMemcpyDeviceToHost,
                             c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipFree(dA));
-  HIP_TRY(c, hipFree(dL));
-  HIP_TRY(c, hipFree(dok));
   return FRECSYS_OK;
 }
 
@@ -3275,6 +3110,10 @@ int frecsys_counter(frecsys_ctx* c, const char* what, int64_t* value) {
     *value = c->rec_splits;
     return FRECSYS_OK;
   }
+  if (!strcmp(what, "live_device_bytes")) {  // of the process, not of this context
+    *value = live_device_bytes().load();
+    return FRECSYS_OK;
+  }
   if (!strcmp(what, "tagged_timeouts")) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream5));
@@ -3292,7 +3131,7 @@ int frecsys_snapshot_residual(frecsys_ctx* c, int32_t side, double* sq) {
   if (!c->snap[side]) return fail(c, FRECSYS_ERR_INVALID, "snapshot_residual: no snapshot taken");
   HIP_TRY(c, hipSetDevice(c->device));
   const int64_t n = c->n[side];
-  int rc = ensure(c, &c->d_rows, &c->cap_rows, (size_t)std::max<int64_t>(n, 1));
+  int rc = ensure(c, c->d_rows, (size_t)std::max<int64_t>(n, 1));
   if (rc) return rc;
   *sq = 0.0;
   if (n == 0) return FRECSYS_OK;

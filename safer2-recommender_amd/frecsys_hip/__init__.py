@@ -434,7 +434,8 @@ class Context:
     def counter(self, what: str) -> int:
         """Cumulative event counter: "hspace_reruns", "tagged_timeouts" or
         "ws_shrinks"; "recommend_splits": the item splits of the last
-        recommend call."""
+        recommend call; "live_device_bytes": the device memory the buffers
+        of every context of the process hold now."""
         v = ctypes.c_int64()
         self._check(self.lib.frecsys_counter(self.h, what.encode(), ctypes.byref(v)))
         return int(v.value)
