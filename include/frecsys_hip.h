@@ -452,6 +452,49 @@ int frecsys_rank_candidates(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
                             const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                             int32_t flags, const uint8_t* item_mask, int32_t* items,
                             float* scores);
+/* Nearest neighbours inside one factor table ("items like this item", "users
+ * like this user"; no reference counterpart): T, the table of `side` (USER or
+ * ITEM), is both the source of the queries and the table searched.  Query row
+ * i is row rows[i] of T (any order, repeats allowed), or row i when rows is
+ * NULL; it lists the k best eligible rows of T by descending score, ties by
+ * ascending id, into ids[i*k .. i*k+k) and, unless scores is NULL, their
+ * scores into scores[i*k .. i*k+k) (host).  A row j is eligible when its mask
+ * byte is non-zero (mask: host [rows of side], or NULL = every row) and,
+ * without FRECSYS_SIM_KEEP_SELF, j != rows[i]: a query never lists its own id,
+ * but rows that are equal to it in value are listed (cosine ~ 1, ties by id).
+ * 1 <= k <= 1024; the slots beyond the eligible count hold id -1 and score
+ * -FLT_MAX, as in frecsys_recommend.
+ *   dot(q, j): frecsys_recommend's chain, acc = fma(T[j][c], T[q][c], acc)
+ * over the padded dim in ascending c from +0 -- bit for bit what
+ * frecsys_recommend would list if T were both its user and its item table.
+ * Without FRECSYS_SIM_COSINE it is the score.
+ *   With FRECSYS_SIM_COSINE: n2_r = dot(r, r), inv_r = n2_r > 0 ?
+ * 1.0f / sqrtf(n2_r) : 0.0f with correctly rounded sqrt and division, and the
+ * score is (dot(q, j) * inv_q) * inv_j + 0.0f, two fp32 multiplies in exactly
+ * that order (the + 0.0f keeps -0.0 out of the keys, as the dot chain does by
+ * construction).  A zero row has cosine +0 with everything.  inv_r depends on
+ * row r alone, not on the batch, the split or the grid.
+ * The norms are computed per call (one lane per row, the chain above: the
+ * tables change with every solve), the scan is frecsys_recommend's with the
+ * scores scaled before they become keys and the row's own id cleared from its
+ * eligibility bits; no normalised copy of T and no rows x rows score matrix
+ * exists.  Workspace and knobs are frecsys_recommend's (FRECSYS_RECOMMEND_WS_MB,
+ * FRECSYS_RECOMMEND_SPLITS: read per call, neither changes a result bit), no
+ * history bitmap; the inverse norms add 4 * rows-of-side bytes outside the
+ * per-row budget.  Both buffers go with frecsys_release_workspaces.
+ * Rank-local at any world size: no collective.  n_rows == 0 returns
+ * FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID, before any device
+ * call: a null context, side EVAL or unknown, k out of range, an unknown flag
+ * bit, a row id out of range, rows == NULL with n_rows above the side's rows,
+ * null ids with n_rows > 0, a side without embeddings.  Timer keys "similar"
+ * (one launch group per row batch) and "similar.norms";
+ * frecsys_work("similar"): 2 rows m d flops (m = rows of side), bytes =
+ * (rows + 2 m) d 4 + 8 rows k (the second m d 4 is the norm pass: cosine
+ * only). */
+#define FRECSYS_SIM_COSINE 1    /* score = cosine; without it: dot product */
+#define FRECSYS_SIM_KEEP_SELF 2 /* without it a query row never lists itself */
+int frecsys_similar(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                    int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids, float* scores);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,
@@ -492,7 +535,9 @@ int frecsys_synchronize(frecsys_ctx* ctx);
 /* Free the wide-dim workspaces (batch workspace of A tiles, long-history
  * slabs, pre-split table, history-space wide bucket); the next solve sizes
  * them again within FRECSYS_WIDE_WS_MB and a quarter of the then free device
- * memory each.  For a caller that needs the device memory between phases
+ * memory each.  The ranking workspace of frecsys_recommend and its
+ * relatives and the inverse norms of frecsys_similar go too; the next such
+ * call sizes them again. For a caller that needs the device memory between phases
  * (evaluation, another model).  No reference counterpart: the reference's
  * per-thread Eigen temporaries are freed per entity. */
 int frecsys_release_workspaces(frecsys_ctx* ctx);

@@ -125,6 +125,21 @@ int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_
                                   const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                                   int32_t exclude_seen, const uint8_t* item_mask,
                                   int32_t* items, float* scores);
+/* The k nearest neighbours of trained items among the items (items[i]: a row
+ * of V) and of trained users among the users (users[i]: a row of U), by cosine
+ * (FRECSYS_SIM_COSINE in flags) or dot product; without FRECSYS_SIM_KEEP_SELF
+ * a query never lists itself.  items / users: n row ids, any order, repeats
+ * allowed, or NULL = rows 0 .. n-1; item_mask / user_mask: host [n_items] /
+ * [n_users] eligibility bytes or NULL; ids / scores: host [n * k] (scores may
+ * be NULL).  Scores, order, ties, the -1 / -FLT_MAX fill and the errors are
+ * frecsys_similar's (frecsys_hip.h); the arguments are checked before any
+ * device call. */
+int frecsys_model_similar_items(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* item_mask, int32_t* ids,
+                                float* scores);
+int frecsys_model_similar_users(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* user_mask, int32_t* ids,
+                                float* scores);
 /* The same for n unseen users given by their histories (as
  * frecsys_model_recommend_fold_in): the model's fold-in projection into the
  * EVAL side of its context, where the projected rows stay, then the ranking

@@ -140,6 +140,7 @@ struct frecsys_ctx {
   DevBuf<float> d_scores;        // evaluation: [batch][items] scores
   DevBuf<int32_t> d_topk;        // [eval rows][k]
   DevBuf<char> d_rec;            // frecsys_recommend: candidates, counts, bitmaps, outputs
+  DevBuf<float> d_sim_inv;       // frecsys_similar: inverse row norms of the side searched
   int64_t rec_splits = 0;       // item splits of the last call (frecsys_counter "recommend_splits")
   // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
   // per row of each side (device scratch + host copy; -1: not solved here),
@@ -332,19 +333,48 @@ size_t ws_budget(frecsys_ctx* c, size_t held) {
   return b;
 }
 
+// What a workspace that was cut after a failed hipMalloc leaves free.  The
+// halving would otherwise stop at the largest size that still fits, i.e. with
+// the device full to within that size's granularity, and the runtime has
+// allocations of its own to make after it: a failed hipMalloc makes it give
+// back the idle queues' scratch memory, and the next kernel with a private
+// segment (wide_syrk2_kernel: 20..28 B per lane, a 2 KiB granule per wave x 32
+// waves x 256 CUs x 8 XCCs = 128 MiB for a grid that fills the device) has its
+// dispatch aborted with HSA_STATUS_ERROR_OUT_OF_RESOURCES when that scratch
+// cannot be allocated again.  512 MiB: four times that, and room for the
+// pre-split table of a short other side, which is allocated behind the cut
+// workspaces without a cut of its own.
+constexpr size_t kRuntimeHeadroom = (size_t)512 << 20;
+bool below_headroom() {
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return fr < kRuntimeHeadroom;
+}
+
 // A workspace of *batch slots of `per` elements: a failed hipMalloc halves
-// the batch (counted in ws_shrinks) until one slot does not fit either.
-// Entities are independent, so the batch size never changes a result.
+// the batch (counted in ws_shrinks) until one slot does not fit either, and a
+// batch that fits only after such a cut is halved on while it leaves less
+// than kRuntimeHeadroom free.  Entities are independent, so the batch size
+// never changes a result.
 template <typename T>
 int ensure_batch(frecsys_ctx* c, DevBuf<T>& b, size_t per, int64_t* batch) {
+  bool cut = false;
   while (true) {
     bool oom = false;
     int rc = try_ensure(c, b, per * (size_t)*batch, &oom);
-    if (rc || !oom) return rc;
-    if (*batch <= 1)
+    if (rc) return rc;
+    if (!oom) {
+      if (!cut || *batch <= 1 || !below_headroom()) return FRECSYS_OK;
+      HIP_TRY(c, b.release());
+    } else if (*batch <= 1) {
       return fail(c, FRECSYS_ERR_HIP, "hipMalloc: out of memory for one workspace slot");
+    }
     *batch = (*batch + 1) / 2;
     ++c->ws_shrinks;
+    cut = true;
   }
 }
 
@@ -473,6 +503,7 @@ int plan_split(frecsys_ctx* c, const std::vector<int32_t>& hs, int64_t n,
   a->n_work = 0;
   if (c->split_rows <= 0 || C <= 0 || c->Dp < 32) return FRECSYS_OK;
   int32_t slab = 0;
+  bool cut = false;
   while (true) {
     c->h_split.clear();
     c->h_work.clear();
@@ -496,9 +527,13 @@ int plan_split(frecsys_ctx* c, const std::vector<int32_t>& hs, int64_t n,
     bool oom = false;
     int rc = try_ensure(c, c->d_slabs, (size_t)slab * slab_floats, &oom);
     if (rc) return rc;
-    if (!oom) break;
+    if (!oom) {  // as ensure_batch: a cut allocation leaves kRuntimeHeadroom free
+      if (!cut || slab <= 1 || !below_headroom()) break;
+      HIP_TRY(c, c->d_slabs.release());
+    }
     ++c->ws_shrinks;
     max_slabs = slab / 2;
+    cut = true;
   }
   int rc = ensure(c, c->d_split, c->h_split.size());
   if (rc) return rc;
@@ -2653,6 +2688,114 @@ int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, i
   return FRECSYS_OK;
 }
 
+int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
+                    int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "similar: null context");
+  const std::string w = "similar: ";
+  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_ITEM)
+    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or ITEM");
+  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
+  if (flags & ~(FRECSYS_SIM_COSINE | FRECSYS_SIM_KEEP_SELF))
+    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  if (n_rows < 0 || (n_rows > 0 && !ids))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  // (cannot happen today: a context allocates the USER and ITEM tables when it
+  // is created; kept for the day a side's table is allocated lazily)
+  if (!c->emb[side]) return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t m = c->n[side], n = n_rows;
+  if (rows) {
+    for (int64_t i = 0; i < n; ++i)
+      if (rows[i] < 0 || rows[i] >= m)
+        return fail(c, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(rows[i]) + " out of range");
+  } else if (n > m) {
+    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
+  }
+  if (n == 0) return FRECSYS_OK;
+  const bool cosine = (flags & FRECSYS_SIM_COSINE) != 0;
+  const bool skip_self = !(flags & FRECSYS_SIM_KEEP_SELF);
+  HIP_TRY(c, hipSetDevice(c->device));
+  // frecsys_recommend's knobs and workspace scheme (no history bitmap: the one
+  // excluded id of a row is tested in the scan), read per call
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  int dev_cus = 256;
+  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int max_splits = recommend_max_splits(k, m);
+  const int64_t row_blocks = (n + 63) / 64;
+  int splits = (int)std::min<int64_t>(max_splits, (2 * (int64_t)dev_cus + row_blocks - 1) / row_blocks);
+  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS"))
+    if (atoi(v) > 0) splits = std::min(max_splits, atoi(v));
+  splits = std::max(1, splits);
+  const int cap = recommend_cap(k);
+  const int64_t W = recommend_words(m);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  // per row of a batch: candidates, counts, outputs
+  const size_t per_row = (size_t)splits * cap * 8 + (size_t)splits * 4 + (size_t)k * 8;
+  int64_t nb = std::max<int64_t>(1, (int64_t)(((size_t)ws_mb << 20) / per_row));
+  if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
+  nb = std::min(nb, n);
+  const size_t o_cand = 0;
+  const size_t o_counts = up16(o_cand + (size_t)nb * splits * cap * 8);
+  const size_t o_items = up16(o_counts + (size_t)nb * splits * 4);
+  const size_t o_scores = up16(o_items + (size_t)nb * k * 4);
+  const size_t o_mask = up16(o_scores + (size_t)nb * k * 4);
+  const size_t o_qrows = up16(o_mask + (size_t)W * 4);
+  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
+  int rc = ensure(c, c->d_rec, total);
+  if (rc) return rc;
+  // outside the per-row budget: one inverse norm per row of the side
+  if (cosine && (rc = ensure(c, c->d_sim_inv, (size_t)m))) return rc;
+  std::vector<uint32_t> maskw((size_t)W, 0u);
+  for (int64_t j = 0; j < m; ++j)
+    if (!mask || mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
+                            hipMemcpyHostToDevice, c->stream));
+  if (rows)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (cosine) {  // per call: every solve rewrites the table
+    ScopedTimer t(c, "similar.norms");
+    HIP_TRY(c, launch_row_inv_norm(c->emb[side], m, c->Dp, c->d_sim_inv, c->stream));
+    t.stop();
+  }
+  RecommendArgs a{};
+  a.X = c->emb[side];
+  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
+  a.Y = c->emb[side];
+  a.m = m;
+  a.Dp = c->Dp;
+  a.k = k;
+  a.splits = splits;
+  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
+  a.cand = (unsigned long long*)(c->d_rec + o_cand);
+  a.counts = (int32_t*)(c->d_rec + o_counts);
+  a.out_items = (int32_t*)(c->d_rec + o_items);
+  a.out_scores = (float*)(c->d_rec + o_scores);
+  a.inv = cosine ? (const float*)c->d_sim_inv : nullptr;
+  a.skip_self = skip_self ? 1 : 0;
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
+    a.r0 = r0;
+    a.n = std::min(nb, n - r0);
+    ScopedTimer t(c, "similar");
+    HIP_TRY(c, launch_recommend(a, c->stream));
+    t.stop();
+    HIP_TRY(c, hipMemcpyAsync(ids + r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
+                              hipMemcpyDeviceToHost, c->stream));
+    if (scores)
+      HIP_TRY(c, hipMemcpyAsync(scores + r0 * k, a.out_scores, sizeof(float) * a.n * k,
+                                hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // scoring flops at the logical dim; bytes: the queries and the table read,
+  // the table once more by the norm pass, the lists written
+  const double dd = c->dim;
+  add_work(c, "similar", 2.0 * (double)n * (double)m * dd,
+           ((double)n + (cosine ? 2.0 : 1.0) * (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
 int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
                          const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
                          float* ndcg) {
@@ -3016,6 +3159,8 @@ int frecsys_release_workspaces(frecsys_ctx* c) {
   HIP_TRY(c, c->dw_zs.release());
   HIP_TRY(c, c->dw_slots.release());
   HIP_TRY(c, c->dw_z.release());
+  HIP_TRY(c, c->d_rec.release());
+  HIP_TRY(c, c->d_sim_inv.release());
   return FRECSYS_OK;
 }
 

@@ -348,6 +348,9 @@ struct RecommendArgs {
   int32_t* counts;           // [n][splits] candidates kept per split (workspace)
   int32_t* out_items;        // [n][k]
   float* out_scores;         // [n][k]
+  // frecsys_similar (X == Y): either one selects the scan's second instantiation
+  const float* inv;          // [m] inverse row norms of Y: the score is the cosine; or nullptr
+  int skip_self;             // != 0: query row i never lists id qrows[r0 + i]
 };
 // Candidate slots per (row, split): 4 k rounded up to a power of two, from
 // 512 to 2048 (2 k at k = 1024: a 128-item tile always fits behind k kept
@@ -359,6 +362,12 @@ int64_t recommend_words(int64_t m);
 // candidates within the merge kernel's LDS.
 int recommend_max_splits(int k, int64_t m);
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
+// Inverse row norms of a table (similar.hip): n2 = the chain acc = fmaf(T[r][c],
+// T[r][c], acc), c ascending from +0 over the padded dim -- recommend.hip's
+// score of row r with itself, bit for bit -- and inv[r] = n2 > 0 ?
+// 1 / sqrt(n2) : 0, sqrt and division correctly rounded.  A function of row r
+// alone.
+hipError_t launch_row_inv_norm(const float* T, int64_t m, int Dp, float* inv, hipStream_t s);
 
 // Scores of caller-supplied pairs and rankings of caller-supplied candidate
 // lists (rerank.hip).  Every score is the chain acc = fmaf(y[c], x[c], acc),

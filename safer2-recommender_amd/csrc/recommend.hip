@@ -18,7 +18,12 @@
 //                       the row's threshold to the row's candidate buffer in
 //                       HBM / L2, and compacts a buffer to its best k (one
 //                       wave per row, bitonic sort in LDS) before a further
-//                       tile could overflow it;
+//                       tile could overflow it.
+//                       Its SIM instantiation is the scan behind
+//                       frecsys_similar (X = Y = one table): the scores are
+//                       scaled by the two rows' inverse norms before they
+//                       become keys (cosine), and a query row never appends
+//                       its own id;
 //   rec_merge_kernel    one workgroup per row: the best k of the splits'
 //                       candidates, ids and scores out, -1 / -FLT_MAX in the
 //                       slots beyond the eligible count.
@@ -41,7 +46,9 @@
 // k-th best and it could never be listed; with any other order of the ids a
 // tie with the k-th key would have to be kept.  (Inside one tile the appends
 // are unordered, but the threshold does not move there.  Stored as key + 1
-// with the test key >= that, so that 0 means "no threshold yet".)
+// with the test key >= that, so that 0 means "no threshold yet".)  The SIM
+// scan keeps the invariant: it sweeps ids ascending too, and its keys are
+// those of the final, scaled score.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -111,7 +118,13 @@ __device__ __forceinline__ int compact_row(u64* __restrict__ g, u64* sb, int nn,
 // read of xs / ys is done) and the barrier that opens the next tile's first
 // k-slab (no wave stages before every wave has arrived there).
 constexpr int kStageFloats = RT * 33 + 32 * (IT + 1);
-template <int CAP>
+// SIM = false is frecsys_recommend's scan.  SIM = true (frecsys_similar) reads
+// a.inv / a.skip_self, which the other instantiation never touches: with
+// a.inv the key is that of (dot * inv[query]) * inv[id] + 0.0f, two fp32
+// multiplies in that order (the + 0.0f turns a -0.0 product into +0, which
+// the dot chain never yields), and with a.skip_self the row's own id is
+// cleared from the tile's eligibility word.
+template <int CAP, bool SIM>
 // 512 slots: registers for 4 waves per SIMD (4 workgroups of 27 KB per CU; the
 // k-slab staging is latency-bound).  The larger sort slices allow 3 and 2.
 __global__ void __launch_bounds__(256, CAP == 512 ? 4 : (CAP == 1024 ? 3 : 2))
@@ -127,6 +140,7 @@ __global__ void __launch_bounds__(256, CAP == 512 ? 4 : (CAP == 1024 ? 3 : 2))
   __shared__ uint32_t elig[RT * 4];
   __shared__ int64_t xrow[RT];
   __shared__ u64* cbase[RT];  // the row's candidate buffer of this split
+  __shared__ float yinv[SIM ? IT : 1];  // SIM: inverse norms of the tile's ids
   const int tid = threadIdx.x, lane = tid & 63, lo = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t base = (int64_t)blockIdx.x * RT;
@@ -146,6 +160,13 @@ __global__ void __launch_bounds__(256, CAP == 512 ? 4 : (CAP == 1024 ? 3 : 2))
   const int NC = (Dp + 31) >> 5;
   const int rl = 32 * R + lo;  // the lane's query row in the block
   u64* const mycand = a.cand + ((base + rl) * splits + split) * CAP;
+  float inv_q = 0.0f;  // SIM: the inverse norm of the lane's query row,
+  int64_t self = -1;   // and the id it never lists
+  if constexpr (SIM) {
+    const int64_t xr = xrow[rl];
+    if (a.inv && xr >= 0) inv_q = a.inv[xr];
+    if (a.skip_self) self = xr;
+  }
   for (int64_t tile = t0; tile < t1; ++tile) {
     const int64_t j0 = tile * IT;
     {  // eligibility words of the tile: 4 per row (the readers of the last
@@ -157,6 +178,9 @@ __global__ void __launch_bounds__(256, CAP == 512 ? 4 : (CAP == 1024 ? 3 : 2))
         if (a.bitmap) word &= ~a.bitmap[(base + rr) * W + tile * 4 + w];
       }
       elig[tid] = word;
+      if constexpr (SIM) {
+        if (a.inv && tid < IT) yinv[tid] = j0 + tid < a.m ? a.inv[j0 + tid] : 0.0f;
+      }
     }
     f32x16 acc[2] = {f32x16{0.f}, f32x16{0.f}};
     for (int c = 0; c < NC; ++c) {
@@ -193,7 +217,17 @@ __global__ void __launch_bounds__(256, CAP == 512 ? 4 : (CAP == 1024 ? 3 : 2))
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int C = Cs + t;
-        const uint32_t ew = elig[rl * 4 + C];
+        uint32_t ew = elig[rl * 4 + C];
+        if constexpr (SIM) {
+          const int64_t so = self - (j0 + 32 * C);
+          if (so >= 0 && so < 32) ew &= ~(1u << so);
+          if (a.inv) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+              acc[t][q] = __fadd_rn(
+                  __fmul_rn(__fmul_rn(acc[t][q], inv_q), yinv[32 * C + acc_row(q, hi)]), 0.0f);
+          }
+        }
         uint32_t pm = 0;
 #pragma unroll
         for (int q = 0; q < 16; ++q)
@@ -284,8 +318,11 @@ __global__ void __launch_bounds__(256) rec_merge_kernel(RecommendArgs a, int64_t
 
 template <int CAP>
 void launch_cap(const RecommendArgs& a, int64_t W, hipStream_t s) {
-  hipLaunchKernelGGL(rec_scan_kernel<CAP>, dim3((unsigned)((a.n + RT - 1) / RT), (unsigned)a.splits),
-                     dim3(256), 0, s, a, W);
+  const dim3 grid((unsigned)((a.n + RT - 1) / RT), (unsigned)a.splits);
+  if (a.inv || a.skip_self)
+    hipLaunchKernelGGL((rec_scan_kernel<CAP, true>), grid, dim3(256), 0, s, a, W);
+  else
+    hipLaunchKernelGGL((rec_scan_kernel<CAP, false>), grid, dim3(256), 0, s, a, W);
   hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)a.n), dim3(256), 0, s, a, (int64_t)CAP);
 }
 

@@ -19,6 +19,7 @@ import numpy as np
 
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
 REC_EXCLUDE_HISTORY = 1
+SIM_COSINE, SIM_KEEP_SELF = 1, 2
 # the cut-offs and tail levels run_model evaluates (run_model.cc:97-100)
 EVAL_K_LIST = (5, 10, 20, 50, 100)
 EVAL_ALPHA_LIST = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
@@ -48,6 +49,7 @@ EXPORTS = (
     "frecsys_set_transport", "frecsys_recommend", "frecsys_solve_side_cg",
     "frecsys_cg_iterations", "frecsys_list_metrics", "frecsys_metric_cvar",
     "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
+    "frecsys_similar",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -59,6 +61,7 @@ MODEL_EXPORTS = (
     "frecsys_model_evaluate", "frecsys_model_evaluate_fold_in",
     "frecsys_model_score", "frecsys_model_rank_candidates",
     "frecsys_model_rank_candidates_fold_in",
+    "frecsys_model_similar_items", "frecsys_model_similar_users",
 )
 
 
@@ -183,6 +186,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_rank_metrics": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, I32, P, P]),
         "frecsys_score_pairs": (ctypes.c_int, [P, I32, P, P, I64, P]),
         "frecsys_rank_candidates": (ctypes.c_int, [P, I32, P, I64, P, P, I32, I32, P, P, P]),
+        "frecsys_similar": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -220,6 +224,8 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
                                            [P, P, P, I64, P, P, P, I32, P, I32, I32, P, P, P]),
         "frecsys_model_score": (ctypes.c_int, [P, P, P, I64, P]),
         "frecsys_model_rank_candidates": (ctypes.c_int, [P, P, I64, P, P, I32, I32, P, P, P]),
+        "frecsys_model_similar_items": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
+        "frecsys_model_similar_users": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
         "frecsys_model_rank_candidates_fold_in": (ctypes.c_int,
                                                   [P, P, P, I64, P, P, I32, I32, P, P, P]),
     }
@@ -441,7 +447,8 @@ class Context:
         return int(v.value)
 
     def release_workspaces(self) -> None:
-        """Free the wide-dim workspaces (resized at the next solve)."""
+        """Free the wide-dim workspaces (resized at the next solve) and the
+        ranking workspaces of recommend / similar (resized at the next call)."""
         self._check(self.lib.frecsys_release_workspaces(self.h))
 
     # -- compute --
@@ -625,6 +632,29 @@ class Context:
             self.h, side, _ptr(r), n, _ptr(cp), _ptr(ci), k,
             REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def similar(self, side: int, k: int, rows=None, cosine: bool = True, keep_self: bool = False,
+                mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(ids int32 [n, k], scores float32 [n, k]): the k nearest rows of
+        the table of `side` (SIDE_USER or SIDE_ITEM) for each query row of the
+        same table, by score descending, id ascending -- frecsys_similar.  The
+        score is the cosine (cosine=True) or recommend's dot product; without
+        keep_self a query never lists its own id.  rows: row ids (any order,
+        repeats allowed; None = every row of the side); mask [rows of side]:
+        non-zero = candidate.  Slots beyond the eligible count hold id -1 and
+        score -FLT_MAX."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[side],), mk.shape
+        ids = np.full((n, k) if k > 0 else (n, 0), -1, dtype=np.int32)
+        scores = np.zeros(ids.shape, dtype=np.float32)
+        flags = (SIM_COSINE if cosine else 0) | (SIM_KEEP_SELF if keep_self else 0)
+        self._check(self.lib.frecsys_similar(self.h, side, _ptr(r), n, k, flags, _ptr(mk),
+                                             _ptr(ids), _ptr(scores)))
+        return ids, scores
 
     def pp_set_rating_index(self, side: int, rix: np.ndarray):
         r = np.ascontiguousarray(rix, dtype=np.int32)
@@ -858,6 +888,39 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return items, scores
+
+    def _similar(self, fn, n_side: int, rows, k: int, metric: str, include_self: bool, mask):
+        if metric not in ("cosine", "dot"):
+            raise ValueError(f"metric must be 'cosine' or 'dot', not {metric!r}")
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert mk.shape == (n_side,), mk.shape
+        ids = np.full((len(r), k) if k > 0 else (len(r), 0), -1, dtype=np.int32)
+        scores = np.zeros(ids.shape, dtype=np.float32)
+        flags = (SIM_COSINE if metric == "cosine" else 0) | (SIM_KEEP_SELF if include_self else 0)
+        rc = fn(self.h, _ptr(r), len(r), k, flags, _ptr(mk), _ptr(ids), _ptr(scores))
+        if rc != OK:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return ids, scores
+
+    def similar_items(self, items, k: int, metric: str = "cosine", include_self: bool = False,
+                      item_mask=None):
+        """(ids int32 [n, k], scores float32 [n, k]): the k items nearest to
+        each of the trained items `items` (rows of V) by metric "cosine" or
+        "dot" (recommend's score), ties by id -- frecsys_model_similar_items.
+        Without include_self an item never lists itself; item_mask [n_items]:
+        non-zero = candidate; -1 / -FLT_MAX beyond the eligible count."""
+        return self._similar(self.lib.frecsys_model_similar_items, self.n_items, items, k, metric,
+                             include_self, item_mask)
+
+    def similar_users(self, users, k: int, metric: str = "cosine", include_self: bool = False,
+                      user_mask=None):
+        """The same among the trained users (rows of U) --
+        frecsys_model_similar_users; user_mask [n_users]."""
+        return self._similar(self.lib.frecsys_model_similar_users, self.n_users, users, k, metric,
+                             include_self, user_mask)
 
     def rank_candidates_fold_in(self, hist_ptr, hist_items, cand_ptr, cand_items, k: int,
                                 exclude_seen: bool = True, item_mask=None):

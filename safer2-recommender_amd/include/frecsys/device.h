@@ -236,6 +236,14 @@ class DeviceContext {
                                    items, scores);
   }
 
+  // Nearest neighbours inside the table of `side` (USER or ITEM) by cosine or
+  // dot product (frecsys_similar; flags: FRECSYS_SIM_*).  The status code, for
+  // callers that report errors.
+  int TrySimilar(int side, const int64_t* rows, int64_t n, int k, int flags, const uint8_t* mask,
+                 int32_t* ids, float* scores) {
+    return frecsys_similar(ctx_, side, rows, n, k, flags, mask, ids, scores);
+  }
+
   // Recall@K / NDCG@K of the ranking Recommend would return with
   // k = max(k_list), computed on the device (frecsys_rank_metrics): recall,
   // ndcg: host [n * nk]; ground-truth row i belongs to query row i.  The

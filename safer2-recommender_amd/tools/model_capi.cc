@@ -245,6 +245,30 @@ int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_
   return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
 }
 
+static int model_similar(frecsys_model* m, const char* what, int side, const int64_t* rows,
+                         int64_t n, int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids,
+                         float* scores) {
+  if (!m || n < 0 || (n > 0 && !ids))
+    return model_fail(FRECSYS_ERR_INVALID, std::string(what) + ": bad arguments");
+  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const int rc = dev.TrySimilar(side, rows, n, k, flags, mask, ids, scores);
+  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_similar_items(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* item_mask, int32_t* ids,
+                                float* scores) {
+  return model_similar(m, "frecsys_model_similar_items", FRECSYS_SIDE_ITEM, items, n, k, flags,
+                       item_mask, ids, scores);
+}
+
+int frecsys_model_similar_users(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* user_mask, int32_t* ids,
+                                float* scores) {
+  return model_similar(m, "frecsys_model_similar_users", FRECSYS_SIDE_USER, users, n, k, flags,
+                       user_mask, ids, scores);
+}
+
 int frecsys_model_rank_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                           const int32_t* hist_items, int64_t n,
                                           const int64_t* cand_ptr, const int32_t* cand_items,
