@@ -452,6 +452,113 @@ int frecsys_rank_candidates(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
                             const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                             int32_t flags, const uint8_t* item_mask, int32_t* items,
                             float* scores);
+/* Metrics of candidate lists on the device (second-stage evaluation; no
+ * reference counterpart): frecsys_list_metrics(L, list_k = k, gt, k_list) of
+ * the lists L that frecsys_rank_candidates returns with k = max(k_list) and
+ * the same side, rows, cand_ptr / cand_items, flags and item_mask -- bitwise,
+ * without the lists leaving the device.  Ground-truth row i belongs to query
+ * row i; a ground-truth id that is not in the list, is masked out or is
+ * excluded as history is simply never a hit, and g stays the count of
+ * distinct ground-truth ids.  Per row batch rank_cand_kernel ranks the
+ * uploaded lists and frecsys_rank_metrics' kernel reads the top-K where the
+ * ranking left it; 2 nk floats per row come back (recall, ndcg: host
+ * [n_rows * nk]).  Batches are frecsys_rank_candidates' (4 bytes per id, 4 k +
+ * 8 nk bytes of outputs and the history bits per row within
+ * FRECSYS_RECOMMEND_WS_MB, which changes no result bit); the ground truth,
+ * tables and cut-offs lie outside that budget as for frecsys_rank_metrics.
+ * Rank-local at any world size: no collective.  n_rows == 0 returns
+ * FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID, before any device
+ * call: frecsys_rank_candidates' cases and frecsys_rank_metrics' cases.
+ * Timer keys "rank_candidates" and "rank_metrics", with their work
+ * definitions (the lists written count 4 k bytes per row: no scores). */
+int frecsys_rank_candidates_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
+                                    int64_t n_rows, const int64_t* cand_ptr,
+                                    const int32_t* cand_items, int32_t flags,
+                                    const uint8_t* item_mask, const int64_t* gt_ptr,
+                                    const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                    float* recall, float* ndcg);
+/* The negatives of sampled evaluation, on the host (no context, no HIP call,
+ * like frecsys_list_metrics): what frecsys_sampled_metrics draws on the
+ * device, bit for bit.  For query row i with side row id r = row_ids[i] (i
+ * when row_ids is NULL), history hist_items[hist_ptr[i] .. hist_ptr[i+1])
+ * (per QUERY row; both NULL = no exclusion; ids outside [0, n_items) are
+ * ignored) and ground truth gt_items[gt_ptr[i] .. gt_ptr[i+1]):
+ *   D = the ascending ids whose item_mask byte is non-zero (all of
+ *   0 .. n_items-1 when item_mask is NULL), M = |D|;
+ *   pool = { j in D : j not in the ground truth, j not in the history },
+ *   E = |pool|.
+ * Whole-pool row (2 n_neg > E or 64 E < M): the negatives are all of pool,
+ * neg_count[i] = E, and negatives[i*n_neg ..) is filled with -1 (the ids are
+ * not returned).  This bounds the expected draws of every other row by
+ * 128 n_neg.  Sampled row otherwise: with mix64(x) = splitmix64's finaliser
+ * (x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ * x *= 0x94D049BB133111EB; x ^= x >> 31) and C = 0x9E3779B97F4A7C15, all in
+ * wrapping uint64: key = mix64(seed + C (r + 1)); for t = 0, 1, ...:
+ * u = mix64(key + C (t + 1)), idx = ((u >> 32) M) >> 32, j = D[idx]; draw t
+ * is accepted when j is in pool and differs from every accepted earlier
+ * draw; the negatives are the first n_neg accepted draws in draw order,
+ * neg_count[i] = n_neg.  A row's sample depends on (seed, r, n_neg, mask,
+ * its ground truth, its history) only -- not on the other rows of the call,
+ * the batch, the grid or the world size.  A row stops after 2^20 + 4096 n_neg
+ * draws at the latest (never reached in practice: a draw is accepted with
+ * probability >= 1/128) and the call then fails with FRECSYS_ERR_HIP, the
+ * code of the device call with the same cap.  Rows run on the host thread
+ * pool.  neg_count: [n_rows]; negatives: [n_rows * n_neg] or NULL.
+ * n_rows == 0 returns FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID,
+ * outputs untouched: n_items outside [1, 2^31), n_rows < 0, n_neg < 0,
+ * n_rows * n_neg overflowing int64, a negative row id, null neg_count / gt_ptr
+ * / gt_items, hist_items without hist_ptr (or the reverse with a non-empty
+ * history), a negative or non-monotone hist_ptr, gt_ptr[0] != 0 or a
+ * non-monotone gt_ptr, a row with no ground truth, a ground-truth id outside
+ * [0, n_items). */
+int frecsys_sample_negatives(int64_t n_items, const uint8_t* item_mask, const int64_t* row_ids,
+                             int64_t n_rows, const int64_t* hist_ptr, const int32_t* hist_items,
+                             const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                             uint64_t seed, int32_t* neg_count, int32_t* negatives);
+/* Sampled evaluation on the device: frecsys_rank_candidates_metrics of the
+ * lists cand_i = distinct(gt_i) followed by the negatives
+ * frecsys_sample_negatives defines for (n_items, item_mask, r = rows[i],
+ * history = the CSR history of row r of `side` when flags has
+ * FRECSYS_REC_EXCLUDE_HISTORY, else none) -- for a whole-pool row all of its
+ * pool.  Every ground-truth id is in the list, eligible or not; the ranking
+ * drops the ineligible ones as it always does.  When every row is a
+ * whole-pool row (n_neg >= n_items, say) the result is frecsys_rank_metrics'
+ * bitwise.  Sampled metrics are NOT estimates of the full-catalogue metrics
+ * of frecsys_rank_metrics and must not be read as such: they rank systems
+ * differently (Krichene & Rendle, KDD 2020).
+ *   Per row batch: one bitmap per row (the layout of the other paths,
+ * 16 ceil(n_items / 128) bytes) receives the blocked bits (history and ground
+ * truth), one pass counts E, and 4 bytes per row come back so that the host
+ * lays the lists out; one wave per row then writes its list into the buffer
+ * rank_cand_kernel reads -- a sampled row in blocks of 64 draws (lane l holds
+ * draw t0 + l; a 64-bit ballot orders the accepted lanes; taken ids are
+ * marked in the row's bitmap), a whole-pool row by compacting its eligible
+ * bits -- and the ranking and the metric kernel follow.  Only 2 nk floats per
+ * row come back, plus neg_count [n_rows] and negatives [n_rows * n_neg] (as
+ * frecsys_sample_negatives returns them) where those are not NULL.
+ * Workspace: rows are cut into batches whose bitmaps and outputs (16
+ * ceil(n_items / 128) + 4 k + 8 nk bytes per row) stay within half of
+ * FRECSYS_RECOMMEND_WS_MB (default 256), each batch into sub-batches whose
+ * lists (4 (g_i + neg_count_i) bytes per row, from the counted pools) stay
+ * within the other half, at least one row each; outside that budget lie 20
+ * bytes per row (list offsets, row ids, pool counts), the ground truth and
+ * tables of frecsys_rank_metrics, the mask bits and 4 M bytes of D when a
+ * mask is given.  The knob changes no result bit.  All of it goes with
+ * frecsys_release_workspaces.  Rank-local at any world size: no collective.
+ * n_rows == 0 returns FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID,
+ * before any device call: frecsys_rank_candidates' and frecsys_rank_metrics'
+ * cases, n_neg < 0, n_rows * n_neg overflowing int64.  FRECSYS_ERR_HIP: a row
+ * reached the draw cap of frecsys_sample_negatives (the kernel loop stops
+ * there and raises the context's fail word; it never hangs).  Timer keys
+ * "sample_negatives" (the bitmap, pool and list kernels), "rank_candidates"
+ * and "rank_metrics"; frecsys_work("sample_negatives"): 0 flops, bytes =
+ * 2 x 16 ceil(n_items / 128) per row (its bitmap written, then read by the
+ * pool pass) + 4 per list id written. */
+int frecsys_sampled_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                            int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                            const int32_t* gt_items, int32_t n_neg, uint64_t seed,
+                            const int32_t* k_list, int32_t nk, float* recall, float* ndcg,
+                            int32_t* neg_count, int32_t* negatives);
 /* Nearest neighbours inside one factor table ("items like this item", "users
  * like this user"; no reference counterpart): T, the table of `side` (USER or
  * ITEM), is both the source of the queries and the table searched.  Query row
@@ -536,7 +643,8 @@ int frecsys_synchronize(frecsys_ctx* ctx);
  * slabs, pre-split table, history-space wide bucket); the next solve sizes
  * them again within FRECSYS_WIDE_WS_MB and a quarter of the then free device
  * memory each.  The ranking workspace of frecsys_recommend and its
- * relatives and the inverse norms of frecsys_similar go too; the next such
+ * relatives (the list ids of frecsys_sampled_metrics among them) and the
+ * inverse norms of frecsys_similar go too; the next such
  * call sizes them again. For a caller that needs the device memory between phases
  * (evaluation, another model).  No reference counterpart: the reference's
  * per-thread Eigen temporaries are freed per entity. */

@@ -181,6 +181,55 @@ int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                    const float* alpha_list, int32_t na,
                                    int32_t exclude_seen, float* recall, float* ndcg,
                                    float* summary);
+/* frecsys_model_evaluate restricted to caller-supplied candidate lists
+ * (second-stage evaluation): Recall@K / NDCG@K of the lists
+ * frecsys_model_rank_candidates returns with k = max(k_list), computed on the
+ * device without the lists leaving it (frecsys_rank_candidates_metrics,
+ * frecsys_hip.h).  Candidate list i (cand_items[cand_ptr[i] .. cand_ptr[i+1]))
+ * and ground-truth row i belong to users[i]; a ground-truth item outside the
+ * list, masked or in the excluded history is never a hit.  item_mask: host
+ * [n_items] or NULL.  recall, ndcg and summary have exactly
+ * frecsys_model_evaluate's layout and arithmetic.  Errors are
+ * frecsys_rank_candidates_metrics', reported before any device call.  The
+ * _fold_in form projects the n histories into the EVAL side first, as
+ * frecsys_model_evaluate_fold_in does. */
+int frecsys_model_evaluate_candidates(frecsys_model* m, const int64_t* users, int64_t n,
+                                      const int64_t* cand_ptr, const int32_t* cand_items,
+                                      const int64_t* gt_ptr, const int32_t* gt_items,
+                                      const int32_t* k_list, int32_t nk, const float* alpha_list,
+                                      int32_t na, int32_t exclude_seen, const uint8_t* item_mask,
+                                      float* recall, float* ndcg, float* summary);
+int frecsys_model_evaluate_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                              const int32_t* hist_items, int64_t n,
+                                              const int64_t* cand_ptr, const int32_t* cand_items,
+                                              const int64_t* gt_ptr, const int32_t* gt_items,
+                                              const int32_t* k_list, int32_t nk,
+                                              const float* alpha_list, int32_t na,
+                                              int32_t exclude_seen, const uint8_t* item_mask,
+                                              float* recall, float* ndcg, float* summary);
+/* Sampled evaluation: each user's distinct ground truth ranked against n_neg
+ * negatives drawn on the device by the generator of frecsys_sample_negatives
+ * with this seed (side row id = users[i]; history row i has id i in the
+ * _fold_in form), or against the user's whole pool where that is small
+ * (frecsys_sampled_metrics, frecsys_hip.h).  The price of an evaluation drops
+ * from users x items scores to users x (n_neg + ground truth); the values are
+ * NOT estimates of frecsys_model_evaluate's full-catalogue metrics and the two
+ * are not interchangeable (Krichene & Rendle, KDD 2020).  Outputs, summary
+ * and exclude_seen as in frecsys_model_evaluate; errors are
+ * frecsys_sampled_metrics', reported before any device call. */
+int frecsys_model_evaluate_sampled(frecsys_model* m, const int64_t* users, int64_t n,
+                                   const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                                   uint64_t seed, const int32_t* k_list, int32_t nk,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   const uint8_t* item_mask, float* recall, float* ndcg,
+                                   float* summary);
+int frecsys_model_evaluate_sampled_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                           const int32_t* hist_items, int64_t n,
+                                           const int64_t* gt_ptr, const int32_t* gt_items,
+                                           int32_t n_neg, uint64_t seed, const int32_t* k_list,
+                                           int32_t nk, const float* alpha_list, int32_t na,
+                                           int32_t exclude_seen, const uint8_t* item_mask,
+                                           float* recall, float* ndcg, float* summary);
 void frecsys_model_destroy(frecsys_model* m);
 const char* frecsys_model_last_error(void);
 

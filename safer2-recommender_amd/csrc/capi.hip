@@ -13,6 +13,8 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
+#include <climits>
 #include <cmath>
 #include <functional>
 #include <cstdio>
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "../../include/frecsys_hip.h"
+#include "../include/frecsys/parallel.h"
 #include "device_buf.h"
 #include "kernels.h"
 #include "wide.h"
@@ -141,6 +144,7 @@ struct frecsys_ctx {
   DevBuf<int32_t> d_topk;        // [eval rows][k]
   DevBuf<char> d_rec;            // frecsys_recommend: candidates, counts, bitmaps, outputs
   DevBuf<float> d_sim_inv;       // frecsys_similar: inverse row norms of the side searched
+  DevBuf<int32_t> d_samp_ids;    // frecsys_sampled_metrics: the candidate ids of a row batch
   int64_t rec_splits = 0;       // item splits of the last call (frecsys_counter "recommend_splits")
   // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
   // per row of each side (device scratch + host copy; -1: not solved here),
@@ -2688,6 +2692,518 @@ int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, i
   return FRECSYS_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// splitmix64's finaliser and its increment: the generator of the sampled
+// negatives (include/frecsys_hip.h), uint64 arithmetic that wraps.
+inline uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+
+// What frecsys_rank_candidates_metrics and frecsys_sampled_metrics share.
+struct CandMetricsCall {
+  int32_t side;
+  const int64_t* rows;
+  int64_t n;
+  int32_t flags;
+  const uint8_t* item_mask;
+  MetricsRequest mt;
+  // caller lists (frecsys_rank_candidates_metrics) ...
+  const int64_t* cand_ptr;
+  const int32_t* cand_items;
+  // ... or sampled ones (cand_ptr == nullptr)
+  int32_t n_neg;
+  uint64_t seed;
+  int32_t* neg_count;
+  int32_t* negatives;
+};
+
+// The argument checks of both, before any device call: frecsys_rank_metrics'
+// and frecsys_rank_candidates' cases.  *k = max k_list.
+int cand_metrics_check(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q,
+                       int32_t* k) {
+  if (q.side != FRECSYS_SIDE_USER && q.side != FRECSYS_SIDE_EVAL)
+    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
+  if (q.flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
+    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  if (q.n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (!q.mt.k_list || q.mt.nk < 1 || q.mt.nk > kMetricMaxCutoffs)
+    return fail(c, FRECSYS_ERR_INVALID,
+                w + "k_list must hold 1 to " + std::to_string(kMetricMaxCutoffs) + " cut-offs");
+  *k = 0;
+  for (int32_t j = 0; j < q.mt.nk; ++j) {
+    if (q.mt.k_list[j] < 1 || q.mt.k_list[j] > kMetricMaxK)
+      return fail(c, FRECSYS_ERR_INVALID, w + "cut-offs must be in [1, 1024]");
+    *k = std::max(*k, q.mt.k_list[j]);
+  }
+  if (!q.cand_ptr) {
+    if (q.n_neg < 0) return fail(c, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
+    if (q.n_neg > 0 && q.n > INT64_MAX / q.n_neg)
+      return fail(c, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
+  }
+  if (q.n == 0) return FRECSYS_OK;
+  if (!q.mt.recall || !q.mt.ndcg)
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  if ((q.flags & FRECSYS_REC_EXCLUDE_HISTORY) && !c->rp[q.side])
+    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
+  if (!c->emb[q.side] || !c->emb[1])
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t ns = c->n[q.side], m = c->n[1];
+  if (q.rows) {
+    for (int64_t i = 0; i < q.n; ++i)
+      if (q.rows[i] < 0 || q.rows[i] >= ns)
+        return fail(c, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(q.rows[i]) + " out of range");
+  } else if (q.n > ns) {
+    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
+  }
+  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
+  int32_t mk = 0;
+  const std::string e =
+      metric_args_error(q.n, q.mt.gt_ptr, q.mt.gt_items, q.mt.k_list, q.mt.nk, m, &mk);
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  return FRECSYS_OK;
+}
+
+// Whole-pool rule of a row with pool size E among M maskable ids.
+inline bool whole_pool_row(int64_t n_neg, int64_t E, int64_t M) {
+  return 2 * n_neg > E || 64 * E < M;
+}
+
+// The device part of both: per row batch the candidate ids are uploaded
+// (caller lists) or written by the sampling kernels (sampled lists), then
+// rank_cand_kernel ranks them where they lie, rank_metrics_kernel reads the
+// lists where the ranking left them, and 2 nk floats per row come back.
+int cand_metrics_impl(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q, int32_t k) {
+  const bool sampled = q.cand_ptr == nullptr;
+  const bool exclude = (q.flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  const int64_t n = q.n, m = c->n[1];
+  const size_t nk = (size_t)q.mt.nk;
+  HIP_TRY(c, hipSetDevice(c->device));
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  const size_t budget = (size_t)ws_mb << 20;
+  const int64_t W = recommend_words(m);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const bool bits = sampled || exclude;  // one bitmap per row of a batch
+  // per row of a batch: its outputs, its metric rows, its bitmap -- and its
+  // candidate ids.  Caller lists: batches are cut greedily in row order over
+  // all of it (frecsys_rank_candidates' scheme).  Sampled lists: the lengths
+  // are known only after the pool pass, so rows are cut into batches by the
+  // fixed part within half the budget, and each batch into sub-batches whose
+  // ids stay within the other half (at least one row each).
+  const size_t row_fixed = (size_t)k * 4 + nk * 8 + (bits ? (size_t)W * 4 : 0);
+  std::vector<int64_t> cuts{0};
+  int64_t max_rows = 0, max_ids = 0;
+  if (sampled) {
+    const int64_t nb =
+        std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)((budget / 2) / row_fixed)));
+    for (int64_t r0 = 0; r0 < n; r0 += nb) cuts.push_back(std::min(n, r0 + nb));
+    max_rows = nb;
+  } else {
+    for (int64_t r0 = 0; r0 < n;) {
+      size_t bytes = 0;
+      int64_t r1 = r0;
+      while (r1 < n) {
+        const size_t add = row_fixed + (size_t)(q.cand_ptr[r1 + 1] - q.cand_ptr[r1]) * 4;
+        if (r1 > r0 && bytes + add > budget) break;
+        bytes += add;
+        ++r1;
+      }
+      max_rows = std::max(max_rows, r1 - r0);
+      max_ids = std::max(max_ids, q.cand_ptr[r1] - q.cand_ptr[r0]);
+      cuts.push_back(r1);
+      r0 = r1;
+    }
+  }
+  // eligibility bits of the items, and the ascending list of the eligible ids
+  // when a mask leaves some out (the domain D of the draws)
+  std::vector<uint32_t> maskw((size_t)W, 0u);
+  std::vector<int32_t> dlist;
+  int64_t M = m;
+  for (int64_t j = 0; j < m; ++j)
+    if (!q.item_mask || q.item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
+  if (sampled && q.item_mask) {
+    for (int64_t j = 0; j < m; ++j)
+      if (q.item_mask[j]) dlist.push_back((int32_t)j);
+    M = (int64_t)dlist.size();
+    if (M == m) dlist.clear();
+  }
+  std::vector<int64_t> gt_sp;
+  std::vector<int32_t> gt_sg;
+  sorted_ground_truth(n, q.mt.gt_ptr, q.mt.gt_items, &gt_sp, &gt_sg);
+  const size_t o_ids = 0;
+  const size_t o_bitmap = up16(o_ids + (size_t)max_ids * 4);
+  const size_t o_items = up16(o_bitmap + (bits ? (size_t)max_rows * W * 4 : 0));
+  const size_t o_recall = up16(o_items + (size_t)max_rows * k * 4);
+  const size_t o_ndcg = up16(o_recall + (size_t)max_rows * nk * 4);
+  // outside the per-row budget: per call
+  const size_t o_mask = up16(o_ndcg + (size_t)max_rows * nk * 4);
+  const size_t o_ptr = up16(o_mask + (size_t)W * 4);
+  const size_t o_qrows = up16(o_ptr + ((size_t)n + 1) * 8);
+  const size_t o_gtptr = up16(o_qrows + (q.rows ? (size_t)n * 8 : 0));
+  const size_t o_gt = up16(o_gtptr + ((size_t)n + 1) * 8);
+  const size_t o_gain = up16(o_gt + gt_sg.size() * 4);
+  const size_t o_idcg = up16(o_gain + sizeof(double) * kMetricMaxK);
+  const size_t o_klist = up16(o_idcg + sizeof(double) * (kMetricMaxK + 1));
+  const size_t o_pool = up16(o_klist + nk * 4);
+  const size_t o_dlist = up16(o_pool + (sampled ? (size_t)n * 4 : 0));
+  const size_t total = o_dlist + dlist.size() * 4;
+  int rc = ensure(c, c->d_rec, total);
+  if (rc) return rc;
+  const MetricTables& tab = metric_tables();
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
+                            hipMemcpyHostToDevice, c->stream));
+  if (q.rows)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, q.rows, sizeof(int64_t) * n,
+                              hipMemcpyHostToDevice, c->stream));
+  if (!sampled)
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr, q.cand_ptr, sizeof(int64_t) * ((size_t)n + 1),
+                              hipMemcpyHostToDevice, c->stream));
+  if (!dlist.empty())
+    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_dlist, dlist.data(), sizeof(int32_t) * dlist.size(),
+                              hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gtptr, gt_sp.data(), sizeof(int64_t) * ((size_t)n + 1),
+                            hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gt, gt_sg.data(), sizeof(int32_t) * gt_sg.size(),
+                            hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gain, tab.gain, sizeof(tab.gain), hipMemcpyHostToDevice,
+                            c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_idcg, tab.idcg, sizeof(tab.idcg), hipMemcpyHostToDevice,
+                            c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_klist, q.mt.k_list, sizeof(int32_t) * nk,
+                            hipMemcpyHostToDevice, c->stream));
+  if (sampled)
+    HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  RankCandArgs a{};
+  a.X = c->emb[q.side];
+  a.qrows = q.rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
+  a.Y = c->emb[1];
+  a.m = m;
+  a.Dp = c->Dp;
+  a.k = k;
+  a.cand_ptr = (const int64_t*)(c->d_rec + o_ptr);
+  a.cand = (const int32_t*)(c->d_rec + o_ids);
+  a.row_ptr = exclude ? c->rp[q.side] : nullptr;
+  a.col = exclude ? c->col[q.side] : nullptr;
+  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
+  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
+  a.out_items = (int32_t*)(c->d_rec + o_items);
+  a.out_scores = nullptr;
+  RankMetricsArgs ma{};
+  ma.lists = a.out_items;
+  ma.k = k;
+  ma.gt_ptr = (const int64_t*)(c->d_rec + o_gtptr);
+  ma.gt = (const int32_t*)(c->d_rec + o_gt);
+  ma.k_list = (const int32_t*)(c->d_rec + o_klist);
+  ma.nk = (int)nk;
+  ma.gain = (const double*)(c->d_rec + o_gain);
+  ma.idcg = (const double*)(c->d_rec + o_idcg);
+  ma.recall = (float*)(c->d_rec + o_recall);
+  ma.ndcg = (float*)(c->d_rec + o_ndcg);
+  // ranks and scores rows [s0, s1) of the call from the ids at a.cand
+  auto rank_rows = [&](int64_t s0, int64_t s1, int64_t cand_base) -> int {
+    a.r0 = s0;
+    a.n = s1 - s0;
+    a.cand_base = cand_base;
+    {
+      ScopedTimer t(c, "rank_candidates");
+      HIP_TRY(c, launch_rank_candidates(a, c->stream));
+      t.stop();
+    }
+    ma.r0 = s0;
+    ma.n = a.n;
+    {
+      ScopedTimer t(c, "rank_metrics");
+      HIP_TRY(c, launch_rank_metrics(ma, c->stream));
+      t.stop();
+    }
+    HIP_TRY(c, hipMemcpyAsync(q.mt.recall + s0 * nk, ma.recall, sizeof(float) * a.n * nk,
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(q.mt.ndcg + s0 * nk, ma.ndcg, sizeof(float) * a.n * nk,
+                              hipMemcpyDeviceToHost, c->stream));
+    return FRECSYS_OK;
+  };
+  double pairs = 0.0;
+  if (!sampled) {
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+      const int64_t s0 = cuts[b], s1 = cuts[b + 1];
+      const int64_t base = q.cand_ptr[s0], ids = q.cand_ptr[s1] - base;
+      if (ids > 0)
+        HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ids, q.cand_items + base, sizeof(int32_t) * ids,
+                                  hipMemcpyHostToDevice, c->stream));
+      if ((rc = rank_rows(s0, s1, base))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    pairs = (double)q.cand_ptr[n];
+  } else {
+    SampledArgs sa{};
+    sa.qrows = a.qrows;
+    sa.m = m;
+    sa.W = W;
+    sa.row_ptr = a.row_ptr;
+    sa.col = a.col;
+    sa.maskw = a.maskw;
+    sa.dlist = dlist.empty() ? nullptr : (const int32_t*)(c->d_rec + o_dlist);
+    sa.M = M;
+    sa.gt_ptr = ma.gt_ptr;
+    sa.gt = ma.gt;
+    sa.n_neg = q.n_neg;
+    sa.seed = q.seed;
+    sa.pool = (int32_t*)(c->d_rec + o_pool);
+    sa.cand_ptr = a.cand_ptr;
+    sa.fail = c->d_fail;
+    uint32_t* const bitmap = (uint32_t*)(c->d_rec + o_bitmap);
+    std::vector<int32_t> pool((size_t)max_rows), ids_host;
+    std::vector<int64_t> ptr((size_t)max_rows + 1);
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
+      const int64_t b0 = cuts[b], b1 = cuts[b + 1], nb = b1 - b0;
+      sa.r0 = b0;
+      sa.n = nb;
+      sa.bitmap = bitmap;
+      {
+        ScopedTimer t(c, "sample_negatives");
+        HIP_TRY(c, launch_sampled_pool(sa, c->stream));
+        t.stop();
+      }
+      HIP_TRY(c, hipMemcpyAsync(pool.data(), sa.pool + b0, sizeof(int32_t) * nb,
+                                hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      // list i of the batch lies at ptr[i - b0] (ptr[0] = 0), on the device
+      // at entry i of the call's pointer array
+      ptr[0] = 0;
+      for (int64_t i = 0; i < nb; ++i) {
+        const int64_t E = pool[(size_t)i];
+        const int64_t cnt = whole_pool_row(q.n_neg, E, M) ? E : q.n_neg;
+        if (q.neg_count) q.neg_count[b0 + i] = (int32_t)cnt;
+        ptr[(size_t)i + 1] =
+            ptr[(size_t)i] + (gt_sp[(size_t)(b0 + i) + 1] - gt_sp[(size_t)(b0 + i)]) + cnt;
+      }
+      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr + (size_t)b0 * 8, ptr.data(),
+                                sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice,
+                                c->stream));
+      pairs += (double)ptr[(size_t)nb];
+      for (int64_t s0 = b0; s0 < b1;) {
+        int64_t s1 = s0 + 1;
+        const int64_t base = ptr[(size_t)(s0 - b0)];
+        while (s1 < b1 && (size_t)(ptr[(size_t)(s1 + 1 - b0)] - base) * 4 <= budget / 2) ++s1;
+        const int64_t ids = ptr[(size_t)(s1 - b0)] - base;
+        if ((rc = ensure(c, c->d_samp_ids, (size_t)std::max<int64_t>(ids, 1)))) return rc;
+        sa.r0 = s0;
+        sa.n = s1 - s0;
+        sa.bitmap = bitmap + (size_t)(s0 - b0) * W;
+        sa.cand_base = base;
+        sa.cand = c->d_samp_ids;
+        {
+          ScopedTimer t(c, "sample_negatives");
+          HIP_TRY(c, launch_sampled_fill(sa, c->stream));
+          t.stop();
+        }
+        if (q.negatives && q.n_neg > 0) {
+          ids_host.resize((size_t)ids);
+          HIP_TRY(c, hipMemcpyAsync(ids_host.data(), sa.cand, sizeof(int32_t) * ids,
+                                    hipMemcpyDeviceToHost, c->stream));
+        }
+        a.cand = sa.cand;
+        a.bitmap = exclude ? sa.bitmap : nullptr;  // refilled with the history alone
+        if ((rc = rank_rows(s0, s1, base))) return rc;
+        unsigned long long f = ~0ull;
+        HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (f != ~0ull)
+          return fail(c, FRECSYS_ERR_HIP,
+                      w + "the draws of query row " + std::to_string((int64_t)f - 1) +
+                          " reached the cap");
+        if (q.negatives && q.n_neg > 0)
+          for (int64_t i = s0; i < s1; ++i) {
+            int32_t* out = q.negatives + i * q.n_neg;
+            const int64_t g = gt_sp[(size_t)i + 1] - gt_sp[(size_t)i];
+            if (whole_pool_row(q.n_neg, pool[(size_t)(i - b0)], M))
+              std::fill(out, out + q.n_neg, -1);
+            else
+              std::memcpy(out, ids_host.data() + (ptr[(size_t)(i - b0)] - base) + g,
+                          sizeof(int32_t) * (size_t)q.n_neg);
+          }
+        s0 = s1;
+      }
+    }
+    // bytes: every row's bitmap zeroed, then read by the pool pass; the ids
+    // of the lists written
+    add_work(c, "sample_negatives", 0.0, (double)n * (double)W * 8.0 + pairs * 4.0, n);
+  }
+  // as frecsys_rank_candidates (the lists: ids only) and frecsys_rank_metrics
+  add_work(c, "rank_candidates", 2.0 * pairs * c->dim,
+           pairs * c->Dp * 4.0 + pairs * 4.0 + (double)n * k * 4.0, n);
+  add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
+           (double)n * k * 4.0 + (double)gt_sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
+               (double)n * (double)nk * 8.0,
+           n);
+  return FRECSYS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frecsys_sample_negatives(int64_t n_items, const uint8_t* item_mask, const int64_t* row_ids,
+                             int64_t n_rows, const int64_t* hist_ptr, const int32_t* hist_items,
+                             const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                             uint64_t seed, int32_t* neg_count, int32_t* negatives) {
+  const std::string w = "sample_negatives: ";
+  if (n_items < 1 || n_items > INT32_MAX)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be in [1, 2^31)");
+  if (n_rows < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n_neg < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
+  if (n_neg > 0 && n_rows > INT64_MAX / n_neg)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
+  if (n_rows == 0) return FRECSYS_OK;
+  if (!neg_count) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null neg_count");
+  const int64_t n = n_rows, m = n_items;
+  if (row_ids)
+    for (int64_t i = 0; i < n; ++i)
+      if (row_ids[i] < 0)
+        return fail(nullptr, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(row_ids[i]) + " out of range");
+  if (!hist_ptr && hist_items)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "hist_items without hist_ptr");
+  if (hist_ptr) {
+    if (hist_ptr[0] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative hist_ptr");
+    for (int64_t i = 0; i < n; ++i)
+      if (hist_ptr[i + 1] < hist_ptr[i])
+        return fail(nullptr, FRECSYS_ERR_INVALID,
+                    w + "hist_ptr not monotone at row " + std::to_string(i));
+    if (hist_ptr[n] > hist_ptr[0] && !hist_items)
+      return fail(nullptr, FRECSYS_ERR_INVALID, w + "null hist_items");
+  }
+  {
+    const int32_t one = 1;
+    int32_t mk = 0;
+    const std::string e = metric_args_error(n, gt_ptr, gt_items, &one, 1, m, &mk);
+    if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  }
+  std::vector<int32_t> dlist;
+  int64_t M = m;
+  if (item_mask) {
+    for (int64_t j = 0; j < m; ++j)
+      if (item_mask[j]) dlist.push_back((int32_t)j);
+    M = (int64_t)dlist.size();
+  }
+  const uint64_t cap = kSampleCapBase + kSampleCapPerNeg * (uint64_t)n_neg;
+  std::atomic<int64_t> capped{-1};
+  // rows on the host thread pool; a task keeps one bitmap of the items and
+  // clears the bits of a row after it (blocked = history and ground truth,
+  // then the taken ids)
+  frecsys::ThreadPool::Get().ParallelFor(n, 64, [&](int64_t lo, int64_t hi) {
+    std::vector<uint64_t> bm((size_t)((m + 63) / 64), 0ull);
+    std::vector<int32_t> set;  // ids whose bit this row set
+    auto mark = [&](int64_t j) {
+      uint64_t& wd = bm[(size_t)(j >> 6)];
+      const uint64_t b = 1ull << (j & 63);
+      if (wd & b) return false;
+      wd |= b;
+      set.push_back((int32_t)j);
+      return true;
+    };
+    for (int64_t i = lo; i < hi; ++i) {
+      set.clear();
+      int64_t blocked = 0;  // distinct blocked ids that lie in D
+      if (hist_ptr)
+        for (int64_t p = hist_ptr[i]; p < hist_ptr[i + 1]; ++p) {
+          const int64_t j = hist_items[p];
+          if (j >= 0 && j < m && mark(j) && (!item_mask || item_mask[j])) ++blocked;
+        }
+      for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p) {
+        const int64_t j = gt_items[p];
+        if (mark(j) && (!item_mask || item_mask[j])) ++blocked;
+      }
+      const int64_t E = M - blocked;
+      int32_t* out = negatives ? negatives + i * n_neg : nullptr;
+      if (whole_pool_row(n_neg, E, M)) {
+        neg_count[i] = (int32_t)E;
+        if (out) std::fill(out, out + n_neg, -1);
+      } else {
+        neg_count[i] = n_neg;
+        const uint64_t r = (uint64_t)(row_ids ? row_ids[i] : i);
+        const uint64_t key = mix64(seed + kGolden * (r + 1));
+        int32_t have = 0;
+        for (uint64_t t = 0; have < n_neg; ++t) {
+          if (t >= cap) {
+            int64_t none = -1;
+            capped.compare_exchange_strong(none, i);
+            break;
+          }
+          const uint64_t x = mix64(key + kGolden * (t + 1));
+          const uint64_t idx = ((x >> 32) * (uint64_t)M) >> 32;
+          const int64_t j = item_mask ? dlist[(size_t)idx] : (int64_t)idx;
+          if (!mark(j)) continue;
+          if (out) out[have] = (int32_t)j;
+          ++have;
+        }
+      }
+      for (const int32_t j : set) bm[(size_t)(j >> 6)] &= ~(1ull << (j & 63));
+    }
+  });
+  if (capped.load() >= 0)
+    return fail(nullptr, FRECSYS_ERR_HIP,
+                w + "the draws of query row " + std::to_string(capped.load()) +
+                    " reached the cap");
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_candidates_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows,
+                                    int64_t n_rows, const int64_t* cand_ptr,
+                                    const int32_t* cand_items, int32_t flags,
+                                    const uint8_t* item_mask, const int64_t* gt_ptr,
+                                    const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                    float* recall, float* ndcg) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates_metrics: null context");
+  const std::string w = "rank_candidates_metrics: ";
+  if (!cand_ptr && n_rows != 0) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_ptr");
+  static const int64_t kNoLists[1] = {0};
+  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
+                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
+                          cand_ptr ? cand_ptr : kNoLists, cand_items, 0, 0, nullptr, nullptr};
+  int32_t k = 0;
+  int rc = cand_metrics_check(c, w, q, &k);
+  if (rc || n_rows == 0) return rc;
+  const int64_t n = n_rows, m = c->n[1];
+  if (cand_ptr[0] != 0) return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr[0] must be 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (cand_ptr[i + 1] < cand_ptr[i])
+      return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr not monotone at row " + std::to_string(i));
+  if (cand_ptr[n] > 0 && !cand_items) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_items");
+  for (int64_t p = 0; p < cand_ptr[n]; ++p)
+    if (cand_items[p] < 0 || cand_items[p] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
+  return cand_metrics_impl(c, w, q, k);
+}
+
+int frecsys_sampled_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                            int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                            const int32_t* gt_items, int32_t n_neg, uint64_t seed,
+                            const int32_t* k_list, int32_t nk, float* recall, float* ndcg,
+                            int32_t* neg_count, int32_t* negatives) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "sampled_metrics: null context");
+  const std::string w = "sampled_metrics: ";
+  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
+                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
+                          nullptr, nullptr, n_neg, seed, neg_count, negatives};
+  int32_t k = 0;
+  const int rc = cand_metrics_check(c, w, q, &k);
+  if (rc || n_rows == 0) return rc;
+  return cand_metrics_impl(c, w, q, k);
+}
+
 int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
                     int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "similar: null context");
@@ -3161,6 +3677,7 @@ int frecsys_release_workspaces(frecsys_ctx* c) {
   HIP_TRY(c, c->dw_z.release());
   HIP_TRY(c, c->d_rec.release());
   HIP_TRY(c, c->d_sim_inv.release());
+  HIP_TRY(c, c->d_samp_ids.release());
   return FRECSYS_OK;
 }
 

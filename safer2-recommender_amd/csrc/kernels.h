@@ -434,6 +434,44 @@ struct RankMetricsArgs {
 };
 hipError_t launch_rank_metrics(const RankMetricsArgs& a, hipStream_t s);
 
+// Candidate lists of sampled evaluation (sampled.hip): the list of query row
+// i of the batch -- cand[cand_ptr[r0 + i] - cand_base ..), RankCandArgs'
+// layout -- is the row's ground truth gt[gt_ptr[r0 + i] .. gt_ptr[r0 + i + 1])
+// (ascending, distinct) followed by its negatives: the whole pool (every id
+// with its maskw bit set that is neither in the ground truth nor, with
+// row_ptr / col given, in the row's history; ascending) when 2 n_neg > E or
+// 64 E < M, else the first n_neg accepted draws of the generator of
+// frecsys_sample_negatives, in draw order.  launch_sampled_pool zeroes the
+// batch's bitmaps, sets the blocked bits and writes E = pool[r0 + i];
+// launch_sampled_fill writes the lists (their lengths, g + E or g + n_neg, are
+// the caller's, from pool[]) and leaves the taken bits set in the bitmaps.
+// *fail (~0ull = none) is lowered to r0 + i + 1 for a row that reached the
+// draw cap or whose list length does not fit its pool.
+constexpr unsigned long long kSampleCapBase = 1ull << 20;  // draws of a sampled row:
+constexpr unsigned long long kSampleCapPerNeg = 4096;      // < base + per_neg * n_neg
+struct SampledArgs {
+  const int64_t* qrows;      // table row of every query row of the call, or nullptr
+  int64_t r0, n;             // this batch: query rows r0 .. r0 + n - 1
+  int64_t m, W;              // items, recommend_words(m)
+  const int64_t* row_ptr;    // CSR of the query table's side, or nullptr (no exclusion)
+  const int32_t* col;
+  const uint32_t* maskw;     // [W] eligibility bits of the items
+  const int32_t* dlist;      // [M] ascending ids with their bit set, or nullptr (M == m)
+  int64_t M;
+  const int64_t* gt_ptr;     // [rows of the call + 1]
+  const int32_t* gt;
+  int32_t n_neg;
+  unsigned long long seed;
+  uint32_t* bitmap;          // [n][W] (workspace)
+  int32_t* pool;             // [rows of the call]
+  const int64_t* cand_ptr;   // [rows of the call + 1] (fill only)
+  int64_t cand_base;
+  int32_t* cand;
+  unsigned long long* fail;
+};
+hipError_t launch_sampled_pool(const SampledArgs& a, hipStream_t s);
+hipError_t launch_sampled_fill(const SampledArgs& a, hipStream_t s);
+
 // Wide dims, Dp = 512 / 1024 (wide.hip).  d-space solve with A in an HBM
 // workspace ([batch][wide_slot_floats(Dp)]), entities a.order[0..n_rows)
 // in batches; Gramian by 128x128 block pairs; per-step tridiagonalisation

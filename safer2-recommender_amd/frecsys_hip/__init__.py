@@ -49,7 +49,8 @@ EXPORTS = (
     "frecsys_set_transport", "frecsys_recommend", "frecsys_solve_side_cg",
     "frecsys_cg_iterations", "frecsys_list_metrics", "frecsys_metric_cvar",
     "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
-    "frecsys_similar",
+    "frecsys_similar", "frecsys_sample_negatives", "frecsys_rank_candidates_metrics",
+    "frecsys_sampled_metrics",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -62,6 +63,8 @@ MODEL_EXPORTS = (
     "frecsys_model_score", "frecsys_model_rank_candidates",
     "frecsys_model_rank_candidates_fold_in",
     "frecsys_model_similar_items", "frecsys_model_similar_users",
+    "frecsys_model_evaluate_candidates", "frecsys_model_evaluate_candidates_fold_in",
+    "frecsys_model_evaluate_sampled", "frecsys_model_evaluate_sampled_fold_in",
 )
 
 
@@ -187,6 +190,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_score_pairs": (ctypes.c_int, [P, I32, P, P, I64, P]),
         "frecsys_rank_candidates": (ctypes.c_int, [P, I32, P, I64, P, P, I32, I32, P, P, P]),
         "frecsys_similar": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
+        "frecsys_sample_negatives": (ctypes.c_int,
+                                     [I64, P, P, I64, P, P, P, P, I32, ctypes.c_uint64, P, P]),
+        "frecsys_rank_candidates_metrics": (ctypes.c_int,
+                                            [P, I32, P, I64, P, P, I32, P, P, P, P, I32, P, P]),
+        "frecsys_sampled_metrics": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, I32,
+                                                   ctypes.c_uint64, P, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -228,6 +237,16 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_similar_users": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
         "frecsys_model_rank_candidates_fold_in": (ctypes.c_int,
                                                   [P, P, P, I64, P, P, I32, I32, P, P, P]),
+        "frecsys_model_evaluate_candidates": (
+            ctypes.c_int, [P, P, I64, P, P, P, P, P, I32, P, I32, I32, P, P, P, P]),
+        "frecsys_model_evaluate_candidates_fold_in": (
+            ctypes.c_int, [P, P, P, I64, P, P, P, P, P, I32, P, I32, I32, P, P, P, P]),
+        "frecsys_model_evaluate_sampled": (
+            ctypes.c_int,
+            [P, P, I64, P, P, I32, ctypes.c_uint64, P, I32, P, I32, I32, P, P, P, P]),
+        "frecsys_model_evaluate_sampled_fold_in": (
+            ctypes.c_int,
+            [P, P, P, I64, P, P, I32, ctypes.c_uint64, P, I32, P, I32, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -299,6 +318,40 @@ def list_metrics(lists, gt_ptr, gt_items, k_list) -> Tuple[np.ndarray, np.ndarra
     if rc:
         raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
     return rec, ndcg
+
+
+def sample_negatives(n_items: int, gt_ptr, gt_items, n_neg: int, seed: int = 0, rows=None,
+                     hist_ptr=None, hist_items=None,
+                     item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(neg_count int32 [n], negatives int32 [n, n_neg]): the negatives of
+    sampled evaluation on the host (frecsys_sample_negatives; no GPU needed),
+    bit for bit what Context.sampled_metrics draws on the device.  Query row i
+    has side row id rows[i] (i when rows is None), the ground truth row i of
+    gt_ptr / gt_items and, if given, the history row i of hist_ptr /
+    hist_items (ids it must not draw).  A whole-pool row (more than half of
+    its pool asked for, or a pool below 1/64 of the maskable items) takes its
+    whole pool: neg_count = the pool size and its negatives row holds -1."""
+    lib = load_library()
+    gp, gi = _ground_truth(gt_ptr, gt_items)
+    n = len(gp) - 1
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    assert r is None or len(r) == n, (len(r), n)
+    hp = None if hist_ptr is None else np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+    hi = None if hist_items is None else np.ascontiguousarray(hist_items,
+                                                             dtype=np.int32).reshape(-1)
+    assert hp is None or len(hp) == n + 1, (len(hp), n)
+    mk = None
+    if item_mask is not None:
+        mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+        assert mk.shape == (n_items,), mk.shape
+    cnt = np.zeros(n, dtype=np.int32)
+    neg = np.full((n, max(n_neg, 0)), -1, dtype=np.int32)
+    rc = lib.frecsys_sample_negatives(n_items, _ptr(mk), _ptr(r), n, _ptr(hp), _ptr(hi), _ptr(gp),
+                                      _ptr(gi), n_neg, seed & 0xFFFFFFFFFFFFFFFF, _ptr(cnt),
+                                      _ptr(neg))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    return cnt, neg
 
 
 def metric_cvar(values, alphas) -> np.ndarray:
@@ -632,6 +685,69 @@ class Context:
             self.h, side, _ptr(r), n, _ptr(cp), _ptr(ci), k,
             REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def rank_candidates_metrics(self, side: int, k_list, cand_ptr, cand_items, gt_ptr, gt_items,
+                                rows=None, exclude_history: bool = True,
+                                item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(recall, ndcg) float32 [n, len(k_list)]: list_metrics of
+        rank_candidates(side, max(k_list), cand_ptr, cand_items, ...)'s lists,
+        bitwise, without the lists leaving the GPU
+        (frecsys_rank_candidates_metrics).  Candidate list i and ground-truth
+        row i belong to query row i; a ground-truth id outside the list, masked
+        or in the excluded history is never a hit."""
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        n = len(cp) - 1
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        assert r is None or len(r) == n, (len(r), n)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        rec = np.zeros((n, len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        self._check(self.lib.frecsys_rank_candidates_metrics(
+            self.h, side, _ptr(r), n, _ptr(cp), _ptr(ci),
+            REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk), _ptr(gp), _ptr(gi), _ptr(ks),
+            len(ks), _ptr(rec), _ptr(ndcg)))
+        return rec, ndcg
+
+    def sampled_metrics(self, side: int, k_list, gt_ptr, gt_items, n_neg: int, seed: int = 0,
+                        rows=None, exclude_history: bool = True, item_mask=None,
+                        return_negatives: bool = False):
+        """(recall, ndcg) float32 [n, len(k_list)] of sampled evaluation
+        (frecsys_sampled_metrics): each query row ranks its distinct ground
+        truth against n_neg negatives drawn on the GPU from the eligible items
+        outside its ground truth (and, with exclude_history, its history) by
+        the generator of sample_negatives -- or against its whole pool where
+        that is small.  With return_negatives also (neg_count int32 [n],
+        negatives int32 [n, n_neg]) as sample_negatives returns them.  Sampled
+        metrics are not estimates of rank_metrics' full-catalogue values."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        rec = np.zeros((n, len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        cnt = neg = None
+        if return_negatives:
+            cnt = np.zeros(n, dtype=np.int32)
+            neg = np.full((n, max(n_neg, 0)), -1, dtype=np.int32)
+        self._check(self.lib.frecsys_sampled_metrics(
+            self.h, side, _ptr(r), n, REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk),
+            _ptr(gp), _ptr(gi), n_neg, seed & 0xFFFFFFFFFFFFFFFF, _ptr(ks), len(ks), _ptr(rec),
+            _ptr(ndcg), _ptr(cnt), _ptr(neg)))
+        if return_negatives:
+            return rec, ndcg, cnt, neg
+        return rec, ndcg
 
     def similar(self, side: int, k: int, rows=None, cosine: bool = True, keep_self: bool = False,
                 mask=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -1000,6 +1116,91 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return self._evaluation(n, ks, al, rec, ndcg, summary)
+
+    def _eval_lists(self, fn, head, n, cand, gt_ptr, gt_items, sample, k_list, alpha_list,
+                    exclude_seen, item_mask):
+        """The four list evaluations: `head` are the leading arguments (users
+        or the history CSR), `cand` the candidate CSR or None, `sample`
+        (n_neg, seed) or None."""
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
+        mk = self._mask(item_mask)
+        rec = np.zeros((n, len(ks)), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
+        args = [self.h] + [_ptr(x) for x in head] + [n]
+        if cand is not None:
+            args += [_ptr(cand[0]), _ptr(cand[1])]
+        args += [_ptr(gp), _ptr(gi)]
+        if sample is not None:
+            args += [sample[0], sample[1] & 0xFFFFFFFFFFFFFFFF]
+        args += [_ptr(ks), len(ks), _ptr(al), len(al), int(bool(exclude_seen)), _ptr(mk),
+                 _ptr(rec), _ptr(ndcg), _ptr(summary)]
+        rc = fn(*args)
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return self._evaluation(n, ks, al, rec, ndcg, summary)
+
+    def evaluate_candidates(self, users, cand_ptr, cand_items, gt_ptr, gt_items,
+                            k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
+                            exclude_seen: bool = True, item_mask=None):
+        """evaluate()'s dict for trained users whose rankings are restricted
+        to caller-supplied candidate lists (CSR cand_ptr / cand_items; list i
+        and ground-truth row i belong to users[i]) --
+        frecsys_model_evaluate_candidates: the metrics of rank_candidates'
+        lists, computed on the GPU."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        assert len(cp) == len(u) + 1, (len(cp), len(u))
+        return self._eval_lists(self.lib.frecsys_model_evaluate_candidates, [u], len(u), (cp, ci),
+                                gt_ptr, gt_items, None, k_list, alpha_list, exclude_seen,
+                                item_mask)
+
+    def evaluate_candidates_fold_in(self, hist_ptr, hist_items, cand_ptr, cand_items, gt_ptr,
+                                    gt_items, k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
+                                    exclude_seen: bool = True, item_mask=None):
+        """The same for unseen users given by their histories: the fold-in
+        projection, then the metrics of candidate list i for history row i
+        (frecsys_model_evaluate_candidates_fold_in).  The projected rows stay
+        in the EVAL side."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        assert len(cp) == n + 1, (len(cp), n)
+        return self._eval_lists(self.lib.frecsys_model_evaluate_candidates_fold_in, [hp, hi], n,
+                                (cp, ci), gt_ptr, gt_items, None, k_list, alpha_list,
+                                exclude_seen, item_mask)
+
+    def evaluate_sampled(self, users, gt_ptr, gt_items, n_neg: int, seed: int = 0,
+                         k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
+                         exclude_seen: bool = True, item_mask=None):
+        """evaluate()'s dict of sampled evaluation for trained users
+        (frecsys_model_evaluate_sampled): each user's ground truth ranked
+        against n_neg negatives drawn on the GPU (Context.sampled_metrics,
+        sample_negatives).  Affordable per epoch where evaluate() is not --
+        and not an estimate of evaluate()'s full-catalogue values."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        return self._eval_lists(self.lib.frecsys_model_evaluate_sampled, [u], len(u), None, gt_ptr,
+                                gt_items, (n_neg, seed), k_list, alpha_list, exclude_seen,
+                                item_mask)
+
+    def evaluate_sampled_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items, n_neg: int,
+                                 seed: int = 0, k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
+                                 exclude_seen: bool = True, item_mask=None):
+        """The same for unseen users given by their histories
+        (frecsys_model_evaluate_sampled_fold_in); history row i has side row
+        id i in the generator.  The projected rows stay in the EVAL side."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        return self._eval_lists(self.lib.frecsys_model_evaluate_sampled_fold_in, [hp, hi], n, None,
+                                gt_ptr, gt_items, (n_neg, seed), k_list, alpha_list, exclude_seen,
+                                item_mask)
 
     def close(self):
         if getattr(self, "h", None):

@@ -254,6 +254,22 @@ class DeviceContext {
     return frecsys_rank_metrics(ctx_, side, rows, n, flags, mask, gt_ptr, gt_items, k_list, nk,
                                 recall, ndcg);
   }
+  // The same metrics of caller-supplied candidate lists
+  // (frecsys_rank_candidates_metrics) and of sampled lists whose negatives are
+  // drawn on the device (frecsys_sampled_metrics): the status code.
+  int TryRankCandidatesMetrics(int side, const int64_t* rows, int64_t n, const int64_t* cand_ptr,
+                               const int32_t* cand_items, int flags, const uint8_t* mask,
+                               const int64_t* gt_ptr, const int32_t* gt_items,
+                               const int32_t* k_list, int nk, float* recall, float* ndcg) {
+    return frecsys_rank_candidates_metrics(ctx_, side, rows, n, cand_ptr, cand_items, flags, mask,
+                                           gt_ptr, gt_items, k_list, nk, recall, ndcg);
+  }
+  int TrySampledMetrics(int side, const int64_t* rows, int64_t n, int flags, const uint8_t* mask,
+                        const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                        uint64_t seed, const int32_t* k_list, int nk, float* recall, float* ndcg) {
+    return frecsys_sampled_metrics(ctx_, side, rows, n, flags, mask, gt_ptr, gt_items, n_neg, seed,
+                                   k_list, nk, recall, ndcg, nullptr, nullptr);
+  }
   struct Metrics {
     MatrixXf recall, ndcg;  // rows x |k_list|
   };

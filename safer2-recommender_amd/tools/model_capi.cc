@@ -4,6 +4,7 @@
 // (frecsys/factory.h); every compute call lands in libfrecsys_hip.so.
 #include <array>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -336,6 +337,9 @@ std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_pt
 // Metrics of `n` query rows of `side` into recall / ndcg, then the summary
 // [(2 + 2 na) nk]: mean recall, mean ndcg, recall CVaR [na][nk], ndcg CVaR
 // [na][nk] -- EvaluationResult's own colwise().mean() and cvar().
+int summarize(int64_t n, const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
+              const float* recall, const float* ndcg, float* summary);
+
 int evaluate_rows(frecsys::DeviceContext& dev, int side, const int64_t* rows, int64_t n,
                   int32_t exclude_seen, const int64_t* gt_ptr, const int32_t* gt_items,
                   const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
@@ -343,6 +347,12 @@ int evaluate_rows(frecsys::DeviceContext& dev, int side, const int64_t* rows, in
   const int rc = dev.TryRankMetrics(side, rows, n, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
                                     nullptr, gt_ptr, gt_items, k_list, nk, recall, ndcg);
   if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
+  return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
+}
+
+// The summary of per-row metric values: the same for every evaluation.
+int summarize(int64_t n, const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
+              const float* recall, const float* ndcg, float* summary) {
   if (!summary) return FRECSYS_OK;
   frecsys::EvaluationResult er{frecsys::VectorXi(nk), frecsys::VectorXf(na),
                                frecsys::MatrixXf(n, nk), frecsys::MatrixXf(n, nk)};
@@ -369,9 +379,132 @@ int evaluate_rows(frecsys::DeviceContext& dev, int side, const int64_t* rows, in
   return FRECSYS_OK;
 }
 
+// The list evaluations: caller lists (cand_ptr given) or sampled ones.
+struct ListEval {
+  const int64_t* cand_ptr;
+  const int32_t* cand_items;
+  int32_t n_neg;
+  uint64_t seed;
+};
+
+// Their argument checks on top of evaluate_args_error, before any device
+// call (the fold-in projection is one); "" when fine.
+std::string list_args_error(int64_t n, int64_t n_items, const ListEval& le, bool sampled) {
+  if (sampled) {
+    if (le.n_neg < 0) return "n_neg must not be negative";
+    if (le.n_neg > 0 && n > INT64_MAX / le.n_neg) return "n * n_neg overflows";
+    return "";
+  }
+  if (!le.cand_ptr || le.cand_ptr[0] != 0) return "bad cand_ptr";
+  for (int64_t i = 0; i < n; ++i)
+    if (le.cand_ptr[i + 1] < le.cand_ptr[i]) return "cand_ptr not monotone";
+  if (le.cand_ptr[n] > 0 && !le.cand_items) return "null cand_items";
+  for (int64_t p = 0; p < le.cand_ptr[n]; ++p)
+    if (le.cand_items[p] < 0 || le.cand_items[p] >= n_items)
+      return "candidate id " + std::to_string(le.cand_items[p]) + " out of range";
+  return "";
+}
+
+std::string hist_args_error(int64_t n, int64_t n_items, const int64_t* hist_ptr,
+                            const int32_t* hist_items) {
+  if (n < 0 || !hist_ptr || hist_ptr[0] != 0) return "bad arguments";
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i]) return "hist_ptr not monotone";
+  if (hist_ptr[n] > 0 && !hist_items) return "null hist_items";
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return "item id " + std::to_string(hist_items[p]) + " out of range";
+  return "";
+}
+
+// users != nullptr: trained users (USER side); else the n histories are
+// projected into the EVAL side first.
+int evaluate_lists(frecsys_model* m, const std::string& w, const int64_t* users,
+                   const int64_t* hist_ptr, const int32_t* hist_items, bool fold_in, int64_t n,
+                   const ListEval& le, bool sampled, const int64_t* gt_ptr,
+                   const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                   const uint8_t* item_mask, float* recall, float* ndcg, float* summary) {
+  if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  frecsys::DeviceContext& dev = dm->device();
+  const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
+  std::string e = fold_in ? hist_args_error(n, n_items, hist_ptr, hist_items) : "";
+  if (e.empty())
+    e = evaluate_args_error(n, n_items, gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg);
+  if (e.empty()) e = list_args_error(n, n_items, le, sampled);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (n == 0) return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
+  int side = FRECSYS_SIDE_USER;
+  if (fold_in) {
+    frecsys::Csr csr;
+    csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+    csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+    dm->FoldIn(csr);
+    side = FRECSYS_SIDE_EVAL;
+  }
+  const int flags = exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0;
+  const int rc =
+      sampled ? dev.TrySampledMetrics(side, users, n, flags, item_mask, gt_ptr, gt_items, le.n_neg,
+                                      le.seed, k_list, nk, recall, ndcg)
+              : dev.TryRankCandidatesMetrics(side, users, n, le.cand_ptr, le.cand_items, flags,
+                                             item_mask, gt_ptr, gt_items, k_list, nk, recall, ndcg);
+  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
+  return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
+}
+
 }  // namespace
 
 extern "C" {
+
+int frecsys_model_evaluate_candidates(frecsys_model* m, const int64_t* users, int64_t n,
+                                      const int64_t* cand_ptr, const int32_t* cand_items,
+                                      const int64_t* gt_ptr, const int32_t* gt_items,
+                                      const int32_t* k_list, int32_t nk, const float* alpha_list,
+                                      int32_t na, int32_t exclude_seen, const uint8_t* item_mask,
+                                      float* recall, float* ndcg, float* summary) {
+  return evaluate_lists(m, "frecsys_model_evaluate_candidates: ", users, nullptr, nullptr, false, n,
+                        ListEval{cand_ptr, cand_items, 0, 0}, false, gt_ptr, gt_items, k_list, nk,
+                        alpha_list, na, exclude_seen, item_mask, recall, ndcg, summary);
+}
+
+int frecsys_model_evaluate_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                              const int32_t* hist_items, int64_t n,
+                                              const int64_t* cand_ptr, const int32_t* cand_items,
+                                              const int64_t* gt_ptr, const int32_t* gt_items,
+                                              const int32_t* k_list, int32_t nk,
+                                              const float* alpha_list, int32_t na,
+                                              int32_t exclude_seen, const uint8_t* item_mask,
+                                              float* recall, float* ndcg, float* summary) {
+  return evaluate_lists(m, "frecsys_model_evaluate_candidates_fold_in: ", nullptr, hist_ptr,
+                        hist_items, true, n, ListEval{cand_ptr, cand_items, 0, 0}, false, gt_ptr,
+                        gt_items, k_list, nk, alpha_list, na, exclude_seen, item_mask, recall, ndcg,
+                        summary);
+}
+
+int frecsys_model_evaluate_sampled(frecsys_model* m, const int64_t* users, int64_t n,
+                                   const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                                   uint64_t seed, const int32_t* k_list, int32_t nk,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   const uint8_t* item_mask, float* recall, float* ndcg,
+                                   float* summary) {
+  return evaluate_lists(m, "frecsys_model_evaluate_sampled: ", users, nullptr, nullptr, false, n,
+                        ListEval{nullptr, nullptr, n_neg, seed}, true, gt_ptr, gt_items, k_list, nk,
+                        alpha_list, na, exclude_seen, item_mask, recall, ndcg, summary);
+}
+
+int frecsys_model_evaluate_sampled_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                           const int32_t* hist_items, int64_t n,
+                                           const int64_t* gt_ptr, const int32_t* gt_items,
+                                           int32_t n_neg, uint64_t seed, const int32_t* k_list,
+                                           int32_t nk, const float* alpha_list, int32_t na,
+                                           int32_t exclude_seen, const uint8_t* item_mask,
+                                           float* recall, float* ndcg, float* summary) {
+  return evaluate_lists(m, "frecsys_model_evaluate_sampled_fold_in: ", nullptr, hist_ptr,
+                        hist_items, true, n, ListEval{nullptr, nullptr, n_neg, seed}, true, gt_ptr,
+                        gt_items, k_list, nk, alpha_list, na, exclude_seen, item_mask, recall, ndcg,
+                        summary);
+}
 
 int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
                            const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list,
