@@ -244,7 +244,9 @@ int frecsys_cg_iterations(frecsys_ctx* ctx, int32_t side, int32_t* host);
 /* Per-user loss over `side` (USER or EVAL) rows against ITEM embeddings and
  * G[ITEM]: (1/h) sum (x.u - 1)^2 + beta u^T G u, halved if half != 0.
  * Rows with empty history get 0.  host_out [rows] may be NULL (result kept
- * on device); for USER it is gathered across ranks first. */
+ * on device); for USER it is gathered across ranks first.  Under external
+ * exchange (world > 1, no communicator) nothing is gathered: a rank computes
+ * the rows of its own shard and the other ranks' rows read 0. */
 int frecsys_user_loss(frecsys_ctx* ctx, int32_t side, float beta, int32_t half,
                       float* host_out);
 /* ---- iALS++ subspace solver (ialspp.h) ----

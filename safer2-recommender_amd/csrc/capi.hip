@@ -680,6 +680,11 @@ int hspace_rows(frecsys_ctx* c, int side, int other, int64_t q0, int64_t q1,
     HIP_TRY(c, hipMemcpyAsync(mark.data(), c->d_mark, (size_t)no, hipMemcpyDeviceToHost,
                               c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // row 0 is always on the list: the history-space kernels load it for the
+    // padding rows of a tile and multiply it by c_j = 0 (dual.hip), so it
+    // must hold a rotated row, not what the allocation happened to contain
+    // (a NaN there failed every pivot and sent the whole side to d-space)
+    if (no > 0) mark[0] = 1;
     std::vector<QueueRec> list;
     for (int64_t r = 0; r < no; ++r)
       if (mark[r]) list.push_back(QueueRec{(int32_t)r, 0, 0});
@@ -858,6 +863,9 @@ void flush_ktimers(frecsys_ctx* c) {
       Timer& t = c->timers[p.name];
       t.total_ms += ms;
       t.launches += 1;
+    } else {
+      (void)hipGetLastError();  // a timer that cannot be read is dropped, not left as the
+                                // thread's last error for the next launch to report
     }
     c->event_pool.push_back(p.a);
     c->event_pool.push_back(p.b);
@@ -1492,7 +1500,8 @@ int launch_dspace(frecsys_ctx* c, SolveArgs ap, const std::vector<int32_t>& hs,
     if (rc) return rc;
     if (can_split) {  // long histories of the first batch cut into slabs (a budget of their own)
       const size_t sf = wide_slab_floats(c->Dp);
-      rc = plan_split(c, hs, batch, heff, &ap, wide_slab_rows(), sf,
+      // (an empty shard has an empty queue but still a batch of one slot)
+      rc = plan_split(c, hs, std::min<int64_t>(batch, ap.n_rows), heff, &ap, wide_slab_rows(), sf,
                       (int64_t)(ws_budget(c, c->d_slabs.cap() * sizeof(float)) / (sf * sizeof(float))),
                       s, true);
       if (rc) return rc;
@@ -2089,7 +2098,9 @@ int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, fl
   const bool fresh = c->d_loss.cap() < rows || !c->d_loss;
   int rc = ensure(c, c->d_loss, rows);
   if (rc) return rc;
-  if (fresh || side == 2)
+  // external exchange (world > 1, no communicator): nothing gathers the
+  // other ranks' rows, so they read 0, not what an earlier EVAL call left
+  if (fresh || side == 2 || (c->world > 1 && !c->comm))
     HIP_TRY(c, hipMemsetAsync(c->d_loss, 0, sizeof(float) * std::max<size_t>(rows, 1), c->stream));
   int64_t lo, hi;
   shard(c, side, &lo, &hi);
@@ -2122,7 +2133,8 @@ int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, fl
     // user_loss: both kernels; user_loss.gather: the gather kernel alone (its
     // own rate for the loss_gather roofline)
     frecsys_ctx::Pending g{"user_loss.gather", pool_event(c), pool_event(c)};
-    a.ev_gather = c->Dp > 16 ? g.a : nullptr;
+    // (no launch on an empty shard: an event nobody records must not be timed)
+    a.ev_gather = (c->Dp > 16 && a.n_rows > 0) ? g.a : nullptr;
     ScopedTimer t(c, "user_loss");
     HIP_TRY(c, launch_user_loss(c->Dp, a, c->stream));
     if (a.ev_gather) {

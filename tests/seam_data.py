@@ -139,16 +139,23 @@ def seam_case(key, dim):
     """Everything one half-step needs: the CSRs, the fp32 embeddings of
     oracle.init_embeddings(1, 0.1), the weights, and the solved side's view
     (ptr, col, X = the other side's rows, E = the solved side's rows)."""
-    if (key, dim) in _cases:
-        return _cases[key, dim]
+    if (key, dim) not in _cases:
+        sd = seam_data()
+        _cases[key, dim] = build_case(key, dim, sd.labels, _data[KINDS[key]["seam"]], "seam")
+    return _cases[key, dim]
+
+
+def build_case(key, dim, labels, oriented, fixture):
+    """seam_case for any fixture: `oriented` is as_users(sd) or as_items(sd)
+    of the data whose solved-side labels are `labels`, matching the seam side
+    of KINDS[key]; `fixture` names the data in the reference caches."""
     import oracle as O
     p = KINDS[key]
-    sd = seam_data()
-    nu, ni, up, uc, ip, ic = _data[p["seam"]]
+    nu, ni, up, uc, ip, ic = oriented
     U, V = O.init_embeddings(1, 0.1, dim, nu, ni)
-    c = types.SimpleNamespace(key=key, dim=dim, labels=sd.labels, nu=nu, ni=ni, up=up, uc=uc,
-                              ip=ip, ic=ic, U=U, V=V, entity_weight=None, entity_reg=None,
-                              other_weight=None, gram_weights=None, **p)
+    c = types.SimpleNamespace(key=key, dim=dim, fixture=fixture, labels=labels, nu=nu, ni=ni,
+                              up=up, uc=uc, ip=ip, ic=ic, U=U, V=V, entity_weight=None,
+                              entity_reg=None, other_weight=None, gram_weights=None, **p)
     c.quirk = bool(p.get("quirk", True))
     if c.seam == "user":
         c.ptr, c.col, c.X, c.E, c.n_other = up, uc, V, U, ni
@@ -178,13 +185,12 @@ def seam_case(key, dim):
         inv = np.where(hu > 0, 1.0 / np.maximum(hu, 1).astype(np.float64), 0.0)
         c.entity_reg = np.bincount(np.repeat(np.arange(ni), c.h), weights=inv[ic],
                                    minlength=ni).astype(np.float32)
-    _cases[key, dim] = c
     return c
 
 
 def reference(c):
     """The float64 half-step of case c (numpy_ref drivers), computed once."""
-    k = (c.key, c.dim)
+    k = (c.fixture, c.key, c.dim)
     if k not in _refs:
         if c.kind == 0:
             r = R.ials_side(c.ptr, c.col, c.X, c.E, c.reg, c.w, c.reg_exp)
@@ -205,7 +211,7 @@ def reference(c):
 
 def oracle_step(c):
     """The fp32 C oracle's half-step of case c, computed once."""
-    k = (c.key, c.dim)
+    k = (c.fixture, c.key, c.dim)
     if k not in _oracle:
         import oracle as O
         G = O.gramian(c.X, c.gram_weights)

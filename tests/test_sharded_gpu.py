@@ -18,54 +18,11 @@ import numpy as np
 import pytest
 
 import frecsys_hip as fh
+from shard_data import allgather_rows as _allgather_rows
+from shard_data import allreduce_gram as _allreduce_gram
+from shard_data import contexts as _contexts
 
 pytestmark = pytest.mark.gpu
-
-
-def _contexts(world, dim, nu, ni, up, uc, ip, ic):
-    ctxs = []
-    for r in range(world):
-        c = fh.Context(dim, nu, ni, device=0)
-        if world > 1:
-            c.comm_init(world, r, None)
-        c.load_csr(fh.SIDE_USER, up, uc)
-        c.load_csr(fh.SIDE_ITEM, ip, ic)
-        c.init_embeddings(1, 0.1)
-        ctxs.append(c)
-    return ctxs
-
-
-def _allreduce_gram(ctxs, side, weights=None):
-    parts = [c.gramian(side, weights) for c in ctxs]
-    if len(ctxs) == 1:
-        return parts[0]
-    # the exchange frecsys_gramian does over RCCL: every group slab from its owner
-    slabs = None
-    for c in ctxs:
-        ng, lo, hi, _ = c.gram_groups(side)
-        mine = c.get_gram_groups(side)
-        if slabs is None:
-            slabs = np.zeros_like(mine)
-        assert not mine[:lo].any() and not mine[hi:].any()  # only its own groups
-        slabs[lo:hi] = mine[lo:hi]
-    owned = sorted(c.gram_groups(side)[1:3] for c in ctxs)
-    assert owned[0][0] == 0 and owned[-1][1] == slabs.shape[0]
-    assert all(a[1] == b[0] for a, b in zip(owned, owned[1:]))  # the ranks tile the groups
-    for c in ctxs:
-        c.set_gram_groups(side, slabs)
-    return ctxs[0].get_gramian(side)
-
-
-def _allgather_rows(ctxs, side):
-    if len(ctxs) == 1:
-        return ctxs[0].get_embeddings(side)
-    full = ctxs[0].get_embeddings(side)
-    for c in ctxs[1:]:
-        lo, hi = c.shard_range(side)
-        full[lo:hi] = c.get_embeddings(side)[lo:hi]
-    for c in ctxs:
-        c.set_embeddings(side, full)
-    return full
 
 
 def _allgather_loss(ctxs, w):
