@@ -9,11 +9,17 @@
 //   partial G over own rows -> ncclAllReduce -> solve own rows ->
 //   grouped ncclBroadcast of every rank's rows (an all-gather with uneven
 //   counts, in place).
+//
+// What lives here: the context's life cycle, the data loaders, the Gramian
+// and its exchange, the solve drivers (d-space, history space, wide, CG), the
+// iALS++ block step, the losses and train statistics, frecsys_eval_topk, the
+// timers / work / counters queries, and the one definition of the functions
+// ctx.h declares.  The ranking and evaluation calls (frecsys_recommend and
+// what followed it) are in serve.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cmath>
 #include <functional>
@@ -26,254 +32,21 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/frecsys_hip.h"
-#include "../include/frecsys/parallel.h"
-#include "device_buf.h"
-#include "kernels.h"
+#include "ctx.h"
 #include "wide.h"
 
-using namespace frecsys_hip;
-
 namespace {
-
 std::string g_last_error;
-
-struct Timer {
-  double total_ms = 0.0;
-  int64_t launches = 0;
-};
-
-// Algorithmic work the library launched under a timer key (SURVEY 8(d)
-// definitions, logical dim d; frecsys_work), accumulated per launch.
-struct Work {
-  double flops = 0.0, bytes = 0.0;
-  int64_t entities = 0, launches = 0;
-};
-
-// A per-entity vector the host hands over on every call: its device copy
-// and the pinned staging buffer upload() fills it through.
-struct UploadBuf {
-  DevBuf<float> dev;
-  PinnedBuf<float> stage;
-};
-
 }  // namespace
 
-// Members are destroyed last to first: the streams and events are declared
-// before every buffer, so they outlive them (frecsys_ctx_destroy
-// synchronises the streams, then deletes the context with its device
-// current).
-struct frecsys_ctx {
-  int dim = 0, Dp = 0, device = 0, quirks = 1;
-  int64_t n[3] = {0, 0, 0};
-  Stream stream;
-  // history-space (dual) path: a second stream for the concurrent d-space
-  // solve of the long histories, and a second lane of history-space buckets
-  Stream stream2, stream3;
-  hipStream_t stream5 = nullptr;  // early basis builds: an alias of stream3
-  Event ev0, ev1;
-  Event ev_fork, ev_join, ev_fork3, ev_join3;
-  Event ev_pre5, ev_eager[2];
-  std::vector<Event> events;  // owner of every pooled event (pool_event)
-  DevBuf<float> emb[3];
-  DevBuf<float> snap[2];
-  DevBuf<float> gram[2];
-  DevBuf<int64_t> rp[3];
-  DevBuf<int32_t> col[3];
-  int64_t nnz[3] = {0, 0, 0};
-  std::vector<int64_t> host_rp[2];
-  std::vector<int64_t> bounds[2];
-  // per-entity vectors (device)
-  UploadBuf d_entity_weight, d_entity_reg, d_other_weight, d_gram_w;
-  DevBuf<float> d_partials;   // Gramian leaf workspace
-  DevBuf<float> d_gslabs[3];  // Gramian group slabs per side (2: train stats)
-  GramPlan gplan[2];             // plan of the last Gramian formed per side
-  int gram_own[2][2] = {{0, 0}, {0, 0}};  // ... and the groups this rank computed
-  DevBuf<float> d_loss;
-  DevBuf<float> d_quad;
-  DevBuf<unsigned long long> d_fail;
-  DevBuf<unsigned int> d_counter;
-  // cumulative event counters (frecsys_counter): [0] tagged-word polls that
-  // timed out on the device (common.h tpoll); history-space reruns on host
-  DevBuf<unsigned int> d_events;
-  int64_t hspace_reruns = 0;
-  // FRECSYS_DUAL_PROF diagnostics: cycle counters of the wide / tiled
-  // d-space solve and of the history-space buckets
-  DevBuf<unsigned long long> w_prof, d_prof, dual_prof;
-  // per side: the rank's entities in decreasing-history order (LPT queue)
-  DevBuf<QueueRec> d_order[3];
-  int64_t order_n[3] = {0, 0, 0};
-  bool order_stale[3] = {true, true, true};
-  std::vector<int64_t> host_rp_eval;
-  ncclComm_t comm = nullptr;
-  int world = 1, rank = 0;
-  std::string err;
-  int64_t err_entity = -1;
-  std::map<std::string, Timer> timers;
-  std::map<std::string, Work> work;
-  // history-space (dual) path: the basis of each side's Gramian, the rotated
-  // copy of each side, and the solved rows in the rotated basis
-  DevBuf<float> q[2];      // Dp x Dp
-  DevBuf<float> tri[2];    // [2 * Dp]: diagonal, subdiagonal
-  DevBuf<float> refl[2];   // Dp x Dp reflectors + [Dp] tau
-  DevBuf<float> xrot[2];   // n_s x Dp
-  DevBuf<char> qsplit[2][2];  // split images of Q, Q^T
-  DevBuf<char> gsplit;  // split image of G[ITEM] for the wide user loss
-  DevBuf<float> out_rot[3];
-  DevBuf<float> dual_table;  // [entities][3][Dp] LDL^T factors
-  // wide dims (Dp = 512 / 1024): tridiagonalisation work, d-space workspace
-  DevBuf<float> tri_work;
-  DevBuf<int32_t> d_rix[2];  // iALS++: rating index per CSR entry
-  DevBuf<float> d_pred[2];   // iALS++: training / EVAL prediction vectors
-  DevBuf<float> d_resid;
-  // sharded iALS++ / SAFER2++ block steps: the block columns of the side's
-  // rows before the step ([n][bw]), for the prediction refresh of the rows
-  // other ranks solve (frecsys_pp_step with RCCL; frecsys_pp_sync without)
-  DevBuf<float> d_pp_old;
-  int pp_old_side = -1, pp_old_start = 0, pp_old_bw = 0;
-  // external-exchange transport (frecsys_set_transport): the in-call
-  // exchanges of a sharded call without a communicator
-  frecsys_transport transport{};
-  bool has_transport = false;
-  std::vector<int32_t> pp_order_all[2];  // every row of the side by decreasing h (stable)
-  DevBuf<float> d_resid_e;       // per-entity residuals [n] of a sharded pp_step
-  DevBuf<float> d_rows;          // train stats: per-row values
-  DevBuf<float> d_gstat;         // train stats: U^T U, V^T V
-  DevBuf<double> d_dot;
-  DevBuf<float> d_scores;        // evaluation: [batch][items] scores
-  DevBuf<int32_t> d_topk;        // [eval rows][k]
-  DevBuf<char> d_rec;            // frecsys_recommend: candidates, counts, bitmaps, outputs
-  DevBuf<float> d_sim_inv;       // frecsys_similar: inverse row norms of the side searched
-  DevBuf<int32_t> d_samp_ids;    // frecsys_sampled_metrics: the candidate ids of a row batch
-  int64_t rec_splits = 0;       // item splits of the last call (frecsys_counter "recommend_splits")
-  // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
-  // per row of each side (device scratch + host copy; -1: not solved here),
-  // the kernel's {sum of i, entities at the cap} and the cumulative counters
-  DevBuf<int32_t> d_cg_iters;
-  DevBuf<unsigned long long> d_cg_stats;
-  DevBuf<int32_t> d_cg_bstart;  // batches of the queue (cg_plan_batches)
-  std::vector<int32_t> cg_bstart;
-  std::vector<int32_t> cg_iters[3];
-  int64_t cg_iterations = 0, cg_unconverged = 0;
-  DevBuf<float> wide_ws;         // [wide batch][wide_slot_floats(Dp)]
-  // the pre-split copy of the other side for the wide d-space SYRK
-  // (wide_syrk.hip; FRECSYS_WIDE_PRESPLIT=0: the register-staged SYRK)
-  DevBuf<char> wide_xs;
-  // the history-space wide bucket (dual.hip, 256 < h_eff <= 512): split Z
-  // fragments, Cholesky slots of S, z
-  DevBuf<char> dw_zs;
-  DevBuf<float> dw_slots;
-  DevBuf<float> dw_z;
-  bool wide_presplit = true;
-  // FRECSYS_WIDE_WS_MB: the budget of EACH of the wide workspaces (the batch
-  // workspace of A tiles, the long-history slabs, the history-space wide
-  // bucket), each allocated only as large as its batch needs (8 GB instead of
-  // 4 measured 0.6 % faster at MSD and config 5, 16 GB another 1.5 % at
-  // config 5 -- fewer, fuller batches).  Each is also capped at a quarter of
-  // the device memory free when it is sized (ws_budget), and a failed
-  // allocation halves its batch instead of failing the call (ensure_batch);
-  // the pre-split table of the other side ((n_other + 1) (6 Dp + 128) B:
-  // 12.6 GB for config 5's 2M users) falls back to the register-staged SYRK
-  // (bit-identical) when it does not fit.  At the default, the three
-  // workspaces and the table take <= 61 GB of 288 at config 5.
-  int64_t wide_ws_mb = 16384;
-  bool ws_free_cap = true;   // FRECSYS_WS_FREE_CAP=0: no free-memory cap (tests of the OOM path)
-  int64_t ws_shrinks = 0;    // allocations cut by a failed hipMalloc (frecsys_counter "ws_shrinks")
-  // long-history split of the d-space solve
-  int split_rows = 4096;         // rows per partial SYRK (FRECSYS_SPLIT_ROWS, 0 = off; swept 512..4096 at ML-20M d=256: 4096 best)
-  std::vector<int2> h_split;
-  std::vector<SplitWork> h_work;
-  DevBuf<int2> d_split;
-  DevBuf<SplitWork> d_work;
-  DevBuf<float> d_slabs;
-  std::vector<int32_t> order_h[3];      // history lengths in queue order
-  std::vector<QueueRec> h_order[3];      // host copy of each side's queue (source of its upload)
-  int dual_on = 1;
-  // Content versions (every write of a side's embeddings or Gramian takes a
-  // fresh number): a Gramian recomputed from unchanged embeddings is reused
-  // (the computation is deterministic, the result would be identical), and
-  // a basis / rotated copy is rebuilt only when its inputs changed.  When a
-  // Gramian is formed for a side whose consumer last took the history-space
-  // path, its basis is built right away on stream5 (e.g. during the user
-  // loss and the host's xi / omega math between epochs) instead of on the
-  // next solve's critical path.
-  uint64_t ver_counter = 0;
-  uint64_t emb_ver[3] = {0, 0, 0};
-  uint64_t gram_ver[2] = {0, 0};
-  uint64_t gram_src[2] = {0, 0};    // emb_ver the Gramian was formed from (0: not reusable)
-  uint64_t basis_gram[2] = {0, 0};  // gram_ver the basis (T, Q, Q pieces) belongs to
-  uint64_t xrot_emb[2] = {0, 0};    // emb_ver of the rotated copy (0: stale / snapshot)
-  uint64_t xrot_gram[2] = {0, 0};   // ... and the basis it was rotated into
-  uint64_t xrot_sub[2] = {0, 0};    // ... and the row subset it covers (0: every row)
-  // Row subsets of the forward rotation: the rows of the other side that a
-  // consumer side's history-space entities read (its shard's queue positions
-  // [key0, key1)).  At N ranks a shard's short histories touch a fraction of
-  // the other side, so the replicated rotation shrinks with N.  Built once
-  // per (queue, split point) -- the histories do not change between epochs.
-  DevBuf<QueueRec> d_hrows[3];
-  int64_t n_hrows[3] = {-1, -1, -1};  // rows in the subset; -1: none (every row)
-  int64_t hrows_key[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
-  // Prefix sums over each side's queue of h_eff, h_eff^2, h_eff^3 and the
-  // non-empty count (two variants: with / without the ProjectV tail rows):
-  // the frecsys_work accounting of any queue range in O(1) instead of a host
-  // loop over the entities on every solve.  Rebuilt with the queue.
-  struct WorkPrefix {
-    bool valid = false;
-    std::vector<double> h1, h2, h3;
-    std::vector<int64_t> nz;
-  };
-  WorkPrefix wprefix[3][2];
-  uint64_t hrows_gen[3] = {0, 0, 0};  // subset id (0: every row)
-  DevBuf<uint8_t> d_mark;
-  bool dual_used[3] = {false, false, false};  // the side's last solve took history space
-  int eager_on = 1;                 // FRECSYS_EAGER=0: no early basis builds (A/B)
-  // Basis kind per side: 0 = tridiagonal (G = Q T Q^T, any mu / lambda per
-  // entity), 1 = Cholesky of the one M = mu*G + lam*I every entity of the
-  // consumer's launch shares (q[] then holds L^-T, tri[][0] its status).
-  // want_*: what the consumer's last history-space solve used (early builds).
-  int basis_mode[2] = {0, 0};
-  float basis_mu[2] = {0.f, 0.f}, basis_lam[2] = {0.f, 0.f};
-  int want_mode[2] = {0, 0};
-  float want_mu[2] = {0.f, 0.f}, want_lam[2] = {0.f, 0.f};
-  int chol_basis_on = 1;            // FRECSYS_CHOL_BASIS=0: always tridiagonal (A/B, tests)
-  DevBuf<float> chol_work;
-  bool eager_pending[2] = {false, false};
-  int dual_max_h = 256;  // longest h_eff on the history-space path (set per Dp at create)
-  int dual_max_h_side[3] = {256, 256, 256};  // per solved side (FRECSYS_DUAL_MAX_H_USER / _ITEM)
-  int dual_serial = 0;  // FRECSYS_DUAL_SERIAL=1: no stream overlap (profiling)
-  int debug_skip = 0;   // FRECSYS_DEBUG_SKIP ablation mask (-DFRECSYS_ABLATION builds only)
-  // per-kernel event pairs, resolved after the call's final synchronisation
-  struct Pending {
-    std::string name;
-    hipEvent_t a, b;
-  };
-  std::vector<Pending> pending;
-  std::vector<hipEvent_t> event_pool;  // idle handles of `events`
-};
-
-namespace {
+// The one definition of what ctx.h declares for every host translation unit.
+namespace frecsys_hip {
 
 int fail(frecsys_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   g_last_error = msg;
   return code;
 }
-
-#define HIP_TRY(c, expr)                                                            \
-  do {                                                                              \
-    hipError_t _e = (expr);                                                         \
-    if (_e != hipSuccess)                                                           \
-      return fail((c), FRECSYS_ERR_HIP,                                             \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));               \
-  } while (0)
-
-#define NCCL_TRY(c, expr)                                                           \
-  do {                                                                              \
-    ncclResult_t _r = (expr);                                                       \
-    if (_r != ncclSuccess)                                                          \
-      return fail((c), FRECSYS_ERR_RCCL,                                            \
-                  std::string(#expr) + ": " + ncclGetErrorString(_r));              \
-  } while (0)
 
 void add_work(frecsys_ctx* c, const std::string& key, double flops, double bytes,
               int64_t entities) {
@@ -284,24 +57,30 @@ void add_work(frecsys_ctx* c, const std::string& key, double flops, double bytes
   w.launches += 1;
 }
 
+void partition_rows(int64_t n_rows, const int64_t* row_ptr, int parts, int64_t* bounds) {
+  const int64_t nnz = row_ptr[n_rows] - row_ptr[0];
+  bounds[0] = 0;
+  for (int r = 1; r < parts; ++r) {
+    const int64_t target = row_ptr[0] + (nnz * r) / parts;
+    const int64_t* it = std::lower_bound(row_ptr, row_ptr + n_rows + 1, target);
+    int64_t b = it - row_ptr;
+    if (b < bounds[r - 1]) b = bounds[r - 1];
+    if (b > n_rows) b = n_rows;
+    bounds[r] = b;
+  }
+  bounds[parts] = n_rows;
+}
+
+}  // namespace frecsys_hip
+
+namespace {
+
 // SURVEY 8(d) per entity of h assembly rows at dim d: d-space SYRK
 // h d (d+1) and LLT d^3/3 + 2 d^2 flops; gather bytes h d 4 (rows) + h 4
 // (ids) + 8 (row offset) + d 4 (the solution written).
 // (SYRK and gather are linear in h: summed from the queue prefix sums,
 // heff_sums below.)
 double dspace_solve_flops(double d) { return d * d * d / 3.0 + 2.0 * d * d; }
-
-// DevBuf::reserve as a call's status.  A buffer that still holds memory
-// after a failure is one whose hipFree failed.
-template <typename T>
-int ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count) {
-  const hipError_t e = b.reserve(count);
-  if (e == hipSuccess) return FRECSYS_OK;
-  return fail(c, FRECSYS_ERR_HIP,
-              std::string(b ? "hipFree(*p): "
-                            : "hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)): ") +
-                  hipGetErrorString(e));
-}
 
 // ensure() that reports an out-of-memory hipMalloc instead of failing
 // (DevBuf::try_reserve): *oom is set and the buffer left empty.
@@ -383,22 +162,6 @@ int ensure_batch(frecsys_ctx* c, DevBuf<T>& b, size_t per, int64_t* batch) {
 }
 
 bool valid_side(int side) { return side >= 0 && side <= 2; }
-
-// Contiguous nnz-balanced split: rank r gets rows whose prefix nnz falls in
-// [r*nnz/P, (r+1)*nnz/P).
-void partition_rows(int64_t n_rows, const int64_t* row_ptr, int parts, int64_t* bounds) {
-  const int64_t nnz = row_ptr[n_rows] - row_ptr[0];
-  bounds[0] = 0;
-  for (int r = 1; r < parts; ++r) {
-    const int64_t target = row_ptr[0] + (nnz * r) / parts;
-    const int64_t* it = std::lower_bound(row_ptr, row_ptr + n_rows + 1, target);
-    int64_t b = it - row_ptr;
-    if (b < bounds[r - 1]) b = bounds[r - 1];
-    if (b > n_rows) b = n_rows;
-    bounds[r] = b;
-  }
-  bounds[parts] = n_rows;
-}
 
 void refresh_bounds(frecsys_ctx* c, int side) {
   if (side > 1) return;
@@ -808,31 +571,6 @@ int upload(frecsys_ctx* c, UploadBuf& b, const float* host, size_t n) {
                             c->stream));
   return FRECSYS_OK;
 }
-
-struct ScopedTimer {
-  frecsys_ctx* c;
-  const char* name;
-  ScopedTimer(frecsys_ctx* c_, const char* n_) : c(c_), name(n_) {
-    (void)hipEventRecord(c->ev0, c->stream);
-  }
-  // The end of the timed work, for a caller that has host work to do while
-  // the device runs: mark(), the host work, then finish().
-  void mark() { (void)hipEventRecord(c->ev1, c->stream); }
-  // Stops the timer: synchronises on the end event and accumulates.
-  void stop() {
-    mark();
-    finish();
-  }
-  void finish() {
-    (void)hipEventSynchronize(c->ev1);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) {
-      Timer& t = c->timers[name];
-      t.total_ms += ms;
-      t.launches += 1;
-    }
-  }
-};
 
 // Event pair around one launch on any stream; resolved by flush_ktimers
 // after the stream has been synchronised.
@@ -2193,1195 +1931,6 @@ int frecsys_eval_topk(frecsys_ctx* c, int32_t k, int32_t* topk) {
   HIP_TRY(c, hipMemcpyAsync(topk, c->d_topk, sizeof(int32_t) * n * k, hipMemcpyDeviceToHost,
                             c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return FRECSYS_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// gain[j] = 1 / log2(j + 2) and its sequential prefix idcg[m] = gain[0] + ...
-// + gain[m-1] (idcg[0] = 0), in double with the host's std::log2: the terms
-// and the norm of RankMetrics (recommender.h:152-182) in its own order.
-struct MetricTables {
-  double gain[kMetricMaxK];
-  double idcg[kMetricMaxK + 1];
-};
-const MetricTables& metric_tables() {
-  static const MetricTables tab = [] {
-    MetricTables t;
-    t.idcg[0] = 0.0;
-    for (int j = 0; j < kMetricMaxK; ++j) {
-      t.gain[j] = 1.0 / std::log2(j + 2.0);
-      t.idcg[j + 1] = t.idcg[j] + t.gain[j];
-    }
-    return t;
-  }();
-  return tab;
-}
-
-// The argument checks frecsys_list_metrics and frecsys_rank_metrics share;
-// "" when fine.  n_items < 0: no upper bound on the ground-truth ids.
-std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
-                              const int32_t* k_list, int32_t nk, int64_t n_items,
-                              int32_t* max_k) {
-  if (n < 0 || !gt_ptr || !k_list) return "bad arguments (null gt_ptr / k_list, n < 0)";
-  if (nk < 1 || nk > kMetricMaxCutoffs)
-    return "nk must be in [1, " + std::to_string(kMetricMaxCutoffs) + "]";
-  int32_t mk = 0;
-  for (int32_t q = 0; q < nk; ++q) {
-    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
-      return "k_list[" + std::to_string(q) + "] must be in [1, " + std::to_string(kMetricMaxK) +
-             "]";
-    mk = std::max(mk, k_list[q]);
-  }
-  *max_k = mk;
-  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
-  for (int64_t i = 0; i < n; ++i) {
-    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
-    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
-  }
-  if (n > 0 && !gt_items) return "null gt_items";
-  for (int64_t p = 0; p < gt_ptr[n]; ++p)
-    if (gt_items[p] < 0 || (n_items >= 0 && gt_items[p] >= n_items))
-      return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
-  return "";
-}
-
-// The ground truth as sets: every row ascending and distinct.  Rows are sorted
-// in place in a copy (a row already strictly ascending is left alone), on host
-// threads over nnz-balanced row ranges when there is enough of it, then
-// closed up over the dropped repeats; the result does not depend on the
-// thread count.
-void sorted_ground_truth(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
-                         std::vector<int64_t>* sp, std::vector<int32_t>* sg) {
-  const int64_t total = gt_ptr[n];
-  sg->assign(gt_items, gt_items + total);
-  sp->assign((size_t)n + 1, 0);
-  std::vector<int64_t> cnt((size_t)n);
-  int32_t* base = sg->data();
-  auto work = [&](int64_t a, int64_t b) {
-    for (int64_t i = a; i < b; ++i) {
-      int32_t* p = base + gt_ptr[i];
-      int32_t* e = base + gt_ptr[i + 1];
-      bool ascending = true;
-      for (int32_t* q = p + 1; q < e; ++q)
-        if (q[-1] >= q[0]) {
-          ascending = false;
-          break;
-        }
-      if (!ascending) {
-        std::sort(p, e);
-        e = std::unique(p, e);
-      }
-      cnt[(size_t)i] = e - p;
-    }
-  };
-  const int nt = total < (1 << 16)
-                     ? 1
-                     : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (nt == 1) {
-    work(0, n);
-  } else {
-    std::vector<int64_t> bounds((size_t)nt + 1);
-    partition_rows(n, gt_ptr, nt, bounds.data());
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(work, bounds[(size_t)t], bounds[(size_t)t + 1]);
-    for (auto& t : th) t.join();
-  }
-  int64_t w = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    if (w != gt_ptr[i]) std::memmove(base + w, base + gt_ptr[i], sizeof(int32_t) * (size_t)cnt[(size_t)i]);
-    w += cnt[(size_t)i];
-    (*sp)[(size_t)i + 1] = w;
-  }
-  sg->resize((size_t)w);
-}
-
-// What frecsys_rank_metrics adds to the ranking of frecsys_recommend.
-struct MetricsRequest {
-  const int64_t* gt_ptr;
-  const int32_t* gt_items;
-  const int32_t* k_list;
-  int32_t nk;
-  float* recall;
-  float* ndcg;
-};
-
-// The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
-// to the host) and frecsys_rank_metrics (mt given: every batch's lists stay on
-// the device, the metric kernel reads them there and n x nk x 2 floats go to
-// the host).  The scan is the same launch with the same workspace layout in
-// both; the ground truth, the tables and the metric outputs lie behind it.
-int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
-                   int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
-                   int32_t* items, float* scores, const MetricsRequest* mt) {
-  const std::string w = std::string(what) + ": ";
-  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
-    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
-  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
-  if (flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
-    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
-  if (n_rows < 0 || (n_rows > 0 && (mt ? (!mt->recall || !mt->ndcg) : !items)))
-    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
-  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
-  if (exclude && !c->rp[side])
-    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
-  if (!c->emb[side] || !c->emb[1])
-    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
-  const int64_t ns = c->n[side], m = c->n[1], n = n_rows;
-  if (rows) {
-    for (int64_t i = 0; i < n; ++i)
-      if (rows[i] < 0 || rows[i] >= ns)
-        return fail(c, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(rows[i]) + " out of range");
-  } else if (n > ns) {
-    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
-  }
-  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
-  std::vector<int64_t> gt_sp;
-  std::vector<int32_t> gt_sg;
-  if (mt) {
-    int32_t mk = 0;
-    const std::string e = metric_args_error(n, mt->gt_ptr, mt->gt_items, mt->k_list, mt->nk, m, &mk);
-    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
-  }
-  if (n == 0) return FRECSYS_OK;
-  const size_t nk = mt ? (size_t)mt->nk : 0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // knobs, read per call
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  int dev_cus = 256;
-  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  // item splits: about 2 workgroups per CU over the call's 64-row blocks,
-  // within what the merge keeps in LDS
-  const int max_splits = recommend_max_splits(k, m);
-  const int64_t row_blocks = (n + 63) / 64;
-  int splits = (int)std::min<int64_t>(max_splits, (2 * (int64_t)dev_cus + row_blocks - 1) / row_blocks);
-  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS"))
-    if (atoi(v) > 0) splits = std::min(max_splits, atoi(v));
-  splits = std::max(1, splits);
-  const int cap = recommend_cap(k);
-  const int64_t W = recommend_words(m);
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  // per row of a batch: candidates, counts, history bits, outputs (and the
-  // two metric rows)
-  const size_t per_row = (size_t)splits * cap * 8 + (size_t)splits * 4 +
-                         (exclude ? (size_t)W * 4 : 0) + (size_t)k * 8 + nk * 8;
-  int64_t nb = std::max<int64_t>(1, (int64_t)(((size_t)ws_mb << 20) / per_row));
-  if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
-  nb = std::min(nb, n);
-  const size_t o_cand = 0;
-  const size_t o_counts = up16(o_cand + (size_t)nb * splits * cap * 8);
-  const size_t o_bitmap = up16(o_counts + (size_t)nb * splits * 4);
-  const size_t o_items = up16(o_bitmap + (exclude ? (size_t)nb * W * 4 : 0));
-  const size_t o_scores = up16(o_items + (size_t)nb * k * 4);
-  const size_t o_mask = up16(o_scores + (size_t)nb * k * 4);
-  const size_t o_qrows = up16(o_mask + (size_t)W * 4);
-  size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
-  // behind the ranking's workspace: ground truth, tables, cut-offs, metric rows
-  size_t o_gtptr = 0, o_gt = 0, o_gain = 0, o_idcg = 0, o_klist = 0, o_recall = 0, o_ndcg = 0;
-  if (mt) {
-    o_gtptr = up16(total);
-    o_gt = up16(o_gtptr + ((size_t)n + 1) * 8);
-    o_gain = up16(o_gt + (size_t)mt->gt_ptr[n] * 4);  // room for every id; repeats are dropped
-    o_idcg = up16(o_gain + sizeof(double) * kMetricMaxK);
-    o_klist = up16(o_idcg + sizeof(double) * (kMetricMaxK + 1));
-    o_recall = up16(o_klist + nk * 4);
-    o_ndcg = up16(o_recall + (size_t)nb * nk * 4);
-    total = o_ndcg + (size_t)nb * nk * 4;
-  }
-  int rc = ensure(c, c->d_rec, total);
-  if (rc) return rc;
-  // eligibility bits of the items: the mask and id < n_items
-  std::vector<uint32_t> maskw((size_t)W, 0u);
-  for (int64_t j = 0; j < m; ++j)
-    if (!item_mask || item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
-                            hipMemcpyHostToDevice, c->stream));
-  if (rows)
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
-                              c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  RecommendArgs a{};
-  a.X = c->emb[side];
-  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
-  a.Y = c->emb[1];
-  a.m = m;
-  a.Dp = c->Dp;
-  a.k = k;
-  a.splits = splits;
-  c->rec_splits = splits;
-  a.row_ptr = exclude ? c->rp[side] : nullptr;
-  a.col = exclude ? c->col[side] : nullptr;
-  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
-  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
-  a.cand = (unsigned long long*)(c->d_rec + o_cand);
-  a.counts = (int32_t*)(c->d_rec + o_counts);
-  a.out_items = (int32_t*)(c->d_rec + o_items);
-  a.out_scores = (float*)(c->d_rec + o_scores);
-  RankMetricsArgs ma{};
-  if (mt) {
-    ma.lists = a.out_items;
-    ma.k = k;
-    ma.gt_ptr = (const int64_t*)(c->d_rec + o_gtptr);
-    ma.gt = (const int32_t*)(c->d_rec + o_gt);
-    ma.k_list = (const int32_t*)(c->d_rec + o_klist);
-    ma.nk = (int)nk;
-    ma.gain = (const double*)(c->d_rec + o_gain);
-    ma.idcg = (const double*)(c->d_rec + o_idcg);
-    ma.recall = (float*)(c->d_rec + o_recall);
-    ma.ndcg = (float*)(c->d_rec + o_ndcg);
-  }
-  for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
-    a.r0 = r0;
-    a.n = std::min(nb, n - r0);
-    ScopedTimer t(c, "recommend");
-    HIP_TRY(c, launch_recommend(a, c->stream));
-    if (mt && r0 == 0) {
-      // the ground truth is sorted on the host while the first batch is
-      // scanned, and uploaded behind it with the tables and the cut-offs
-      t.mark();
-      sorted_ground_truth(n, mt->gt_ptr, mt->gt_items, &gt_sp, &gt_sg);
-      const MetricTables& tab = metric_tables();
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gtptr, gt_sp.data(), sizeof(int64_t) * ((size_t)n + 1),
-                                hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gt, gt_sg.data(), sizeof(int32_t) * gt_sg.size(),
-                                hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gain, tab.gain, sizeof(tab.gain),
-                                hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_idcg, tab.idcg, sizeof(tab.idcg),
-                                hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_klist, mt->k_list, sizeof(int32_t) * nk,
-                                hipMemcpyHostToDevice, c->stream));
-      t.finish();
-    } else {
-      t.stop();
-    }
-    if (mt) {  // the lists stay on the device: only the metric rows come back
-      ma.r0 = r0;
-      ma.n = a.n;
-      ScopedTimer tm(c, "rank_metrics");
-      HIP_TRY(c, launch_rank_metrics(ma, c->stream));
-      tm.stop();
-      HIP_TRY(c, hipMemcpyAsync(mt->recall + r0 * nk, ma.recall, sizeof(float) * a.n * nk,
-                                hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(mt->ndcg + r0 * nk, ma.ndcg, sizeof(float) * a.n * nk,
-                                hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      continue;
-    }
-    HIP_TRY(c, hipMemcpyAsync(items + r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
-                              hipMemcpyDeviceToHost, c->stream));
-    if (scores)
-      HIP_TRY(c, hipMemcpyAsync(scores + r0 * k, a.out_scores, sizeof(float) * a.n * k,
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // scoring flops at the logical dim; bytes: both tables read once, lists written
-  const double dd = c->dim;
-  add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
-           ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
-  // metrics: two double divisions per (row, cut-off); bytes: the lists and the
-  // ground truth read, the metric rows written
-  if (mt)
-    add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
-             (double)n * k * 4.0 + (double)gt_sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
-                 (double)n * (double)nk * 8.0,
-             n);
-  return FRECSYS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
-                      int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
-  return recommend_impl(c, "recommend", side, rows, n_rows, k, flags, item_mask, items, scores,
-                        nullptr);
-}
-
-int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
-                         int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
-                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
-                         float* ndcg) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: null context");
-  // the list length is the largest cut-off
-  if (!k_list || nk < 1 || nk > kMetricMaxCutoffs)
-    return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: k_list must hold 1 to " +
-                                            std::to_string(kMetricMaxCutoffs) + " cut-offs");
-  int32_t k = 0;
-  for (int32_t q = 0; q < nk; ++q) {
-    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
-      return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: cut-offs must be in [1, 1024]");
-    k = std::max(k, k_list[q]);
-  }
-  const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
-  return recommend_impl(c, "rank_metrics", side, rows, n_rows, k, flags, item_mask, nullptr, nullptr,
-                        &mt);
-}
-
-int frecsys_score_pairs(frecsys_ctx* c, int32_t side, const int64_t* rows, const int32_t* items,
-                        int64_t n_pairs, float* scores) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "score_pairs: null context");
-  const std::string w = "score_pairs: ";
-  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
-    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
-  if (n_pairs < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative pair count");
-  if (n_pairs == 0) return FRECSYS_OK;
-  if (!rows || !items || !scores) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
-  if (!c->emb[side] || !c->emb[1])
-    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
-  const int64_t ns = c->n[side], m = c->n[1], n = n_pairs;
-  for (int64_t i = 0; i < n; ++i) {
-    if (rows[i] < 0 || rows[i] >= ns)
-      return fail(c, FRECSYS_ERR_INVALID, w + "row id " + std::to_string(rows[i]) + " out of range");
-    if (items[i] < 0 || items[i] >= m)
-      return fail(c, FRECSYS_ERR_INVALID,
-                  w + "item id " + std::to_string(items[i]) + " out of range");
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  // per pair: row id, item id, score
-  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(64, (ws_mb << 20) / 16));
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_rows = 0, o_items = up16((size_t)nb * 8), o_out = up16(o_items + (size_t)nb * 4);
-  int rc = ensure(c, c->d_rec, o_out + (size_t)nb * 4);
-  if (rc) return rc;
-  ScorePairsArgs a{};
-  a.X = c->emb[side];
-  a.Y = c->emb[1];
-  a.Dp = c->Dp;
-  a.rows = (const int64_t*)(c->d_rec + o_rows);
-  a.items = (const int32_t*)(c->d_rec + o_items);
-  a.out = (float*)(c->d_rec + o_out);
-  for (int64_t p0 = 0; p0 < n; p0 += nb) {  // one timed launch per pair batch
-    a.n = std::min(nb, n - p0);
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_rows, rows + p0, sizeof(int64_t) * a.n,
-                              hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_items, items + p0, sizeof(int32_t) * a.n,
-                              hipMemcpyHostToDevice, c->stream));
-    ScopedTimer t(c, "score_pairs");
-    HIP_TRY(c, launch_score_pairs(a, c->stream));
-    t.stop();
-    HIP_TRY(c, hipMemcpyAsync(scores + p0, a.out, sizeof(float) * a.n, hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // flops at the logical dim; bytes: one padded item row per pair, ids, scores
-  add_work(c, "score_pairs", 2.0 * (double)n * c->dim,
-           (double)n * c->Dp * 4.0 + (double)n * 12.0 + (double)n * 4.0, n);
-  return FRECSYS_OK;
-}
-
-int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
-                            const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
-                            int32_t flags, const uint8_t* item_mask, int32_t* items,
-                            float* scores) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates: null context");
-  const std::string w = "rank_candidates: ";
-  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_EVAL)
-    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
-  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
-  if (flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
-    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
-  if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n_rows == 0) return FRECSYS_OK;
-  if (!cand_ptr || !items) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
-  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
-  if (exclude && !c->rp[side])
-    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
-  if (!c->emb[side] || !c->emb[1])
-    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
-  const int64_t ns = c->n[side], m = c->n[1], n = n_rows;
-  if (rows) {
-    for (int64_t i = 0; i < n; ++i)
-      if (rows[i] < 0 || rows[i] >= ns)
-        return fail(c, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(rows[i]) + " out of range");
-  } else if (n > ns) {
-    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
-  }
-  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
-  if (cand_ptr[0] != 0) return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr[0] must be 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (cand_ptr[i + 1] < cand_ptr[i])
-      return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr not monotone at row " + std::to_string(i));
-  const int64_t pairs = cand_ptr[n];
-  if (pairs > 0 && !cand_items) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_items");
-  for (int64_t p = 0; p < pairs; ++p)
-    if (cand_items[p] < 0 || cand_items[p] >= m)
-      return fail(c, FRECSYS_ERR_INVALID,
-                  w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  const int64_t W = recommend_words(m);
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  // per row of a batch: its candidate ids, its outputs, its history bits.
-  // Batches are cut greedily in row order (at least one row each); the
-  // workspace is sized for the largest.
-  const size_t row_fixed = (size_t)k * 8 + (exclude ? (size_t)W * 4 : 0);
-  const size_t budget = (size_t)ws_mb << 20;
-  std::vector<int64_t> cuts{0};
-  int64_t max_rows = 0, max_ids = 0;
-  for (int64_t r0 = 0; r0 < n;) {
-    size_t bytes = 0;
-    int64_t r1 = r0;
-    while (r1 < n) {
-      const size_t add = row_fixed + (size_t)(cand_ptr[r1 + 1] - cand_ptr[r1]) * 4;
-      if (r1 > r0 && bytes + add > budget) break;
-      bytes += add;
-      ++r1;
-    }
-    max_rows = std::max(max_rows, r1 - r0);
-    max_ids = std::max(max_ids, cand_ptr[r1] - cand_ptr[r0]);
-    cuts.push_back(r1);
-    r0 = r1;
-  }
-  const size_t o_ids = 0;
-  const size_t o_bitmap = up16(o_ids + (size_t)max_ids * 4);
-  const size_t o_items = up16(o_bitmap + (exclude ? (size_t)max_rows * W * 4 : 0));
-  const size_t o_scores = up16(o_items + (size_t)max_rows * k * 4);
-  const size_t o_mask = up16(o_scores + (size_t)max_rows * k * 4);
-  const size_t o_ptr = up16(o_mask + (size_t)W * 4);
-  const size_t o_qrows = up16(o_ptr + ((size_t)n + 1) * 8);
-  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
-  int rc = ensure(c, c->d_rec, total);
-  if (rc) return rc;
-  std::vector<uint32_t> maskw((size_t)W, 0u);
-  for (int64_t j = 0; j < m; ++j)
-    if (!item_mask || item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
-                            hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr, cand_ptr, sizeof(int64_t) * ((size_t)n + 1),
-                            hipMemcpyHostToDevice, c->stream));
-  if (rows)
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
-                              c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  RankCandArgs a{};
-  a.X = c->emb[side];
-  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
-  a.Y = c->emb[1];
-  a.m = m;
-  a.Dp = c->Dp;
-  a.k = k;
-  a.cand_ptr = (const int64_t*)(c->d_rec + o_ptr);
-  a.cand = (const int32_t*)(c->d_rec + o_ids);
-  a.row_ptr = exclude ? c->rp[side] : nullptr;
-  a.col = exclude ? c->col[side] : nullptr;
-  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
-  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
-  a.out_items = (int32_t*)(c->d_rec + o_items);
-  a.out_scores = scores ? (float*)(c->d_rec + o_scores) : nullptr;
-  for (size_t b = 0; b + 1 < cuts.size(); ++b) {  // one timed launch group per row batch
-    a.r0 = cuts[b];
-    a.n = cuts[b + 1] - cuts[b];
-    a.cand_base = cand_ptr[a.r0];
-    const int64_t ids = cand_ptr[a.r0 + a.n] - a.cand_base;
-    if (ids > 0)
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ids, cand_items + a.cand_base, sizeof(int32_t) * ids,
-                                hipMemcpyHostToDevice, c->stream));
-    ScopedTimer t(c, "rank_candidates");
-    HIP_TRY(c, launch_rank_candidates(a, c->stream));
-    t.stop();
-    HIP_TRY(c, hipMemcpyAsync(items + a.r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
-                              hipMemcpyDeviceToHost, c->stream));
-    if (scores)
-      HIP_TRY(c, hipMemcpyAsync(scores + a.r0 * k, a.out_scores, sizeof(float) * a.n * k,
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // flops at the logical dim; bytes: one padded item row per candidate, the
-  // ids read, the lists written
-  add_work(c, "rank_candidates", 2.0 * (double)pairs * c->dim,
-           (double)pairs * c->Dp * 4.0 + (double)pairs * 4.0 + (double)n * k * 8.0, n);
-  return FRECSYS_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// splitmix64's finaliser and its increment: the generator of the sampled
-// negatives (include/frecsys_hip.h), uint64 arithmetic that wraps.
-inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-// What frecsys_rank_candidates_metrics and frecsys_sampled_metrics share.
-struct CandMetricsCall {
-  int32_t side;
-  const int64_t* rows;
-  int64_t n;
-  int32_t flags;
-  const uint8_t* item_mask;
-  MetricsRequest mt;
-  // caller lists (frecsys_rank_candidates_metrics) ...
-  const int64_t* cand_ptr;
-  const int32_t* cand_items;
-  // ... or sampled ones (cand_ptr == nullptr)
-  int32_t n_neg;
-  uint64_t seed;
-  int32_t* neg_count;
-  int32_t* negatives;
-};
-
-// The argument checks of both, before any device call: frecsys_rank_metrics'
-// and frecsys_rank_candidates' cases.  *k = max k_list.
-int cand_metrics_check(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q,
-                       int32_t* k) {
-  if (q.side != FRECSYS_SIDE_USER && q.side != FRECSYS_SIDE_EVAL)
-    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or EVAL");
-  if (q.flags & ~FRECSYS_REC_EXCLUDE_HISTORY)
-    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
-  if (q.n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (!q.mt.k_list || q.mt.nk < 1 || q.mt.nk > kMetricMaxCutoffs)
-    return fail(c, FRECSYS_ERR_INVALID,
-                w + "k_list must hold 1 to " + std::to_string(kMetricMaxCutoffs) + " cut-offs");
-  *k = 0;
-  for (int32_t j = 0; j < q.mt.nk; ++j) {
-    if (q.mt.k_list[j] < 1 || q.mt.k_list[j] > kMetricMaxK)
-      return fail(c, FRECSYS_ERR_INVALID, w + "cut-offs must be in [1, 1024]");
-    *k = std::max(*k, q.mt.k_list[j]);
-  }
-  if (!q.cand_ptr) {
-    if (q.n_neg < 0) return fail(c, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
-    if (q.n_neg > 0 && q.n > INT64_MAX / q.n_neg)
-      return fail(c, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
-  }
-  if (q.n == 0) return FRECSYS_OK;
-  if (!q.mt.recall || !q.mt.ndcg)
-    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
-  if ((q.flags & FRECSYS_REC_EXCLUDE_HISTORY) && !c->rp[q.side])
-    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
-  if (!c->emb[q.side] || !c->emb[1])
-    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
-  const int64_t ns = c->n[q.side], m = c->n[1];
-  if (q.rows) {
-    for (int64_t i = 0; i < q.n; ++i)
-      if (q.rows[i] < 0 || q.rows[i] >= ns)
-        return fail(c, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(q.rows[i]) + " out of range");
-  } else if (q.n > ns) {
-    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
-  }
-  if (m < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
-  int32_t mk = 0;
-  const std::string e =
-      metric_args_error(q.n, q.mt.gt_ptr, q.mt.gt_items, q.mt.k_list, q.mt.nk, m, &mk);
-  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
-  return FRECSYS_OK;
-}
-
-// Whole-pool rule of a row with pool size E among M maskable ids.
-inline bool whole_pool_row(int64_t n_neg, int64_t E, int64_t M) {
-  return 2 * n_neg > E || 64 * E < M;
-}
-
-// The device part of both: per row batch the candidate ids are uploaded
-// (caller lists) or written by the sampling kernels (sampled lists), then
-// rank_cand_kernel ranks them where they lie, rank_metrics_kernel reads the
-// lists where the ranking left them, and 2 nk floats per row come back.
-int cand_metrics_impl(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q, int32_t k) {
-  const bool sampled = q.cand_ptr == nullptr;
-  const bool exclude = (q.flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
-  const int64_t n = q.n, m = c->n[1];
-  const size_t nk = (size_t)q.mt.nk;
-  HIP_TRY(c, hipSetDevice(c->device));
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  const size_t budget = (size_t)ws_mb << 20;
-  const int64_t W = recommend_words(m);
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const bool bits = sampled || exclude;  // one bitmap per row of a batch
-  // per row of a batch: its outputs, its metric rows, its bitmap -- and its
-  // candidate ids.  Caller lists: batches are cut greedily in row order over
-  // all of it (frecsys_rank_candidates' scheme).  Sampled lists: the lengths
-  // are known only after the pool pass, so rows are cut into batches by the
-  // fixed part within half the budget, and each batch into sub-batches whose
-  // ids stay within the other half (at least one row each).
-  const size_t row_fixed = (size_t)k * 4 + nk * 8 + (bits ? (size_t)W * 4 : 0);
-  std::vector<int64_t> cuts{0};
-  int64_t max_rows = 0, max_ids = 0;
-  if (sampled) {
-    const int64_t nb =
-        std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)((budget / 2) / row_fixed)));
-    for (int64_t r0 = 0; r0 < n; r0 += nb) cuts.push_back(std::min(n, r0 + nb));
-    max_rows = nb;
-  } else {
-    for (int64_t r0 = 0; r0 < n;) {
-      size_t bytes = 0;
-      int64_t r1 = r0;
-      while (r1 < n) {
-        const size_t add = row_fixed + (size_t)(q.cand_ptr[r1 + 1] - q.cand_ptr[r1]) * 4;
-        if (r1 > r0 && bytes + add > budget) break;
-        bytes += add;
-        ++r1;
-      }
-      max_rows = std::max(max_rows, r1 - r0);
-      max_ids = std::max(max_ids, q.cand_ptr[r1] - q.cand_ptr[r0]);
-      cuts.push_back(r1);
-      r0 = r1;
-    }
-  }
-  // eligibility bits of the items, and the ascending list of the eligible ids
-  // when a mask leaves some out (the domain D of the draws)
-  std::vector<uint32_t> maskw((size_t)W, 0u);
-  std::vector<int32_t> dlist;
-  int64_t M = m;
-  for (int64_t j = 0; j < m; ++j)
-    if (!q.item_mask || q.item_mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
-  if (sampled && q.item_mask) {
-    for (int64_t j = 0; j < m; ++j)
-      if (q.item_mask[j]) dlist.push_back((int32_t)j);
-    M = (int64_t)dlist.size();
-    if (M == m) dlist.clear();
-  }
-  std::vector<int64_t> gt_sp;
-  std::vector<int32_t> gt_sg;
-  sorted_ground_truth(n, q.mt.gt_ptr, q.mt.gt_items, &gt_sp, &gt_sg);
-  const size_t o_ids = 0;
-  const size_t o_bitmap = up16(o_ids + (size_t)max_ids * 4);
-  const size_t o_items = up16(o_bitmap + (bits ? (size_t)max_rows * W * 4 : 0));
-  const size_t o_recall = up16(o_items + (size_t)max_rows * k * 4);
-  const size_t o_ndcg = up16(o_recall + (size_t)max_rows * nk * 4);
-  // outside the per-row budget: per call
-  const size_t o_mask = up16(o_ndcg + (size_t)max_rows * nk * 4);
-  const size_t o_ptr = up16(o_mask + (size_t)W * 4);
-  const size_t o_qrows = up16(o_ptr + ((size_t)n + 1) * 8);
-  const size_t o_gtptr = up16(o_qrows + (q.rows ? (size_t)n * 8 : 0));
-  const size_t o_gt = up16(o_gtptr + ((size_t)n + 1) * 8);
-  const size_t o_gain = up16(o_gt + gt_sg.size() * 4);
-  const size_t o_idcg = up16(o_gain + sizeof(double) * kMetricMaxK);
-  const size_t o_klist = up16(o_idcg + sizeof(double) * (kMetricMaxK + 1));
-  const size_t o_pool = up16(o_klist + nk * 4);
-  const size_t o_dlist = up16(o_pool + (sampled ? (size_t)n * 4 : 0));
-  const size_t total = o_dlist + dlist.size() * 4;
-  int rc = ensure(c, c->d_rec, total);
-  if (rc) return rc;
-  const MetricTables& tab = metric_tables();
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
-                            hipMemcpyHostToDevice, c->stream));
-  if (q.rows)
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, q.rows, sizeof(int64_t) * n,
-                              hipMemcpyHostToDevice, c->stream));
-  if (!sampled)
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr, q.cand_ptr, sizeof(int64_t) * ((size_t)n + 1),
-                              hipMemcpyHostToDevice, c->stream));
-  if (!dlist.empty())
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_dlist, dlist.data(), sizeof(int32_t) * dlist.size(),
-                              hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gtptr, gt_sp.data(), sizeof(int64_t) * ((size_t)n + 1),
-                            hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gt, gt_sg.data(), sizeof(int32_t) * gt_sg.size(),
-                            hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_gain, tab.gain, sizeof(tab.gain), hipMemcpyHostToDevice,
-                            c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_idcg, tab.idcg, sizeof(tab.idcg), hipMemcpyHostToDevice,
-                            c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_klist, q.mt.k_list, sizeof(int32_t) * nk,
-                            hipMemcpyHostToDevice, c->stream));
-  if (sampled)
-    HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  RankCandArgs a{};
-  a.X = c->emb[q.side];
-  a.qrows = q.rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
-  a.Y = c->emb[1];
-  a.m = m;
-  a.Dp = c->Dp;
-  a.k = k;
-  a.cand_ptr = (const int64_t*)(c->d_rec + o_ptr);
-  a.cand = (const int32_t*)(c->d_rec + o_ids);
-  a.row_ptr = exclude ? c->rp[q.side] : nullptr;
-  a.col = exclude ? c->col[q.side] : nullptr;
-  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
-  a.bitmap = exclude ? (uint32_t*)(c->d_rec + o_bitmap) : nullptr;
-  a.out_items = (int32_t*)(c->d_rec + o_items);
-  a.out_scores = nullptr;
-  RankMetricsArgs ma{};
-  ma.lists = a.out_items;
-  ma.k = k;
-  ma.gt_ptr = (const int64_t*)(c->d_rec + o_gtptr);
-  ma.gt = (const int32_t*)(c->d_rec + o_gt);
-  ma.k_list = (const int32_t*)(c->d_rec + o_klist);
-  ma.nk = (int)nk;
-  ma.gain = (const double*)(c->d_rec + o_gain);
-  ma.idcg = (const double*)(c->d_rec + o_idcg);
-  ma.recall = (float*)(c->d_rec + o_recall);
-  ma.ndcg = (float*)(c->d_rec + o_ndcg);
-  // ranks and scores rows [s0, s1) of the call from the ids at a.cand
-  auto rank_rows = [&](int64_t s0, int64_t s1, int64_t cand_base) -> int {
-    a.r0 = s0;
-    a.n = s1 - s0;
-    a.cand_base = cand_base;
-    {
-      ScopedTimer t(c, "rank_candidates");
-      HIP_TRY(c, launch_rank_candidates(a, c->stream));
-      t.stop();
-    }
-    ma.r0 = s0;
-    ma.n = a.n;
-    {
-      ScopedTimer t(c, "rank_metrics");
-      HIP_TRY(c, launch_rank_metrics(ma, c->stream));
-      t.stop();
-    }
-    HIP_TRY(c, hipMemcpyAsync(q.mt.recall + s0 * nk, ma.recall, sizeof(float) * a.n * nk,
-                              hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(q.mt.ndcg + s0 * nk, ma.ndcg, sizeof(float) * a.n * nk,
-                              hipMemcpyDeviceToHost, c->stream));
-    return FRECSYS_OK;
-  };
-  double pairs = 0.0;
-  if (!sampled) {
-    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
-      const int64_t s0 = cuts[b], s1 = cuts[b + 1];
-      const int64_t base = q.cand_ptr[s0], ids = q.cand_ptr[s1] - base;
-      if (ids > 0)
-        HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ids, q.cand_items + base, sizeof(int32_t) * ids,
-                                  hipMemcpyHostToDevice, c->stream));
-      if ((rc = rank_rows(s0, s1, base))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    pairs = (double)q.cand_ptr[n];
-  } else {
-    SampledArgs sa{};
-    sa.qrows = a.qrows;
-    sa.m = m;
-    sa.W = W;
-    sa.row_ptr = a.row_ptr;
-    sa.col = a.col;
-    sa.maskw = a.maskw;
-    sa.dlist = dlist.empty() ? nullptr : (const int32_t*)(c->d_rec + o_dlist);
-    sa.M = M;
-    sa.gt_ptr = ma.gt_ptr;
-    sa.gt = ma.gt;
-    sa.n_neg = q.n_neg;
-    sa.seed = q.seed;
-    sa.pool = (int32_t*)(c->d_rec + o_pool);
-    sa.cand_ptr = a.cand_ptr;
-    sa.fail = c->d_fail;
-    uint32_t* const bitmap = (uint32_t*)(c->d_rec + o_bitmap);
-    std::vector<int32_t> pool((size_t)max_rows), ids_host;
-    std::vector<int64_t> ptr((size_t)max_rows + 1);
-    for (size_t b = 0; b + 1 < cuts.size(); ++b) {
-      const int64_t b0 = cuts[b], b1 = cuts[b + 1], nb = b1 - b0;
-      sa.r0 = b0;
-      sa.n = nb;
-      sa.bitmap = bitmap;
-      {
-        ScopedTimer t(c, "sample_negatives");
-        HIP_TRY(c, launch_sampled_pool(sa, c->stream));
-        t.stop();
-      }
-      HIP_TRY(c, hipMemcpyAsync(pool.data(), sa.pool + b0, sizeof(int32_t) * nb,
-                                hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      // list i of the batch lies at ptr[i - b0] (ptr[0] = 0), on the device
-      // at entry i of the call's pointer array
-      ptr[0] = 0;
-      for (int64_t i = 0; i < nb; ++i) {
-        const int64_t E = pool[(size_t)i];
-        const int64_t cnt = whole_pool_row(q.n_neg, E, M) ? E : q.n_neg;
-        if (q.neg_count) q.neg_count[b0 + i] = (int32_t)cnt;
-        ptr[(size_t)i + 1] =
-            ptr[(size_t)i] + (gt_sp[(size_t)(b0 + i) + 1] - gt_sp[(size_t)(b0 + i)]) + cnt;
-      }
-      HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_ptr + (size_t)b0 * 8, ptr.data(),
-                                sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyHostToDevice,
-                                c->stream));
-      pairs += (double)ptr[(size_t)nb];
-      for (int64_t s0 = b0; s0 < b1;) {
-        int64_t s1 = s0 + 1;
-        const int64_t base = ptr[(size_t)(s0 - b0)];
-        while (s1 < b1 && (size_t)(ptr[(size_t)(s1 + 1 - b0)] - base) * 4 <= budget / 2) ++s1;
-        const int64_t ids = ptr[(size_t)(s1 - b0)] - base;
-        if ((rc = ensure(c, c->d_samp_ids, (size_t)std::max<int64_t>(ids, 1)))) return rc;
-        sa.r0 = s0;
-        sa.n = s1 - s0;
-        sa.bitmap = bitmap + (size_t)(s0 - b0) * W;
-        sa.cand_base = base;
-        sa.cand = c->d_samp_ids;
-        {
-          ScopedTimer t(c, "sample_negatives");
-          HIP_TRY(c, launch_sampled_fill(sa, c->stream));
-          t.stop();
-        }
-        if (q.negatives && q.n_neg > 0) {
-          ids_host.resize((size_t)ids);
-          HIP_TRY(c, hipMemcpyAsync(ids_host.data(), sa.cand, sizeof(int32_t) * ids,
-                                    hipMemcpyDeviceToHost, c->stream));
-        }
-        a.cand = sa.cand;
-        a.bitmap = exclude ? sa.bitmap : nullptr;  // refilled with the history alone
-        if ((rc = rank_rows(s0, s1, base))) return rc;
-        unsigned long long f = ~0ull;
-        HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (f != ~0ull)
-          return fail(c, FRECSYS_ERR_HIP,
-                      w + "the draws of query row " + std::to_string((int64_t)f - 1) +
-                          " reached the cap");
-        if (q.negatives && q.n_neg > 0)
-          for (int64_t i = s0; i < s1; ++i) {
-            int32_t* out = q.negatives + i * q.n_neg;
-            const int64_t g = gt_sp[(size_t)i + 1] - gt_sp[(size_t)i];
-            if (whole_pool_row(q.n_neg, pool[(size_t)(i - b0)], M))
-              std::fill(out, out + q.n_neg, -1);
-            else
-              std::memcpy(out, ids_host.data() + (ptr[(size_t)(i - b0)] - base) + g,
-                          sizeof(int32_t) * (size_t)q.n_neg);
-          }
-        s0 = s1;
-      }
-    }
-    // bytes: every row's bitmap zeroed, then read by the pool pass; the ids
-    // of the lists written
-    add_work(c, "sample_negatives", 0.0, (double)n * (double)W * 8.0 + pairs * 4.0, n);
-  }
-  // as frecsys_rank_candidates (the lists: ids only) and frecsys_rank_metrics
-  add_work(c, "rank_candidates", 2.0 * pairs * c->dim,
-           pairs * c->Dp * 4.0 + pairs * 4.0 + (double)n * k * 4.0, n);
-  add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
-           (double)n * k * 4.0 + (double)gt_sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
-               (double)n * (double)nk * 8.0,
-           n);
-  return FRECSYS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int frecsys_sample_negatives(int64_t n_items, const uint8_t* item_mask, const int64_t* row_ids,
-                             int64_t n_rows, const int64_t* hist_ptr, const int32_t* hist_items,
-                             const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
-                             uint64_t seed, int32_t* neg_count, int32_t* negatives) {
-  const std::string w = "sample_negatives: ";
-  if (n_items < 1 || n_items > INT32_MAX)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be in [1, 2^31)");
-  if (n_rows < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n_neg < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
-  if (n_neg > 0 && n_rows > INT64_MAX / n_neg)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
-  if (n_rows == 0) return FRECSYS_OK;
-  if (!neg_count) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null neg_count");
-  const int64_t n = n_rows, m = n_items;
-  if (row_ids)
-    for (int64_t i = 0; i < n; ++i)
-      if (row_ids[i] < 0)
-        return fail(nullptr, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(row_ids[i]) + " out of range");
-  if (!hist_ptr && hist_items)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "hist_items without hist_ptr");
-  if (hist_ptr) {
-    if (hist_ptr[0] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative hist_ptr");
-    for (int64_t i = 0; i < n; ++i)
-      if (hist_ptr[i + 1] < hist_ptr[i])
-        return fail(nullptr, FRECSYS_ERR_INVALID,
-                    w + "hist_ptr not monotone at row " + std::to_string(i));
-    if (hist_ptr[n] > hist_ptr[0] && !hist_items)
-      return fail(nullptr, FRECSYS_ERR_INVALID, w + "null hist_items");
-  }
-  {
-    const int32_t one = 1;
-    int32_t mk = 0;
-    const std::string e = metric_args_error(n, gt_ptr, gt_items, &one, 1, m, &mk);
-    if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  }
-  std::vector<int32_t> dlist;
-  int64_t M = m;
-  if (item_mask) {
-    for (int64_t j = 0; j < m; ++j)
-      if (item_mask[j]) dlist.push_back((int32_t)j);
-    M = (int64_t)dlist.size();
-  }
-  const uint64_t cap = kSampleCapBase + kSampleCapPerNeg * (uint64_t)n_neg;
-  std::atomic<int64_t> capped{-1};
-  // rows on the host thread pool; a task keeps one bitmap of the items and
-  // clears the bits of a row after it (blocked = history and ground truth,
-  // then the taken ids)
-  frecsys::ThreadPool::Get().ParallelFor(n, 64, [&](int64_t lo, int64_t hi) {
-    std::vector<uint64_t> bm((size_t)((m + 63) / 64), 0ull);
-    std::vector<int32_t> set;  // ids whose bit this row set
-    auto mark = [&](int64_t j) {
-      uint64_t& wd = bm[(size_t)(j >> 6)];
-      const uint64_t b = 1ull << (j & 63);
-      if (wd & b) return false;
-      wd |= b;
-      set.push_back((int32_t)j);
-      return true;
-    };
-    for (int64_t i = lo; i < hi; ++i) {
-      set.clear();
-      int64_t blocked = 0;  // distinct blocked ids that lie in D
-      if (hist_ptr)
-        for (int64_t p = hist_ptr[i]; p < hist_ptr[i + 1]; ++p) {
-          const int64_t j = hist_items[p];
-          if (j >= 0 && j < m && mark(j) && (!item_mask || item_mask[j])) ++blocked;
-        }
-      for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p) {
-        const int64_t j = gt_items[p];
-        if (mark(j) && (!item_mask || item_mask[j])) ++blocked;
-      }
-      const int64_t E = M - blocked;
-      int32_t* out = negatives ? negatives + i * n_neg : nullptr;
-      if (whole_pool_row(n_neg, E, M)) {
-        neg_count[i] = (int32_t)E;
-        if (out) std::fill(out, out + n_neg, -1);
-      } else {
-        neg_count[i] = n_neg;
-        const uint64_t r = (uint64_t)(row_ids ? row_ids[i] : i);
-        const uint64_t key = mix64(seed + kGolden * (r + 1));
-        int32_t have = 0;
-        for (uint64_t t = 0; have < n_neg; ++t) {
-          if (t >= cap) {
-            int64_t none = -1;
-            capped.compare_exchange_strong(none, i);
-            break;
-          }
-          const uint64_t x = mix64(key + kGolden * (t + 1));
-          const uint64_t idx = ((x >> 32) * (uint64_t)M) >> 32;
-          const int64_t j = item_mask ? dlist[(size_t)idx] : (int64_t)idx;
-          if (!mark(j)) continue;
-          if (out) out[have] = (int32_t)j;
-          ++have;
-        }
-      }
-      for (const int32_t j : set) bm[(size_t)(j >> 6)] &= ~(1ull << (j & 63));
-    }
-  });
-  if (capped.load() >= 0)
-    return fail(nullptr, FRECSYS_ERR_HIP,
-                w + "the draws of query row " + std::to_string(capped.load()) +
-                    " reached the cap");
-  return FRECSYS_OK;
-}
-
-int frecsys_rank_candidates_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows,
-                                    int64_t n_rows, const int64_t* cand_ptr,
-                                    const int32_t* cand_items, int32_t flags,
-                                    const uint8_t* item_mask, const int64_t* gt_ptr,
-                                    const int32_t* gt_items, const int32_t* k_list, int32_t nk,
-                                    float* recall, float* ndcg) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates_metrics: null context");
-  const std::string w = "rank_candidates_metrics: ";
-  if (!cand_ptr && n_rows != 0) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_ptr");
-  static const int64_t kNoLists[1] = {0};
-  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
-                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
-                          cand_ptr ? cand_ptr : kNoLists, cand_items, 0, 0, nullptr, nullptr};
-  int32_t k = 0;
-  int rc = cand_metrics_check(c, w, q, &k);
-  if (rc || n_rows == 0) return rc;
-  const int64_t n = n_rows, m = c->n[1];
-  if (cand_ptr[0] != 0) return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr[0] must be 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (cand_ptr[i + 1] < cand_ptr[i])
-      return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr not monotone at row " + std::to_string(i));
-  if (cand_ptr[n] > 0 && !cand_items) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_items");
-  for (int64_t p = 0; p < cand_ptr[n]; ++p)
-    if (cand_items[p] < 0 || cand_items[p] >= m)
-      return fail(c, FRECSYS_ERR_INVALID,
-                  w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
-  return cand_metrics_impl(c, w, q, k);
-}
-
-int frecsys_sampled_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
-                            int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
-                            const int32_t* gt_items, int32_t n_neg, uint64_t seed,
-                            const int32_t* k_list, int32_t nk, float* recall, float* ndcg,
-                            int32_t* neg_count, int32_t* negatives) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "sampled_metrics: null context");
-  const std::string w = "sampled_metrics: ";
-  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
-                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
-                          nullptr, nullptr, n_neg, seed, neg_count, negatives};
-  int32_t k = 0;
-  const int rc = cand_metrics_check(c, w, q, &k);
-  if (rc || n_rows == 0) return rc;
-  return cand_metrics_impl(c, w, q, k);
-}
-
-int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
-                    int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
-  if (!c) return fail(c, FRECSYS_ERR_INVALID, "similar: null context");
-  const std::string w = "similar: ";
-  if (side != FRECSYS_SIDE_USER && side != FRECSYS_SIDE_ITEM)
-    return fail(c, FRECSYS_ERR_INVALID, w + "side must be USER or ITEM");
-  if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
-  if (flags & ~(FRECSYS_SIM_COSINE | FRECSYS_SIM_KEEP_SELF))
-    return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
-  if (n_rows < 0 || (n_rows > 0 && !ids))
-    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
-  // (cannot happen today: a context allocates the USER and ITEM tables when it
-  // is created; kept for the day a side's table is allocated lazily)
-  if (!c->emb[side]) return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
-  const int64_t m = c->n[side], n = n_rows;
-  if (rows) {
-    for (int64_t i = 0; i < n; ++i)
-      if (rows[i] < 0 || rows[i] >= m)
-        return fail(c, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(rows[i]) + " out of range");
-  } else if (n > m) {
-    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
-  }
-  if (n == 0) return FRECSYS_OK;
-  const bool cosine = (flags & FRECSYS_SIM_COSINE) != 0;
-  const bool skip_self = !(flags & FRECSYS_SIM_KEEP_SELF);
-  HIP_TRY(c, hipSetDevice(c->device));
-  // frecsys_recommend's knobs and workspace scheme (no history bitmap: the one
-  // excluded id of a row is tested in the scan), read per call
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  int dev_cus = 256;
-  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const int max_splits = recommend_max_splits(k, m);
-  const int64_t row_blocks = (n + 63) / 64;
-  int splits = (int)std::min<int64_t>(max_splits, (2 * (int64_t)dev_cus + row_blocks - 1) / row_blocks);
-  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS"))
-    if (atoi(v) > 0) splits = std::min(max_splits, atoi(v));
-  splits = std::max(1, splits);
-  const int cap = recommend_cap(k);
-  const int64_t W = recommend_words(m);
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  // per row of a batch: candidates, counts, outputs
-  const size_t per_row = (size_t)splits * cap * 8 + (size_t)splits * 4 + (size_t)k * 8;
-  int64_t nb = std::max<int64_t>(1, (int64_t)(((size_t)ws_mb << 20) / per_row));
-  if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
-  nb = std::min(nb, n);
-  const size_t o_cand = 0;
-  const size_t o_counts = up16(o_cand + (size_t)nb * splits * cap * 8);
-  const size_t o_items = up16(o_counts + (size_t)nb * splits * 4);
-  const size_t o_scores = up16(o_items + (size_t)nb * k * 4);
-  const size_t o_mask = up16(o_scores + (size_t)nb * k * 4);
-  const size_t o_qrows = up16(o_mask + (size_t)W * 4);
-  const size_t total = o_qrows + (rows ? (size_t)n * 8 : 0);
-  int rc = ensure(c, c->d_rec, total);
-  if (rc) return rc;
-  // outside the per-row budget: one inverse norm per row of the side
-  if (cosine && (rc = ensure(c, c->d_sim_inv, (size_t)m))) return rc;
-  std::vector<uint32_t> maskw((size_t)W, 0u);
-  for (int64_t j = 0; j < m; ++j)
-    if (!mask || mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
-  HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_mask, maskw.data(), sizeof(uint32_t) * W,
-                            hipMemcpyHostToDevice, c->stream));
-  if (rows)
-    HIP_TRY(c, hipMemcpyAsync(c->d_rec + o_qrows, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice,
-                              c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (cosine) {  // per call: every solve rewrites the table
-    ScopedTimer t(c, "similar.norms");
-    HIP_TRY(c, launch_row_inv_norm(c->emb[side], m, c->Dp, c->d_sim_inv, c->stream));
-    t.stop();
-  }
-  RecommendArgs a{};
-  a.X = c->emb[side];
-  a.qrows = rows ? (const int64_t*)(c->d_rec + o_qrows) : nullptr;
-  a.Y = c->emb[side];
-  a.m = m;
-  a.Dp = c->Dp;
-  a.k = k;
-  a.splits = splits;
-  a.maskw = (const uint32_t*)(c->d_rec + o_mask);
-  a.cand = (unsigned long long*)(c->d_rec + o_cand);
-  a.counts = (int32_t*)(c->d_rec + o_counts);
-  a.out_items = (int32_t*)(c->d_rec + o_items);
-  a.out_scores = (float*)(c->d_rec + o_scores);
-  a.inv = cosine ? (const float*)c->d_sim_inv : nullptr;
-  a.skip_self = skip_self ? 1 : 0;
-  for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
-    a.r0 = r0;
-    a.n = std::min(nb, n - r0);
-    ScopedTimer t(c, "similar");
-    HIP_TRY(c, launch_recommend(a, c->stream));
-    t.stop();
-    HIP_TRY(c, hipMemcpyAsync(ids + r0 * k, a.out_items, sizeof(int32_t) * a.n * k,
-                              hipMemcpyDeviceToHost, c->stream));
-    if (scores)
-      HIP_TRY(c, hipMemcpyAsync(scores + r0 * k, a.out_scores, sizeof(float) * a.n * k,
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // scoring flops at the logical dim; bytes: the queries and the table read,
-  // the table once more by the norm pass, the lists written
-  const double dd = c->dim;
-  add_work(c, "similar", 2.0 * (double)n * (double)m * dd,
-           ((double)n + (cosine ? 2.0 : 1.0) * (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
-  return FRECSYS_OK;
-}
-
-int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
-                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
-                         float* ndcg) {
-  int32_t mk = 0;
-  const std::string e = metric_args_error(n, gt_ptr, gt_items, k_list, nk, -1, &mk);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: " + e);
-  if (list_k < mk)
-    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: list_k is below the largest cut-off");
-  if (n > 0 && (!lists || !recall || !ndcg))
-    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: bad arguments (null lists / outputs)");
-  const MetricTables& tab = metric_tables();
-  std::vector<int64_t> sp;
-  std::vector<int32_t> sg;
-  sorted_ground_truth(n, gt_ptr, gt_items, &sp, &sg);
-  std::vector<uint8_t> hit((size_t)mk);
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t* g0 = sg.data() + sp[(size_t)i];
-    const int32_t* g1 = sg.data() + sp[(size_t)i + 1];
-    const int64_t g = g1 - g0;
-    const int32_t* list = lists + i * list_k;
-    for (int32_t j = 0; j < mk; ++j)  // -1: an empty slot, never a hit
-      hit[(size_t)j] = list[j] >= 0 && std::binary_search(g0, g1, list[j]);
-    for (int32_t q = 0; q < nk; ++q) {
-      const int32_t kq = k_list[q];  // <= mk <= list_k
-      double hits = 0.0, dcg = 0.0;
-      for (int32_t j = 0; j < kq; ++j)
-        if (hit[(size_t)j]) {
-          hits += 1.0;
-          dcg += tab.gain[j];
-        }
-      const double norm = tab.idcg[std::min<int64_t>(kq, g)];
-      recall[i * nk + q] = (float)(hits / std::min<float>((float)kq, (float)g));
-      ndcg[i * nk + q] = (float)(dcg / norm);
-    }
-  }
-  return FRECSYS_OK;
-}
-
-int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int32_t na,
-                        float* out) {
-  if (n < 0 || na < 0 || (n > 0 && !values) || (na > 0 && (!alphas || !out)))
-    return fail(nullptr, FRECSYS_ERR_INVALID, "metric_cvar: bad arguments");
-  // EvaluationResult::cvar (evaluation.h:83-102), verbatim
-  std::vector<float> ms(values, values + n);
-  std::sort(ms.begin(), ms.end());
-  for (int32_t j = 0; j < na; ++j) out[j] = 0.0f;
-  int64_t counter = 0;
-  float acc = 0.0f;
-  for (int64_t i = 0; i < n; ++i) {
-    acc += ms[(size_t)i];
-    for (int64_t j = counter; j < na; ++j) {
-      const int pos = (int)((float)n * alphas[j]);
-      if (pos == i) {
-        out[counter] = acc / (float)(i + 1);
-        counter++;
-      }
-    }
-  }
   return FRECSYS_OK;
 }
 

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface between the C-ABI host code (capi.hip) and
+// kernels.h -- launch interface between the C-ABI host code (capi.hip, serve.hip) and
 // the gfx950 kernels (solve.hip, gramian.hip, loss.hip).  Internal header.
 #pragma once
 

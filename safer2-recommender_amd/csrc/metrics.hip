@@ -1,7 +1,7 @@
 // metrics.hip -- Recall@K and NDCG@K of ranked lists that are still in device
 // memory: the last step of frecsys_rank_metrics, run on rec_merge_kernel's
 // out_items right after the fused scoring + top-K of a row batch
-// (recommend.hip).  Restates frecsys_list_metrics (capi.hip; the reference's
+// (recommend.hip).  Restates frecsys_list_metrics (serve.hip; the reference's
 // RankMetrics, recommender.h:152-182) operation for operation, so that the two
 // agree bitwise:
 //

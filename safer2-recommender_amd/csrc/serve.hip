@@ -1,0 +1,1136 @@
+// serve.hip -- host side of the ranking and evaluation calls of the C-ABI
+// (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
+// frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
+// frecsys_sampled_metrics, frecsys_similar, and the host-only
+// frecsys_sample_negatives, frecsys_list_metrics, frecsys_metric_cvar.  No
+// kernels here: recommend.hip, similar.hip, rerank.hip, sampled.hip and
+// metrics.hip hold them (kernels.h).
+//
+// Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
+// aligned typed regions (Carver): first the regions of a row batch (candidate
+// slots or ids, bitmaps, the lists, the metric rows), then what the call needs
+// once (eligibility words, candidate pointers, query row ids, ground truth,
+// tables, cut-offs).  The budget (workspace_budget) bounds the batch regions
+// only.
+//
+// Batches.  A call runs its rows in batches, one timed launch group each, and
+// synchronises after each batch's copy-back:
+//   scan calls (recommend, rank_metrics, similar): budget / bytes per row,
+//     rounded down to whole 64-row blocks, with the item splits of scan_plan;
+//   pairs (score_pairs): budget / 16 B, at least 64;
+//   caller lists (rank_candidates, rank_candidates_metrics): rows in order
+//     while their fixed bytes and ids fit the budget (cut_by_candidates);
+//   sampled lists (sampled_metrics): rows by their fixed bytes within half the
+//     budget, then sub-batches whose ids fit the other half.
+// Rows are independent, so the batch size never changes a result.
+//
+// Checks.  Each entry point keeps its own order of checks and its own point
+// of return for zero rows; the checkers below are its pieces.
+#include <algorithm>
+#include <atomic>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../include/frecsys/parallel.h"
+#include "ctx.h"
+
+namespace {
+
+// The side (USER or `other`), k (nullptr: the call has none) and the flags.
+int check_query(frecsys_ctx* c, const std::string& w, int32_t side, int32_t other,
+                const int32_t* k, int32_t flags, int32_t known_flags) {
+  if (side != FRECSYS_SIDE_USER && side != other)
+    return fail(c, FRECSYS_ERR_INVALID,
+                w + "side must be USER or " + (other == FRECSYS_SIDE_EVAL ? "EVAL" : "ITEM"));
+  if (k && (*k < 1 || *k > 1024)) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
+  if (flags & ~known_flags) return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  return FRECSYS_OK;
+}
+
+// The context's state and the query rows: a CSR to exclude from, both tables,
+// row ids within the side (or no more rows than it has), and items to rank
+// when the table searched is not the side's own.
+int check_rows(frecsys_ctx* c, const std::string& w, int32_t side, int32_t table, bool exclude,
+               const int64_t* rows, int64_t n) {
+  if (exclude && !c->rp[side])
+    return fail(c, FRECSYS_ERR_INVALID, w + "exclude flag on a side with no CSR loaded");
+  if (!c->emb[side] || !c->emb[table])
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t ns = c->n[side];
+  if (rows) {
+    for (int64_t i = 0; i < n; ++i)
+      if (rows[i] < 0 || rows[i] >= ns)
+        return fail(c, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(rows[i]) + " out of range");
+  } else if (n > ns) {
+    return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
+  }
+  if (table != side && c->n[table] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
+  return FRECSYS_OK;
+}
+
+// A candidate CSR over n rows with ids in [0, m).
+int check_candidates(frecsys_ctx* c, const std::string& w, const int64_t* cand_ptr,
+                     const int32_t* cand_items, int64_t n, int64_t m) {
+  if (cand_ptr[0] != 0) return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr[0] must be 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (cand_ptr[i + 1] < cand_ptr[i])
+      return fail(c, FRECSYS_ERR_INVALID, w + "cand_ptr not monotone at row " + std::to_string(i));
+  if (cand_ptr[n] > 0 && !cand_items) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_items");
+  for (int64_t p = 0; p < cand_ptr[n]; ++p)
+    if (cand_items[p] < 0 || cand_items[p] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
+  return FRECSYS_OK;
+}
+
+// A cut-off list; *k = its largest, the length of the lists to rank.
+int check_cutoffs(frecsys_ctx* c, const std::string& w, const int32_t* k_list, int32_t nk,
+                  int32_t* k) {
+  if (!k_list || nk < 1 || nk > kMetricMaxCutoffs)
+    return fail(c, FRECSYS_ERR_INVALID,
+                w + "k_list must hold 1 to " + std::to_string(kMetricMaxCutoffs) + " cut-offs");
+  *k = 0;
+  for (int32_t q = 0; q < nk; ++q) {
+    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
+      return fail(c, FRECSYS_ERR_INVALID, w + "cut-offs must be in [1, 1024]");
+    *k = std::max(*k, k_list[q]);
+  }
+  return FRECSYS_OK;
+}
+
+// Bytes the regions of a row batch may take: 256 MiB, or the knob (read per call).
+size_t workspace_budget() {
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  return (size_t)ws_mb << 20;
+}
+
+// The carver of c->d_rec.  take<T>(count) hands out the next 16-byte aligned
+// region.  A call states its layout once, in a function that run() calls
+// twice: the first pass only sizes (the pointers it returns are offsets from
+// zero, not to be used), then the buffer grows to the total, and the second
+// pass returns the device pointers.
+class Carver {
+  uintptr_t base_ = 0;
+  size_t used_ = 0;
+
+ public:
+  template <typename T>
+  T* take(size_t count) {
+    const size_t at = (used_ + 15) & ~(size_t)15;
+    used_ = at + count * sizeof(T);
+    return reinterpret_cast<T*>(base_ + at);
+  }
+  // A region some calls do without: no bytes and nullptr then.
+  template <typename T>
+  T* take_if(bool wanted, size_t count) {
+    T* p = take<T>(wanted ? count : 0);
+    return wanted ? p : nullptr;
+  }
+  template <typename Layout>
+  static int run(frecsys_ctx* c, Layout layout) {
+    Carver cv;
+    layout(cv);
+    const int rc = ensure(c, c->d_rec, cv.used_);
+    if (rc) return rc;
+    cv.base_ = reinterpret_cast<uintptr_t>((char*)c->d_rec);
+    cv.used_ = 0;
+    layout(cv);
+    return FRECSYS_OK;
+  }
+};
+
+template <typename T>
+hipError_t to_device(frecsys_ctx* c, const T* dst, const T* src, size_t count) {
+  return hipMemcpyAsync(const_cast<T*>(dst), src, sizeof(T) * count, hipMemcpyHostToDevice,
+                        c->stream);
+}
+template <typename T>
+hipError_t to_host(frecsys_ctx* c, T* dst, const T* src, size_t count) {
+  return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream);
+}
+
+// Eligibility bits of the m items: the mask and id < m.
+std::vector<uint32_t> item_mask_words(int64_t m, const uint8_t* mask) {
+  std::vector<uint32_t> maskw((size_t)recommend_words(m), 0u);
+  for (int64_t j = 0; j < m; ++j)
+    if (!mask || mask[j]) maskw[(size_t)(j >> 5)] |= 1u << (j & 31);
+  return maskw;
+}
+
+// The scan of a table of m rows for n query rows: item splits -- about 2
+// workgroups per CU over the call's 64-row blocks, within what the merge keeps
+// in LDS, or what the splits knob says (read per call) -- and the rows of a
+// batch: per row its candidates, counts and outputs, and per_row_extra bytes.
+struct ScanPlan {
+  int splits, cap;
+  int64_t nb;
+};
+ScanPlan scan_plan(const frecsys_ctx* c, int k, int64_t m, int64_t n, size_t per_row_extra) {
+  int dev_cus = 256;
+  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int max_splits = recommend_max_splits(k, m);
+  const int64_t row_blocks = (n + 63) / 64;
+  int splits = (int)std::min<int64_t>(max_splits, (2 * (int64_t)dev_cus + row_blocks - 1) / row_blocks);
+  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS"))
+    if (atoi(v) > 0) splits = std::min(max_splits, atoi(v));
+  splits = std::max(1, splits);
+  const int cap = recommend_cap(k);
+  const size_t per_row =
+      (size_t)splits * cap * 8 + (size_t)splits * 4 + (size_t)k * 8 + per_row_extra;
+  int64_t nb = std::max<int64_t>(1, (int64_t)(workspace_budget() / per_row));
+  if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
+  return {splits, cap, std::min(nb, n)};
+}
+
+// The scan's arguments but the batch, and its regions: per row of a batch the
+// candidates, counts, history bits (when a CSR is excluded) and outputs, then
+// the eligibility words and the query row ids.
+RecommendArgs scan_args(const frecsys_ctx* c, int side, int table, int k, int splits,
+                        bool exclude) {
+  RecommendArgs a{};
+  a.X = c->emb[side];
+  a.Y = c->emb[table];
+  a.m = c->n[table];
+  a.Dp = c->Dp;
+  a.k = k;
+  a.splits = splits;
+  a.row_ptr = exclude ? c->rp[side] : nullptr;
+  a.col = exclude ? c->col[side] : nullptr;
+  return a;
+}
+void carve_scan(Carver& cv, RecommendArgs& a, const ScanPlan& p, bool rows, int64_t n) {
+  const size_t nb = (size_t)p.nb, W = (size_t)recommend_words(a.m);
+  a.cand = cv.take<unsigned long long>(nb * p.splits * p.cap);
+  a.counts = cv.take<int32_t>(nb * p.splits);
+  a.bitmap = cv.take_if<uint32_t>(a.row_ptr != nullptr, nb * W);
+  a.out_items = cv.take<int32_t>(nb * a.k);
+  a.out_scores = cv.take<float>(nb * a.k);
+  a.maskw = cv.take<uint32_t>(W);
+  a.qrows = cv.take_if<int64_t>(rows, (size_t)n);
+}
+
+// Rows cut greedily in row order into batches whose bytes -- row_fixed per
+// row and 4 per candidate id -- stay within the budget (at least one row
+// each); the workspace is sized for the largest.
+struct Cuts {
+  std::vector<int64_t> cuts{0};
+  int64_t max_rows = 0, max_ids = 0;
+};
+Cuts cut_by_candidates(const int64_t* ptr, int64_t n, size_t row_fixed, size_t budget) {
+  Cuts r;
+  for (int64_t r0 = 0; r0 < n;) {
+    size_t bytes = 0;
+    int64_t r1 = r0;
+    while (r1 < n) {
+      const size_t add = row_fixed + (size_t)(ptr[r1 + 1] - ptr[r1]) * 4;
+      if (r1 > r0 && bytes + add > budget) break;
+      bytes += add;
+      ++r1;
+    }
+    r.max_rows = std::max(r.max_rows, r1 - r0);
+    r.max_ids = std::max(r.max_ids, ptr[r1] - ptr[r0]);
+    r.cuts.push_back(r1);
+    r0 = r1;
+  }
+  return r;
+}
+
+// What the two candidate rankings share of RankCandArgs.
+RankCandArgs cand_args(const frecsys_ctx* c, int side, int k, bool exclude) {
+  RankCandArgs a{};
+  a.X = c->emb[side];
+  a.Y = c->emb[1];
+  a.m = c->n[1];
+  a.Dp = c->Dp;
+  a.k = k;
+  a.row_ptr = exclude ? c->rp[side] : nullptr;
+  a.col = exclude ? c->col[side] : nullptr;
+  return a;
+}
+
+// A batch's lists to the host, and the end of the batch.
+int fetch_lists(frecsys_ctx* c, int32_t* items, float* scores, int k, int64_t r0, int64_t cnt,
+                const int32_t* d_items, const float* d_scores) {
+  HIP_TRY(c, to_host(c, items + r0 * k, d_items, (size_t)(cnt * k)));
+  if (scores) HIP_TRY(c, to_host(c, scores + r0 * k, d_scores, (size_t)(cnt * k)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FRECSYS_OK;
+}
+
+// gain[j] = 1 / log2(j + 2) and its sequential prefix idcg[m] = gain[0] + ...
+// + gain[m-1] (idcg[0] = 0), in double with the host's std::log2: the terms
+// and the norm of RankMetrics (recommender.h:152-182) in its own order.
+struct MetricTables {
+  double gain[kMetricMaxK];
+  double idcg[kMetricMaxK + 1];
+};
+const MetricTables& metric_tables() {
+  static const MetricTables tab = [] {
+    MetricTables t;
+    t.idcg[0] = 0.0;
+    for (int j = 0; j < kMetricMaxK; ++j) {
+      t.gain[j] = 1.0 / std::log2(j + 2.0);
+      t.idcg[j + 1] = t.idcg[j] + t.gain[j];
+    }
+    return t;
+  }();
+  return tab;
+}
+
+// The argument checks frecsys_list_metrics and frecsys_rank_metrics share;
+// "" when fine.  n_items < 0: no upper bound on the ground-truth ids.
+std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
+                              const int32_t* k_list, int32_t nk, int64_t n_items,
+                              int32_t* max_k) {
+  if (n < 0 || !gt_ptr || !k_list) return "bad arguments (null gt_ptr / k_list, n < 0)";
+  if (nk < 1 || nk > kMetricMaxCutoffs)
+    return "nk must be in [1, " + std::to_string(kMetricMaxCutoffs) + "]";
+  int32_t mk = 0;
+  for (int32_t q = 0; q < nk; ++q) {
+    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
+      return "k_list[" + std::to_string(q) + "] must be in [1, " + std::to_string(kMetricMaxK) +
+             "]";
+    mk = std::max(mk, k_list[q]);
+  }
+  *max_k = mk;
+  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
+  for (int64_t i = 0; i < n; ++i) {
+    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
+    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
+  }
+  if (n > 0 && !gt_items) return "null gt_items";
+  for (int64_t p = 0; p < gt_ptr[n]; ++p)
+    if (gt_items[p] < 0 || (n_items >= 0 && gt_items[p] >= n_items))
+      return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
+  return "";
+}
+
+// The ground truth as sets: every row ascending and distinct.  Rows are sorted
+// in place in a copy (a row already strictly ascending is left alone), on host
+// threads over nnz-balanced row ranges when there is enough of it, then
+// closed up over the dropped repeats; the result does not depend on the
+// thread count.
+void sorted_ground_truth(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
+                         std::vector<int64_t>* sp, std::vector<int32_t>* sg) {
+  const int64_t total = gt_ptr[n];
+  sg->assign(gt_items, gt_items + total);
+  sp->assign((size_t)n + 1, 0);
+  std::vector<int64_t> cnt((size_t)n);
+  int32_t* base = sg->data();
+  auto work = [&](int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) {
+      int32_t* p = base + gt_ptr[i];
+      int32_t* e = base + gt_ptr[i + 1];
+      bool ascending = true;
+      for (int32_t* q = p + 1; q < e; ++q)
+        if (q[-1] >= q[0]) {
+          ascending = false;
+          break;
+        }
+      if (!ascending) {
+        std::sort(p, e);
+        e = std::unique(p, e);
+      }
+      cnt[(size_t)i] = e - p;
+    }
+  };
+  const int nt = total < (1 << 16)
+                     ? 1
+                     : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  if (nt == 1) {
+    work(0, n);
+  } else {
+    std::vector<int64_t> bounds((size_t)nt + 1);
+    partition_rows(n, gt_ptr, nt, bounds.data());
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, bounds[(size_t)t], bounds[(size_t)t + 1]);
+    for (auto& t : th) t.join();
+  }
+  int64_t w = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (w != gt_ptr[i]) std::memmove(base + w, base + gt_ptr[i], sizeof(int32_t) * (size_t)cnt[(size_t)i]);
+    w += cnt[(size_t)i];
+    (*sp)[(size_t)i + 1] = w;
+  }
+  sg->resize((size_t)w);
+}
+
+// What the metric calls add to a ranking call.
+struct MetricsRequest {
+  const int64_t* gt_ptr;
+  const int32_t* gt_items;
+  const int32_t* k_list;
+  int32_t nk;
+  float* recall;
+  float* ndcg;
+};
+
+// The metrics behind a ranking of n rows into lists of k: the lists stay on
+// the device, rank_metrics_kernel reads them there and 2 nk floats per row go
+// to the host.  The order of its steps is the caller's: sort() before or
+// during the first scan, the regions where the call's layout has them.
+struct MetricsStage {
+  const MetricsRequest& mt;
+  const int64_t n;
+  const size_t nk;
+  RankMetricsArgs ma{};
+  std::vector<int64_t> sp;  // the ground truth as sets (sorted_ground_truth)
+  std::vector<int32_t> sg;
+
+  MetricsStage(const MetricsRequest& r, int64_t rows, int k) : mt(r), n(rows), nk((size_t)r.nk) {
+    ma.k = k;
+    ma.nk = r.nk;
+  }
+  void sort() { sorted_ground_truth(n, mt.gt_ptr, mt.gt_items, &sp, &sg); }
+  // per call: the ground truth (room for gt_room ids), the tables, the cut-offs
+  void carve_inputs(Carver& cv, size_t gt_room) {
+    ma.gt_ptr = cv.take<int64_t>((size_t)n + 1);
+    ma.gt = cv.take<int32_t>(gt_room);
+    ma.gain = cv.take<double>(kMetricMaxK);
+    ma.idcg = cv.take<double>(kMetricMaxK + 1);
+    ma.k_list = cv.take<int32_t>(nk);
+  }
+  // per row of a batch: the two metric rows
+  void carve_rows(Carver& cv, int64_t nb) {
+    ma.recall = cv.take<float>((size_t)nb * nk);
+    ma.ndcg = cv.take<float>((size_t)nb * nk);
+  }
+  int upload(frecsys_ctx* c) {
+    const MetricTables& tab = metric_tables();
+    HIP_TRY(c, to_device(c, ma.gt_ptr, sp.data(), sp.size()));
+    HIP_TRY(c, to_device(c, ma.gt, sg.data(), sg.size()));
+    HIP_TRY(c, to_device(c, ma.gain, tab.gain, (size_t)kMetricMaxK));
+    HIP_TRY(c, to_device(c, ma.idcg, tab.idcg, (size_t)kMetricMaxK + 1));
+    HIP_TRY(c, to_device(c, ma.k_list, mt.k_list, nk));
+    return FRECSYS_OK;
+  }
+  // rows [r0, r0 + cnt) of the call, their lists at `lists`; the metric rows
+  // are on their way to the host when it returns (the caller synchronises)
+  int run(frecsys_ctx* c, const int32_t* lists, int64_t r0, int64_t cnt) {
+    ma.lists = lists;
+    ma.r0 = r0;
+    ma.n = cnt;
+    ScopedTimer t(c, "rank_metrics");
+    HIP_TRY(c, launch_rank_metrics(ma, c->stream));
+    t.stop();
+    HIP_TRY(c, to_host(c, mt.recall + r0 * nk, ma.recall, (size_t)cnt * nk));
+    HIP_TRY(c, to_host(c, mt.ndcg + r0 * nk, ma.ndcg, (size_t)cnt * nk));
+    return FRECSYS_OK;
+  }
+  // two double divisions per (row, cut-off); bytes: the lists and the ground
+  // truth read, the metric rows written
+  void book(frecsys_ctx* c) const {
+    add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
+             (double)n * ma.k * 4.0 + (double)sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
+                 (double)n * (double)nk * 8.0,
+             n);
+  }
+};
+
+// The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
+// to the host) and frecsys_rank_metrics (mt given: every batch's lists stay on
+// the device and the metric rows go to the host).  The scan is the same launch
+// with the same workspace layout in both; the ground truth, the tables and the
+// metric outputs lie behind it.
+int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
+                   int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
+                   int32_t* items, float* scores, const MetricsRequest* mt) {
+  const std::string w = std::string(what) + ": ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
+  if (rc) return rc;
+  if (n_rows < 0 || (n_rows > 0 && (mt ? (!mt->recall || !mt->ndcg) : !items)))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, exclude, rows, n_rows))) return rc;
+  const int64_t m = c->n[1], n = n_rows;
+  if (mt) {
+    int32_t mk = 0;
+    const std::string e = metric_args_error(n, mt->gt_ptr, mt->gt_items, mt->k_list, mt->nk, m, &mk);
+    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  }
+  if (n == 0) return FRECSYS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const MetricsRequest none{};
+  MetricsStage ms(mt ? *mt : none, n, k);
+  // per row of a batch beside the scan's own: history bits, the two metric rows
+  const ScanPlan p =
+      scan_plan(c, k, m, n, (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8);
+  c->rec_splits = p.splits;
+  RecommendArgs a = scan_args(c, side, FRECSYS_SIDE_ITEM, k, p.splits, exclude);
+  rc = Carver::run(c, [&](Carver& cv) {
+    carve_scan(cv, a, p, rows != nullptr, n);
+    if (mt) {
+      ms.carve_inputs(cv, (size_t)mt->gt_ptr[n]);  // room for every id; repeats are dropped
+      ms.carve_rows(cv, p.nb);
+    }
+  });
+  if (rc) return rc;
+  const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int64_t r0 = 0; r0 < n; r0 += p.nb) {  // one timed launch group per row batch
+    a.r0 = r0;
+    a.n = std::min(p.nb, n - r0);
+    ScopedTimer t(c, "recommend");
+    HIP_TRY(c, launch_recommend(a, c->stream));
+    if (mt && r0 == 0) {
+      // the ground truth is sorted on the host while the first batch is
+      // scanned, and uploaded behind it with the tables and the cut-offs
+      t.mark();
+      ms.sort();
+      if ((rc = ms.upload(c))) return rc;
+      t.finish();
+    } else {
+      t.stop();
+    }
+    if (mt) {
+      if ((rc = ms.run(c, a.out_items, r0, a.n))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if ((rc = fetch_lists(c, items, scores, k, r0, a.n, a.out_items, a.out_scores))) {
+      return rc;
+    }
+  }
+  // scoring flops at the logical dim; bytes: both tables read once, lists written
+  const double dd = c->dim;
+  add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
+           ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  if (mt) ms.book(c);
+  return FRECSYS_OK;
+}
+
+// splitmix64's finaliser and its increment: the generator of the sampled
+// negatives (include/frecsys_hip.h), uint64 arithmetic that wraps.
+inline uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+
+// What frecsys_rank_candidates_metrics and frecsys_sampled_metrics share.
+struct CandMetricsCall {
+  int32_t side;
+  const int64_t* rows;
+  int64_t n;
+  int32_t flags;
+  const uint8_t* item_mask;
+  MetricsRequest mt;
+  // caller lists (frecsys_rank_candidates_metrics) ...
+  const int64_t* cand_ptr;
+  const int32_t* cand_items;
+  // ... or sampled ones (cand_ptr == nullptr)
+  int32_t n_neg;
+  uint64_t seed;
+  int32_t* neg_count;
+  int32_t* negatives;
+};
+
+// The argument checks of both, before any device call: frecsys_rank_metrics'
+// and frecsys_rank_candidates' cases.  *k = max k_list.
+int cand_metrics_check(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q,
+                       int32_t* k) {
+  int rc = check_query(c, w, q.side, FRECSYS_SIDE_EVAL, nullptr, q.flags,
+                       FRECSYS_REC_EXCLUDE_HISTORY);
+  if (rc) return rc;
+  if (q.n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if ((rc = check_cutoffs(c, w, q.mt.k_list, q.mt.nk, k))) return rc;
+  if (!q.cand_ptr) {
+    if (q.n_neg < 0) return fail(c, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
+    if (q.n_neg > 0 && q.n > INT64_MAX / q.n_neg)
+      return fail(c, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
+  }
+  if (q.n == 0) return FRECSYS_OK;
+  if (!q.mt.recall || !q.mt.ndcg)
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  if ((rc = check_rows(c, w, q.side, FRECSYS_SIDE_ITEM,
+                       (q.flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0, q.rows, q.n)))
+    return rc;
+  int32_t mk = 0;
+  const std::string e =
+      metric_args_error(q.n, q.mt.gt_ptr, q.mt.gt_items, q.mt.k_list, q.mt.nk, c->n[1], &mk);
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  return FRECSYS_OK;
+}
+
+// Whole-pool rule of a row with pool size E among M maskable ids.
+inline bool whole_pool_row(int64_t n_neg, int64_t E, int64_t M) {
+  return 2 * n_neg > E || 64 * E < M;
+}
+
+// The device part of both: per row batch the candidate ids are uploaded
+// (caller lists) or written by the sampling kernels (sampled lists), then
+// rank_cand_kernel ranks them where they lie and the metrics stage reads the
+// lists where the ranking left them.
+int cand_metrics_impl(frecsys_ctx* c, const std::string& w, const CandMetricsCall& q, int32_t k) {
+  const bool sampled = q.cand_ptr == nullptr;
+  const bool exclude = (q.flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  const int64_t n = q.n, m = c->n[1];
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t budget = workspace_budget();
+  const int64_t W = recommend_words(m);
+  const bool bits = sampled || exclude;  // one bitmap per row of a batch
+  MetricsStage ms(q.mt, n, k);
+  // per row of a batch: its outputs, its metric rows, its bitmap -- and its
+  // candidate ids.  Sampled lists: the lengths are known only after the pool
+  // pass, so rows are cut into batches by the fixed part within half the
+  // budget, and each batch into sub-batches whose ids stay within the other
+  // half (at least one row each).
+  const size_t row_fixed = (size_t)k * 4 + ms.nk * 8 + (bits ? (size_t)W * 4 : 0);
+  Cuts ct;
+  if (sampled) {
+    const int64_t nb =
+        std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)((budget / 2) / row_fixed)));
+    for (int64_t r0 = 0; r0 < n; r0 += nb) ct.cuts.push_back(std::min(n, r0 + nb));
+    ct.max_rows = nb;
+  } else {
+    ct = cut_by_candidates(q.cand_ptr, n, row_fixed, budget);
+  }
+  // eligibility bits of the items, and the ascending list of the eligible ids
+  // when a mask leaves some out (the domain D of the draws)
+  const std::vector<uint32_t> maskw = item_mask_words(m, q.item_mask);
+  std::vector<int32_t> dlist;
+  int64_t M = m;
+  if (sampled && q.item_mask) {
+    for (int64_t j = 0; j < m; ++j)
+      if (q.item_mask[j]) dlist.push_back((int32_t)j);
+    M = (int64_t)dlist.size();
+    if (M == m) dlist.clear();
+  }
+  ms.sort();
+  RankCandArgs a = cand_args(c, q.side, k, exclude);
+  SampledArgs sa{};
+  uint32_t* bitmap = nullptr;
+  int rc = Carver::run(c, [&](Carver& cv) {
+    a.cand = cv.take<int32_t>((size_t)ct.max_ids);
+    bitmap = cv.take_if<uint32_t>(bits, (size_t)ct.max_rows * W);
+    a.out_items = cv.take<int32_t>((size_t)ct.max_rows * k);
+    ms.carve_rows(cv, ct.max_rows);
+    // outside the per-row budget: per call
+    a.maskw = cv.take<uint32_t>((size_t)W);
+    a.cand_ptr = cv.take<int64_t>((size_t)n + 1);
+    a.qrows = cv.take_if<int64_t>(q.rows != nullptr, (size_t)n);
+    ms.carve_inputs(cv, ms.sg.size());
+    sa.pool = cv.take<int32_t>(sampled ? (size_t)n : 0);
+    sa.dlist = cv.take_if<int32_t>(!dlist.empty(), dlist.size());
+  });
+  if (rc) return rc;
+  a.bitmap = exclude ? bitmap : nullptr;
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  if (q.rows) HIP_TRY(c, to_device(c, a.qrows, q.rows, (size_t)n));
+  if (!sampled) HIP_TRY(c, to_device(c, a.cand_ptr, q.cand_ptr, (size_t)n + 1));
+  if (!dlist.empty()) HIP_TRY(c, to_device(c, sa.dlist, dlist.data(), dlist.size()));
+  if ((rc = ms.upload(c))) return rc;
+  if (sampled)
+    HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // ranks and scores rows [s0, s1) of the call from the ids at a.cand
+  auto rank_rows = [&](int64_t s0, int64_t s1, int64_t cand_base) -> int {
+    a.r0 = s0;
+    a.n = s1 - s0;
+    a.cand_base = cand_base;
+    {
+      ScopedTimer t(c, "rank_candidates");
+      HIP_TRY(c, launch_rank_candidates(a, c->stream));
+      t.stop();
+    }
+    return ms.run(c, a.out_items, s0, a.n);
+  };
+  double pairs = 0.0;
+  if (!sampled) {
+    for (size_t b = 0; b + 1 < ct.cuts.size(); ++b) {
+      const int64_t s0 = ct.cuts[b], s1 = ct.cuts[b + 1];
+      const int64_t base = q.cand_ptr[s0], ids = q.cand_ptr[s1] - base;
+      if (ids > 0) HIP_TRY(c, to_device(c, a.cand, q.cand_items + base, (size_t)ids));
+      if ((rc = rank_rows(s0, s1, base))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    pairs = (double)q.cand_ptr[n];
+  } else {
+    sa.qrows = a.qrows;
+    sa.m = m;
+    sa.W = W;
+    sa.row_ptr = a.row_ptr;
+    sa.col = a.col;
+    sa.maskw = a.maskw;
+    sa.M = M;
+    sa.gt_ptr = ms.ma.gt_ptr;
+    sa.gt = ms.ma.gt;
+    sa.n_neg = q.n_neg;
+    sa.seed = q.seed;
+    sa.cand_ptr = a.cand_ptr;
+    sa.fail = c->d_fail;
+    const std::vector<int64_t>& gt_sp = ms.sp;
+    std::vector<int32_t> pool((size_t)ct.max_rows), ids_host;
+    std::vector<int64_t> ptr((size_t)ct.max_rows + 1);
+    for (size_t b = 0; b + 1 < ct.cuts.size(); ++b) {
+      const int64_t b0 = ct.cuts[b], b1 = ct.cuts[b + 1], nb = b1 - b0;
+      sa.r0 = b0;
+      sa.n = nb;
+      sa.bitmap = bitmap;
+      {
+        ScopedTimer t(c, "sample_negatives");
+        HIP_TRY(c, launch_sampled_pool(sa, c->stream));
+        t.stop();
+      }
+      HIP_TRY(c, to_host(c, pool.data(), sa.pool + b0, (size_t)nb));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      // list i of the batch lies at ptr[i - b0] (ptr[0] = 0), on the device
+      // at entry i of the call's pointer array
+      ptr[0] = 0;
+      for (int64_t i = 0; i < nb; ++i) {
+        const int64_t E = pool[(size_t)i];
+        const int64_t cnt = whole_pool_row(q.n_neg, E, M) ? E : q.n_neg;
+        if (q.neg_count) q.neg_count[b0 + i] = (int32_t)cnt;
+        ptr[(size_t)i + 1] =
+            ptr[(size_t)i] + (gt_sp[(size_t)(b0 + i) + 1] - gt_sp[(size_t)(b0 + i)]) + cnt;
+      }
+      HIP_TRY(c, to_device(c, a.cand_ptr + b0, ptr.data(), (size_t)nb + 1));
+      pairs += (double)ptr[(size_t)nb];
+      for (int64_t s0 = b0; s0 < b1;) {
+        int64_t s1 = s0 + 1;
+        const int64_t base = ptr[(size_t)(s0 - b0)];
+        while (s1 < b1 && (size_t)(ptr[(size_t)(s1 + 1 - b0)] - base) * 4 <= budget / 2) ++s1;
+        const int64_t ids = ptr[(size_t)(s1 - b0)] - base;
+        if ((rc = ensure(c, c->d_samp_ids, (size_t)std::max<int64_t>(ids, 1)))) return rc;
+        sa.r0 = s0;
+        sa.n = s1 - s0;
+        sa.bitmap = bitmap + (size_t)(s0 - b0) * W;
+        sa.cand_base = base;
+        sa.cand = c->d_samp_ids;
+        {
+          ScopedTimer t(c, "sample_negatives");
+          HIP_TRY(c, launch_sampled_fill(sa, c->stream));
+          t.stop();
+        }
+        if (q.negatives && q.n_neg > 0) {
+          ids_host.resize((size_t)ids);
+          HIP_TRY(c, to_host(c, ids_host.data(), sa.cand, (size_t)ids));
+        }
+        a.cand = sa.cand;
+        a.bitmap = exclude ? sa.bitmap : nullptr;  // refilled with the history alone
+        if ((rc = rank_rows(s0, s1, base))) return rc;
+        unsigned long long f = ~0ull;
+        HIP_TRY(c, hipMemcpyAsync(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (f != ~0ull)
+          return fail(c, FRECSYS_ERR_HIP,
+                      w + "the draws of query row " + std::to_string((int64_t)f - 1) +
+                          " reached the cap");
+        if (q.negatives && q.n_neg > 0)
+          for (int64_t i = s0; i < s1; ++i) {
+            int32_t* out = q.negatives + i * q.n_neg;
+            const int64_t g = gt_sp[(size_t)i + 1] - gt_sp[(size_t)i];
+            if (whole_pool_row(q.n_neg, pool[(size_t)(i - b0)], M))
+              std::fill(out, out + q.n_neg, -1);
+            else
+              std::memcpy(out, ids_host.data() + (ptr[(size_t)(i - b0)] - base) + g,
+                          sizeof(int32_t) * (size_t)q.n_neg);
+          }
+        s0 = s1;
+      }
+    }
+    // bytes: every row's bitmap zeroed, then read by the pool pass; the ids
+    // of the lists written
+    add_work(c, "sample_negatives", 0.0, (double)n * (double)W * 8.0 + pairs * 4.0, n);
+  }
+  // as frecsys_rank_candidates (the lists: ids only) and frecsys_rank_metrics
+  add_work(c, "rank_candidates", 2.0 * pairs * c->dim,
+           pairs * c->Dp * 4.0 + pairs * 4.0 + (double)n * k * 4.0, n);
+  ms.book(c);
+  return FRECSYS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
+                      int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
+  return recommend_impl(c, "recommend", side, rows, n_rows, k, flags, item_mask, items, scores,
+                        nullptr);
+}
+
+int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                         int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
+                         float* ndcg) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: null context");
+  int32_t k = 0;  // the list length is the largest cut-off
+  const int rc = check_cutoffs(c, "rank_metrics: ", k_list, nk, &k);
+  if (rc) return rc;
+  const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
+  return recommend_impl(c, "rank_metrics", side, rows, n_rows, k, flags, item_mask, nullptr, nullptr,
+                        &mt);
+}
+
+int frecsys_score_pairs(frecsys_ctx* c, int32_t side, const int64_t* rows, const int32_t* items,
+                        int64_t n_pairs, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "score_pairs: null context");
+  const std::string w = "score_pairs: ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, nullptr, 0, 0);
+  if (rc) return rc;
+  if (n_pairs < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative pair count");
+  if (n_pairs == 0) return FRECSYS_OK;
+  if (!rows || !items || !scores) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->emb[side] || !c->emb[1])
+    return fail(c, FRECSYS_ERR_INVALID, w + "side has no embeddings yet");
+  const int64_t ns = c->n[side], m = c->n[1], n = n_pairs;
+  for (int64_t i = 0; i < n; ++i) {  // pair by pair: the first bad pair is the one reported
+    if (rows[i] < 0 || rows[i] >= ns)
+      return fail(c, FRECSYS_ERR_INVALID, w + "row id " + std::to_string(rows[i]) + " out of range");
+    if (items[i] < 0 || items[i] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "item id " + std::to_string(items[i]) + " out of range");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // per pair: row id, item id, score
+  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(64, (int64_t)(workspace_budget() / 16)));
+  ScorePairsArgs a{};
+  a.X = c->emb[side];
+  a.Y = c->emb[1];
+  a.Dp = c->Dp;
+  rc = Carver::run(c, [&](Carver& cv) {
+    a.rows = cv.take<int64_t>((size_t)nb);
+    a.items = cv.take<int32_t>((size_t)nb);
+    a.out = cv.take<float>((size_t)nb);
+  });
+  if (rc) return rc;
+  for (int64_t p0 = 0; p0 < n; p0 += nb) {  // one timed launch per pair batch
+    a.n = std::min(nb, n - p0);
+    HIP_TRY(c, to_device(c, a.rows, rows + p0, (size_t)a.n));
+    HIP_TRY(c, to_device(c, a.items, items + p0, (size_t)a.n));
+    ScopedTimer t(c, "score_pairs");
+    HIP_TRY(c, launch_score_pairs(a, c->stream));
+    t.stop();
+    HIP_TRY(c, to_host(c, scores + p0, a.out, (size_t)a.n));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // flops at the logical dim; bytes: one padded item row per pair, ids, scores
+  add_work(c, "score_pairs", 2.0 * (double)n * c->dim,
+           (double)n * c->Dp * 4.0 + (double)n * 12.0 + (double)n * 4.0, n);
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                            const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                            int32_t flags, const uint8_t* item_mask, int32_t* items,
+                            float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates: null context");
+  const std::string w = "rank_candidates: ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
+  if (rc) return rc;
+  if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n_rows == 0) return FRECSYS_OK;
+  if (!cand_ptr || !items) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  const int64_t m = c->n[1], n = n_rows;
+  if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, exclude, rows, n))) return rc;
+  if ((rc = check_candidates(c, w, cand_ptr, cand_items, n, m))) return rc;
+  const int64_t pairs = cand_ptr[n];
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int64_t W = recommend_words(m);
+  // per row of a batch: its candidate ids, its outputs, its history bits
+  const Cuts ct = cut_by_candidates(cand_ptr, n, (size_t)k * 8 + (exclude ? (size_t)W * 4 : 0),
+                                    workspace_budget());
+  RankCandArgs a = cand_args(c, side, k, exclude);
+  rc = Carver::run(c, [&](Carver& cv) {
+    a.cand = cv.take<int32_t>((size_t)ct.max_ids);
+    a.bitmap = cv.take_if<uint32_t>(exclude, (size_t)ct.max_rows * W);
+    a.out_items = cv.take<int32_t>((size_t)ct.max_rows * k);
+    a.out_scores = cv.take<float>((size_t)ct.max_rows * k);
+    a.maskw = cv.take<uint32_t>((size_t)W);
+    a.cand_ptr = cv.take<int64_t>((size_t)n + 1);
+    a.qrows = cv.take_if<int64_t>(rows != nullptr, (size_t)n);
+  });
+  if (rc) return rc;
+  if (!scores) a.out_scores = nullptr;
+  const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  HIP_TRY(c, to_device(c, a.cand_ptr, cand_ptr, (size_t)n + 1));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b + 1 < ct.cuts.size(); ++b) {  // one timed launch group per row batch
+    a.r0 = ct.cuts[b];
+    a.n = ct.cuts[b + 1] - ct.cuts[b];
+    a.cand_base = cand_ptr[a.r0];
+    const int64_t ids = cand_ptr[a.r0 + a.n] - a.cand_base;
+    if (ids > 0) HIP_TRY(c, to_device(c, a.cand, cand_items + a.cand_base, (size_t)ids));
+    ScopedTimer t(c, "rank_candidates");
+    HIP_TRY(c, launch_rank_candidates(a, c->stream));
+    t.stop();
+    if ((rc = fetch_lists(c, items, scores, k, a.r0, a.n, a.out_items, a.out_scores))) return rc;
+  }
+  // flops at the logical dim; bytes: one padded item row per candidate, the
+  // ids read, the lists written
+  add_work(c, "rank_candidates", 2.0 * (double)pairs * c->dim,
+           (double)pairs * c->Dp * 4.0 + (double)pairs * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
+int frecsys_sample_negatives(int64_t n_items, const uint8_t* item_mask, const int64_t* row_ids,
+                             int64_t n_rows, const int64_t* hist_ptr, const int32_t* hist_items,
+                             const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
+                             uint64_t seed, int32_t* neg_count, int32_t* negatives) {
+  const std::string w = "sample_negatives: ";
+  if (n_items < 1 || n_items > INT32_MAX)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be in [1, 2^31)");
+  if (n_rows < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n_neg < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
+  if (n_neg > 0 && n_rows > INT64_MAX / n_neg)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
+  if (n_rows == 0) return FRECSYS_OK;
+  if (!neg_count) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null neg_count");
+  const int64_t n = n_rows, m = n_items;
+  if (row_ids)
+    for (int64_t i = 0; i < n; ++i)
+      if (row_ids[i] < 0)
+        return fail(nullptr, FRECSYS_ERR_INVALID,
+                    w + "row id " + std::to_string(row_ids[i]) + " out of range");
+  if (!hist_ptr && hist_items)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "hist_items without hist_ptr");
+  if (hist_ptr) {
+    if (hist_ptr[0] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative hist_ptr");
+    for (int64_t i = 0; i < n; ++i)
+      if (hist_ptr[i + 1] < hist_ptr[i])
+        return fail(nullptr, FRECSYS_ERR_INVALID,
+                    w + "hist_ptr not monotone at row " + std::to_string(i));
+    if (hist_ptr[n] > hist_ptr[0] && !hist_items)
+      return fail(nullptr, FRECSYS_ERR_INVALID, w + "null hist_items");
+  }
+  {
+    const int32_t one = 1;
+    int32_t mk = 0;
+    const std::string e = metric_args_error(n, gt_ptr, gt_items, &one, 1, m, &mk);
+    if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  }
+  std::vector<int32_t> dlist;
+  int64_t M = m;
+  if (item_mask) {
+    for (int64_t j = 0; j < m; ++j)
+      if (item_mask[j]) dlist.push_back((int32_t)j);
+    M = (int64_t)dlist.size();
+  }
+  const uint64_t cap = kSampleCapBase + kSampleCapPerNeg * (uint64_t)n_neg;
+  std::atomic<int64_t> capped{-1};
+  // rows on the host thread pool; a task keeps one bitmap of the items and
+  // clears the bits of a row after it (blocked = history and ground truth,
+  // then the taken ids)
+  frecsys::ThreadPool::Get().ParallelFor(n, 64, [&](int64_t lo, int64_t hi) {
+    std::vector<uint64_t> bm((size_t)((m + 63) / 64), 0ull);
+    std::vector<int32_t> set;  // ids whose bit this row set
+    auto mark = [&](int64_t j) {
+      uint64_t& wd = bm[(size_t)(j >> 6)];
+      const uint64_t b = 1ull << (j & 63);
+      if (wd & b) return false;
+      wd |= b;
+      set.push_back((int32_t)j);
+      return true;
+    };
+    for (int64_t i = lo; i < hi; ++i) {
+      set.clear();
+      int64_t blocked = 0;  // distinct blocked ids that lie in D
+      if (hist_ptr)
+        for (int64_t p = hist_ptr[i]; p < hist_ptr[i + 1]; ++p) {
+          const int64_t j = hist_items[p];
+          if (j >= 0 && j < m && mark(j) && (!item_mask || item_mask[j])) ++blocked;
+        }
+      for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p) {
+        const int64_t j = gt_items[p];
+        if (mark(j) && (!item_mask || item_mask[j])) ++blocked;
+      }
+      const int64_t E = M - blocked;
+      int32_t* out = negatives ? negatives + i * n_neg : nullptr;
+      if (whole_pool_row(n_neg, E, M)) {
+        neg_count[i] = (int32_t)E;
+        if (out) std::fill(out, out + n_neg, -1);
+      } else {
+        neg_count[i] = n_neg;
+        const uint64_t r = (uint64_t)(row_ids ? row_ids[i] : i);
+        const uint64_t key = mix64(seed + kGolden * (r + 1));
+        int32_t have = 0;
+        for (uint64_t t = 0; have < n_neg; ++t) {
+          if (t >= cap) {
+            int64_t none = -1;
+            capped.compare_exchange_strong(none, i);
+            break;
+          }
+          const uint64_t x = mix64(key + kGolden * (t + 1));
+          const uint64_t idx = ((x >> 32) * (uint64_t)M) >> 32;
+          const int64_t j = item_mask ? dlist[(size_t)idx] : (int64_t)idx;
+          if (!mark(j)) continue;
+          if (out) out[have] = (int32_t)j;
+          ++have;
+        }
+      }
+      for (const int32_t j : set) bm[(size_t)(j >> 6)] &= ~(1ull << (j & 63));
+    }
+  });
+  if (capped.load() >= 0)
+    return fail(nullptr, FRECSYS_ERR_HIP,
+                w + "the draws of query row " + std::to_string(capped.load()) +
+                    " reached the cap");
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_candidates_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows,
+                                    int64_t n_rows, const int64_t* cand_ptr,
+                                    const int32_t* cand_items, int32_t flags,
+                                    const uint8_t* item_mask, const int64_t* gt_ptr,
+                                    const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                    float* recall, float* ndcg) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_candidates_metrics: null context");
+  const std::string w = "rank_candidates_metrics: ";
+  if (!cand_ptr && n_rows != 0) return fail(c, FRECSYS_ERR_INVALID, w + "null cand_ptr");
+  static const int64_t kNoLists[1] = {0};
+  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
+                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
+                          cand_ptr ? cand_ptr : kNoLists, cand_items, 0, 0, nullptr, nullptr};
+  int32_t k = 0;
+  int rc = cand_metrics_check(c, w, q, &k);
+  if (rc || n_rows == 0) return rc;
+  if ((rc = check_candidates(c, w, cand_ptr, cand_items, n_rows, c->n[1]))) return rc;
+  return cand_metrics_impl(c, w, q, k);
+}
+
+int frecsys_sampled_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                            int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                            const int32_t* gt_items, int32_t n_neg, uint64_t seed,
+                            const int32_t* k_list, int32_t nk, float* recall, float* ndcg,
+                            int32_t* neg_count, int32_t* negatives) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "sampled_metrics: null context");
+  const std::string w = "sampled_metrics: ";
+  const CandMetricsCall q{side, rows, n_rows, flags, item_mask,
+                          MetricsRequest{gt_ptr, gt_items, k_list, nk, recall, ndcg},
+                          nullptr, nullptr, n_neg, seed, neg_count, negatives};
+  int32_t k = 0;
+  const int rc = cand_metrics_check(c, w, q, &k);
+  if (rc || n_rows == 0) return rc;
+  return cand_metrics_impl(c, w, q, k);
+}
+
+int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
+                    int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "similar: null context");
+  const std::string w = "similar: ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_ITEM, &k, flags,
+                       FRECSYS_SIM_COSINE | FRECSYS_SIM_KEEP_SELF);
+  if (rc) return rc;
+  if (n_rows < 0 || (n_rows > 0 && !ids))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  // ("no embeddings" cannot happen today: a context allocates the USER and
+  // ITEM tables when it is created; kept for the day a table is allocated
+  // lazily)
+  if ((rc = check_rows(c, w, side, side, false, rows, n_rows))) return rc;
+  const int64_t m = c->n[side], n = n_rows;
+  if (n == 0) return FRECSYS_OK;
+  const bool cosine = (flags & FRECSYS_SIM_COSINE) != 0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // frecsys_recommend's scan of the side's own table (no history bitmap: the
+  // one excluded id of a row is tested in the scan)
+  const ScanPlan p = scan_plan(c, k, m, n, 0);
+  RecommendArgs a = scan_args(c, side, side, k, p.splits, false);
+  if ((rc = Carver::run(c, [&](Carver& cv) { carve_scan(cv, a, p, rows != nullptr, n); })))
+    return rc;
+  // outside the per-row budget: one inverse norm per row of the side
+  if (cosine && (rc = ensure(c, c->d_sim_inv, (size_t)m))) return rc;
+  const std::vector<uint32_t> maskw = item_mask_words(m, mask);
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (cosine) {  // per call: every solve rewrites the table
+    ScopedTimer t(c, "similar.norms");
+    HIP_TRY(c, launch_row_inv_norm(c->emb[side], m, c->Dp, c->d_sim_inv, c->stream));
+    t.stop();
+  }
+  a.inv = cosine ? (const float*)c->d_sim_inv : nullptr;
+  a.skip_self = (flags & FRECSYS_SIM_KEEP_SELF) ? 0 : 1;
+  for (int64_t r0 = 0; r0 < n; r0 += p.nb) {  // one timed launch group per row batch
+    a.r0 = r0;
+    a.n = std::min(p.nb, n - r0);
+    ScopedTimer t(c, "similar");
+    HIP_TRY(c, launch_recommend(a, c->stream));
+    t.stop();
+    if ((rc = fetch_lists(c, ids, scores, k, r0, a.n, a.out_items, a.out_scores))) return rc;
+  }
+  // scoring flops at the logical dim; bytes: the queries and the table read,
+  // the table once more by the norm pass, the lists written
+  const double dd = c->dim;
+  add_work(c, "similar", 2.0 * (double)n * (double)m * dd,
+           ((double)n + (cosine ? 2.0 : 1.0) * (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
+int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
+                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
+                         float* ndcg) {
+  int32_t mk = 0;
+  const std::string e = metric_args_error(n, gt_ptr, gt_items, k_list, nk, -1, &mk);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: " + e);
+  if (list_k < mk)
+    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: list_k is below the largest cut-off");
+  if (n > 0 && (!lists || !recall || !ndcg))
+    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: bad arguments (null lists / outputs)");
+  const MetricTables& tab = metric_tables();
+  std::vector<int64_t> sp;
+  std::vector<int32_t> sg;
+  sorted_ground_truth(n, gt_ptr, gt_items, &sp, &sg);
+  std::vector<uint8_t> hit((size_t)mk);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t* g0 = sg.data() + sp[(size_t)i];
+    const int32_t* g1 = sg.data() + sp[(size_t)i + 1];
+    const int64_t g = g1 - g0;
+    const int32_t* list = lists + i * list_k;
+    for (int32_t j = 0; j < mk; ++j)  // -1: an empty slot, never a hit
+      hit[(size_t)j] = list[j] >= 0 && std::binary_search(g0, g1, list[j]);
+    for (int32_t q = 0; q < nk; ++q) {
+      const int32_t kq = k_list[q];  // <= mk <= list_k
+      double hits = 0.0, dcg = 0.0;
+      for (int32_t j = 0; j < kq; ++j)
+        if (hit[(size_t)j]) {
+          hits += 1.0;
+          dcg += tab.gain[j];
+        }
+      const double norm = tab.idcg[std::min<int64_t>(kq, g)];
+      recall[i * nk + q] = (float)(hits / std::min<float>((float)kq, (float)g));
+      ndcg[i * nk + q] = (float)(dcg / norm);
+    }
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int32_t na,
+                        float* out) {
+  if (n < 0 || na < 0 || (n > 0 && !values) || (na > 0 && (!alphas || !out)))
+    return fail(nullptr, FRECSYS_ERR_INVALID, "metric_cvar: bad arguments");
+  // EvaluationResult::cvar (evaluation.h:83-102), verbatim
+  std::vector<float> ms(values, values + n);
+  std::sort(ms.begin(), ms.end());
+  for (int32_t j = 0; j < na; ++j) out[j] = 0.0f;
+  int64_t counter = 0;
+  float acc = 0.0f;
+  for (int64_t i = 0; i < n; ++i) {
+    acc += ms[(size_t)i];
+    for (int64_t j = counter; j < na; ++j) {
+      const int pos = (int)((float)n * alphas[j]);
+      if (pos == i) {
+        out[counter] = acc / (float)(i + 1);
+        counter++;
+      }
+    }
+  }
+  return FRECSYS_OK;
+}
+
+}  // extern "C"
