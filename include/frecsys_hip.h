@@ -401,6 +401,63 @@ int frecsys_rank_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows, in
                          int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
                          const int32_t* gt_items, const int32_t* k_list, int32_t nk,
                          float* recall, float* ndcg);
+/* MRR and AUC of full-catalogue positions on the host (no reference
+ * counterpart; the expected-percentile-rank family of the original iALS
+ * evaluation).  No context and no HIP call, like frecsys_list_metrics.  Row i
+ * has the positions rank[gt_ptr[i] .. gt_ptr[i+1]) of its ground-truth entries
+ * (frecsys_rank_positions: 0-based, -1 = the item is not eligible) among
+ * M = eligible[i] eligible items.  R = the ascending distinct non-negative
+ * ranks of the row, g = |R| (distinct items have distinct ranks).  mrr[i] =
+ * g ? (float)(1.0 / (double)(R[0] + 1)) : 0.0f.  auc[i] = 0.0f when g = 0,
+ * 1.0f when M = g, else (float)(1.0 - (double)inv / ((double)g * (double)(M -
+ * g))) with inv = sum_q (R[q] - q) as an int64: the number of (held-out, other
+ * eligible) pairs in the wrong order -- an integer, so no summation order has
+ * to be stated.  mrr, auc: [n_rows].  FRECSYS_ERR_INVALID: a null pointer,
+ * n_rows < 0, gt_ptr[0] != 0 or a non-monotone gt_ptr, a row with no ground
+ * truth (as for frecsys_list_metrics; a row whose ground truth is entirely
+ * ineligible is valid and scores 0 / 0), a rank outside [-1, eligible[i]).  All
+ * checks come before the first write. */
+int frecsys_position_metrics(const int32_t* rank, const int64_t* gt_ptr, const int32_t* eligible,
+                             int64_t n_rows, float* mrr, float* auc);
+/* Exact positions of ground-truth items in the full ranking (no reference
+ * counterpart): what frecsys_recommend cannot report past k = 1024.  side,
+ * rows, flags and item_mask mean what they mean for frecsys_recommend;
+ * ground-truth row i (gt_items[gt_ptr[i] .. gt_ptr[i+1]), not empty, repeats
+ * allowed) belongs to query row i.  E_i = the eligible items of row i as
+ * frecsys_recommend defines them, word(i, j) = (u64)score_key(s_ij) << 32 |
+ * ~(u32)j with s_ij frecsys_recommend's score bit for bit.  For entry t with
+ * item j: rank[t] = -1 when j is not in E_i, else the number of j' in E_i with
+ * word(i, j') > word(i, j) -- the 0-based slot frecsys_recommend would list j
+ * in if its k were large enough; ties by ascending item id; a repeated id has
+ * the same rank at every occurrence.  eligible[i] = |E_i|.  mrr / auc are
+ * frecsys_position_metrics of those ranks, bitwise, computed on the device
+ * without the ranks leaving it.  rank: host [gt_ptr[n_rows]]; eligible, mrr,
+ * auc: host [n_rows]; each may be NULL, not all four.
+ * Per row batch: the history bits as for frecsys_recommend; one kernel scores
+ * every ground-truth entry by frecsys_score_pairs' chain (the scan's bits),
+ * forms the words and sorts each row's distinct eligible ones descending as
+ * thresholds; the scan (frecsys_recommend's tile and FMA chain; no score
+ * matrix, no candidate buffers, no top-K) counts, per row, the eligible items
+ * between consecutive thresholds with integer atomics (rows with up to 32
+ * thresholds in LDS, longer ones in global memory, as exactly); one wave per
+ * row turns the counts into ranks by a prefix sum, counts the eligibility
+ * bits, and forms mrr / auc with the host function's own int64 and IEEE
+ * double operations.  Workspace: per batch 28 bytes per ground-truth entry and
+ * 20 per row plus the history bits, the rows cut greedily so that a batch
+ * stays within FRECSYS_RECOMMEND_WS_MB (at least one row); the items are cut
+ * into FRECSYS_RECOMMEND_SPLITS parts as for frecsys_recommend.  Both knobs
+ * are read per call and change no result bit.  Rank-local at any world size.
+ * n_rows == 0 returns FRECSYS_OK and touches nothing.  FRECSYS_ERR_INVALID,
+ * before any device call: frecsys_recommend's cases but k, the ground-truth
+ * cases of frecsys_rank_metrics (a ground-truth id >= n_items among them),
+ * all four outputs NULL.  Timer key "rank_positions" (one launch group per
+ * row batch; nothing runs under "recommend"); frecsys_work("rank_positions"):
+ * 2 rows items d flops, bytes = the ground truth read, the ranks and the
+ * three values per row written. */
+int frecsys_rank_positions(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                           int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                           const int32_t* gt_items, int32_t* rank, int32_t* eligible, float* mrr,
+                           float* auc);
 /* Scores of caller-supplied pairs (no reference counterpart): scores[i] =
  * V[items[i]] . X[rows[i]] for the n_pairs pairs, X the table of `side` (USER
  * or EVAL), rows / items / scores host arrays [n_pairs]; any order, repeats

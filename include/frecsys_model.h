@@ -181,6 +181,29 @@ int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                    const float* alpha_list, int32_t na,
                                    int32_t exclude_seen, float* recall, float* ndcg,
                                    float* summary);
+/* Full-catalogue positions of the ground truth of n trained users
+ * (frecsys_rank_positions, frecsys_hip.h): where frecsys_model_recommend would
+ * list each held-out item if its k were large enough, and per user the
+ * reciprocal rank of the best one and the AUC.  rank: host [gt_ptr[n]];
+ * eligible, mrr, auc: host [n]; each may be NULL, not all four.  item_mask:
+ * host [n_items] or NULL.  summary: host [2 + 2 na] or NULL (it needs mrr and
+ * auc) -- mean mrr, mean auc, mrr CVaR [na], auc CVaR [na], by
+ * frecsys_model_evaluate's own mean (double sum in row order) and cvar(),
+ * quirks included.  Errors are frecsys_rank_positions', reported before any
+ * device call.  The _fold_in form projects the n histories into the EVAL side
+ * first, as frecsys_model_evaluate_fold_in does. */
+int frecsys_model_evaluate_ranks(frecsys_model* m, const int64_t* users, int64_t n,
+                                 const int64_t* gt_ptr, const int32_t* gt_items,
+                                 const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                 const uint8_t* item_mask, int32_t* rank, int32_t* eligible,
+                                 float* mrr, float* auc, float* summary);
+int frecsys_model_evaluate_ranks_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                         const int32_t* hist_items, int64_t n,
+                                         const int64_t* gt_ptr, const int32_t* gt_items,
+                                         const float* alpha_list, int32_t na,
+                                         int32_t exclude_seen, const uint8_t* item_mask,
+                                         int32_t* rank, int32_t* eligible, float* mrr,
+                                         float* auc, float* summary);
 /* frecsys_model_evaluate restricted to caller-supplied candidate lists
  * (second-stage evaluation): Recall@K / NDCG@K of the lists
  * frecsys_model_rank_candidates returns with k = max(k_list), computed on the

@@ -362,6 +362,50 @@ int64_t recommend_words(int64_t m);
 // candidates within the merge kernel's LDS.
 int recommend_max_splits(int k, int64_t m);
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
+// The history bitmaps of a row batch alone, as launch_recommend fills them
+// (rec_history_kernel): bitmap[n][recommend_words(m)] zeroed, then bit j of
+// row i set for every j of the CSR history of query row r0 + i.
+hipError_t launch_history_bits(const int64_t* row_ptr, const int32_t* col, const int64_t* qrows,
+                               int64_t r0, int64_t n, int64_t m, uint32_t* bitmap, hipStream_t s);
+
+// Exact positions of ground-truth items among all eligible items
+// (positions.hip): for query row i of the batch and entry t of its ground
+// truth gt[gt_ptr[r0 + i] - gt_base .. gt_ptr[r0 + i + 1] - gt_base), rank[t] =
+// the number of eligible items whose word (score_key(score) << 32 | ~id) is
+// larger than the entry's, -1 when the entry's item is not eligible;
+// eligible[i] = the eligible count; mrr / auc as frecsys_position_metrics
+// defines them.  Rows, eligibility and scores as in RecommendArgs.  Entry
+// regions are indexed by gt_ptr[...] - gt_base; row i's counters start at
+// that offset + i (one more counter than entries per row).
+struct PositionsArgs {
+  const float* X;            // query table, ld = Dp
+  const int64_t* qrows;      // table row of every query row of the call, or nullptr
+  int64_t r0, n;             // this batch: query rows r0 .. r0 + n - 1
+  const float* Y;            // items, ld = Dp
+  int64_t m;                 // items
+  int Dp;
+  int splits;                // item splits, 1 .. positions_max_splits(m)
+  const int64_t* row_ptr;    // CSR of the query table's side (with bitmap), or nullptr
+  const int32_t* col;
+  const uint32_t* maskw;     // [recommend_words(m)] eligibility bits of the items
+  uint32_t* bitmap;          // [n][recommend_words(m)] history bits (workspace), or nullptr
+  const int64_t* gt_ptr;     // [rows of the call + 1]
+  int64_t gt_base;           // gt_ptr[r0]: gt[0] is the first entry of the batch
+  const int32_t* gt;         // the batch's ground-truth ids, each in [0, m)
+  unsigned long long* words;  // [entries] word per entry, 0 = not eligible (workspace)
+  unsigned long long* thr;    // [entries] per row: distinct words, descending (workspace)
+  int32_t* g;                // [n] thresholds per row (workspace)
+  uint32_t* counters;        // [entries + n] (workspace)
+  int32_t* rank;             // [entries]
+  int32_t* eligible;         // [n]
+  float* mrr;                // [n]
+  float* auc;                // [n]
+};
+hipError_t launch_positions(const PositionsArgs& a, hipStream_t s);
+// Thresholds per row that pos_scan_kernel keeps in LDS (longer rows count in
+// global memory), and its largest split count: one 128-item tile per split.
+int positions_lds_thresholds();
+int positions_max_splits(int64_t m);
 // Inverse row norms of a table (similar.hip): n2 = the chain acc = fmaf(T[r][c],
 // T[r][c], acc), c ascending from +0 over the padded dim -- recommend.hip's
 // score of row r with itself, bit for bit -- and inv[r] = n2 > 0 ?

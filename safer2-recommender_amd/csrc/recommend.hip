@@ -344,6 +344,18 @@ int recommend_max_splits(int k, int64_t m) {
   return s < 1 ? 1 : (int)s;
 }
 
+hipError_t launch_history_bits(const int64_t* row_ptr, const int32_t* col, const int64_t* qrows,
+                               int64_t r0, int64_t n, int64_t m, uint32_t* bitmap, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (!row_ptr || !col || !bitmap || m < 1) return hipErrorInvalidValue;
+  const int64_t W = recommend_words(m);
+  hipError_t e = hipMemsetAsync(bitmap, 0, sizeof(uint32_t) * (size_t)n * (size_t)W, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rec_history_kernel, dim3((unsigned)n), dim3(64), 0, s, row_ptr, col, qrows, r0,
+                     m, W, bitmap);
+  return hipGetLastError();
+}
+
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (a.k < 1 || a.k > 1024 || a.m < 1 || a.splits < 1 ||

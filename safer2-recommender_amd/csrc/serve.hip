@@ -1,10 +1,11 @@
 // serve.hip -- host side of the ranking and evaluation calls of the C-ABI
 // (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
 // frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
-// frecsys_sampled_metrics, frecsys_similar, and the host-only
-// frecsys_sample_negatives, frecsys_list_metrics, frecsys_metric_cvar.  No
-// kernels here: recommend.hip, similar.hip, rerank.hip, sampled.hip and
-// metrics.hip hold them (kernels.h).
+// frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions, and the
+// host-only frecsys_sample_negatives, frecsys_list_metrics,
+// frecsys_position_metrics, frecsys_metric_cvar.  No kernels here:
+// recommend.hip, similar.hip, rerank.hip, sampled.hip, metrics.hip and
+// positions.hip hold them (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -20,6 +21,7 @@
 //   pairs (score_pairs): budget / 16 B, at least 64;
 //   caller lists (rank_candidates, rank_candidates_metrics): rows in order
 //     while their fixed bytes and ids fit the budget (cut_by_candidates);
+//   positions (rank_positions): the same cut by the ground-truth entries;
 //   sampled lists (sampled_metrics): rows by their fixed bytes within half the
 //     budget, then sub-batches whose ids fit the other half.
 // Rows are independent, so the batch size never changes a result.
@@ -217,19 +219,20 @@ void carve_scan(Carver& cv, RecommendArgs& a, const ScanPlan& p, bool rows, int6
 }
 
 // Rows cut greedily in row order into batches whose bytes -- row_fixed per
-// row and 4 per candidate id -- stay within the budget (at least one row
-// each); the workspace is sized for the largest.
+// row and per_id (4: the id alone) per candidate id -- stay within the budget
+// (at least one row each); the workspace is sized for the largest.
 struct Cuts {
   std::vector<int64_t> cuts{0};
   int64_t max_rows = 0, max_ids = 0;
 };
-Cuts cut_by_candidates(const int64_t* ptr, int64_t n, size_t row_fixed, size_t budget) {
+Cuts cut_by_candidates(const int64_t* ptr, int64_t n, size_t row_fixed, size_t budget,
+                       size_t per_id = 4) {
   Cuts r;
   for (int64_t r0 = 0; r0 < n;) {
     size_t bytes = 0;
     int64_t r1 = r0;
     while (r1 < n) {
-      const size_t add = row_fixed + (size_t)(ptr[r1 + 1] - ptr[r1]) * 4;
+      const size_t add = row_fixed + (size_t)(ptr[r1 + 1] - ptr[r1]) * per_id;
       if (r1 > r0 && bytes + add > budget) break;
       bytes += add;
       ++r1;
@@ -284,6 +287,17 @@ const MetricTables& metric_tables() {
   return tab;
 }
 
+// The rules of a ground-truth pointer array over n rows: starts at 0, monotone,
+// no empty row; "" when fine.
+std::string gt_ptr_error(int64_t n, const int64_t* gt_ptr) {
+  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
+  for (int64_t i = 0; i < n; ++i) {
+    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
+    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
+  }
+  return "";
+}
+
 // The argument checks frecsys_list_metrics and frecsys_rank_metrics share;
 // "" when fine.  n_items < 0: no upper bound on the ground-truth ids.
 std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
@@ -300,11 +314,8 @@ std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* g
     mk = std::max(mk, k_list[q]);
   }
   *max_k = mk;
-  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
-  for (int64_t i = 0; i < n; ++i) {
-    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
-    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
-  }
+  const std::string e = gt_ptr_error(n, gt_ptr);
+  if (!e.empty()) return e;
   if (n > 0 && !gt_items) return "null gt_items";
   for (int64_t p = 0; p < gt_ptr[n]; ++p)
     if (gt_items[p] < 0 || (n_items >= 0 && gt_items[p] >= n_items))
@@ -1107,6 +1118,124 @@ int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const 
       ndcg[i * nk + q] = (float)(dcg / norm);
     }
   }
+  return FRECSYS_OK;
+}
+
+int frecsys_position_metrics(const int32_t* rank, const int64_t* gt_ptr, const int32_t* eligible,
+                             int64_t n_rows, float* mrr, float* auc) {
+  const std::string w = "position_metrics: ";
+  if (n_rows < 0 || !gt_ptr)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad arguments (null gt_ptr, n < 0)");
+  const int64_t n = n_rows;
+  const std::string e = gt_ptr_error(n, gt_ptr);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  if (n > 0 && (!rank || !eligible || !mrr || !auc))
+    return fail(nullptr, FRECSYS_ERR_INVALID,
+                w + "bad arguments (null ranks / eligible / outputs)");
+  for (int64_t i = 0; i < n; ++i)  // (so a row never has more distinct ranks than eligible items)
+    for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p)
+      if (rank[p] < -1 || rank[p] >= eligible[i])
+        return fail(nullptr, FRECSYS_ERR_INVALID,
+                    w + "rank " + std::to_string(rank[p]) + " of row " + std::to_string(i) +
+                        " outside [-1, eligible)");
+  std::vector<int32_t> R;
+  for (int64_t i = 0; i < n; ++i) {
+    R.assign(rank + gt_ptr[i], rank + gt_ptr[i + 1]);
+    std::sort(R.begin(), R.end());
+    R.erase(std::unique(R.begin(), R.end()), R.end());
+    if (!R.empty() && R[0] < 0) R.erase(R.begin());
+    const int64_t g = (int64_t)R.size(), M = eligible[i];  // g <= M
+    int64_t inv = 0;
+    for (int64_t q = 0; q < g; ++q) inv += (int64_t)R[(size_t)q] - q;
+    mrr[i] = g ? (float)(1.0 / (double)((int64_t)R[0] + 1)) : 0.0f;
+    auc[i] = g == 0   ? 0.0f
+             : M == g ? 1.0f
+                      : (float)(1.0 - (double)inv / ((double)g * (double)(M - g)));
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_positions(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                           int32_t flags, const uint8_t* item_mask, const int64_t* gt_ptr,
+                           const int32_t* gt_items, int32_t* rank, int32_t* eligible, float* mrr,
+                           float* auc) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_positions: null context");
+  const std::string w = "rank_positions: ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, nullptr, flags, FRECSYS_REC_EXCLUDE_HISTORY);
+  if (rc) return rc;
+  if (n_rows < 0 || (n_rows > 0 && !rank && !eligible && !mrr && !auc))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, exclude, rows, n_rows))) return rc;
+  const int64_t m = c->n[1], n = n_rows;
+  {
+    const int32_t one = 1;  // the ground-truth cases of the metric calls; no cut-offs here
+    int32_t mk = 0;
+    const std::string e = metric_args_error(n, gt_ptr, gt_items, &one, 1, m, &mk);
+    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  }
+  if (n == 0) return FRECSYS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int64_t W = recommend_words(m);
+  // per ground-truth entry of a batch: id, word, threshold, counter, rank; per
+  // row: one more counter, the threshold count, eligible, mrr, auc, history bits
+  const Cuts ct = cut_by_candidates(gt_ptr, n, 20 + (exclude ? (size_t)W * 4 : 0),
+                                    workspace_budget(), 28);
+  PositionsArgs a{};
+  a.X = c->emb[side];
+  a.Y = c->emb[1];
+  a.m = m;
+  a.Dp = c->Dp;
+  a.splits = scan_plan(c, 1, m, n, 0).splits;  // no list: one tile per split at least
+  c->rec_splits = a.splits;
+  a.row_ptr = exclude ? c->rp[side] : nullptr;
+  a.col = exclude ? c->col[side] : nullptr;
+  int32_t* d_gt = nullptr;
+  rc = Carver::run(c, [&](Carver& cv) {
+    const size_t ids = (size_t)ct.max_ids, nb = (size_t)ct.max_rows;
+    d_gt = cv.take<int32_t>(ids);
+    a.words = cv.take<unsigned long long>(ids);
+    a.thr = cv.take<unsigned long long>(ids);
+    a.counters = cv.take<uint32_t>(ids + nb);
+    a.rank = cv.take<int32_t>(ids);
+    a.g = cv.take<int32_t>(nb);
+    a.bitmap = cv.take_if<uint32_t>(exclude, nb * (size_t)W);
+    a.eligible = cv.take<int32_t>(nb);
+    a.mrr = cv.take<float>(nb);
+    a.auc = cv.take<float>(nb);
+    // outside the per-row budget: per call
+    a.maskw = cv.take<uint32_t>((size_t)W);
+    a.gt_ptr = cv.take<int64_t>((size_t)n + 1);
+    a.qrows = cv.take_if<int64_t>(rows != nullptr, (size_t)n);
+  });
+  if (rc) return rc;
+  a.gt = d_gt;
+  const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  HIP_TRY(c, to_device(c, a.gt_ptr, gt_ptr, (size_t)n + 1));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b + 1 < ct.cuts.size(); ++b) {  // one timed launch group per row batch
+    a.r0 = ct.cuts[b];
+    a.n = ct.cuts[b + 1] - ct.cuts[b];
+    a.gt_base = gt_ptr[a.r0];
+    const int64_t ids = gt_ptr[a.r0 + a.n] - a.gt_base;
+    HIP_TRY(c, to_device(c, a.gt, gt_items + a.gt_base, (size_t)ids));
+    ScopedTimer t(c, "rank_positions");
+    HIP_TRY(c, launch_positions(a, c->stream));
+    t.stop();
+    if (rank) HIP_TRY(c, to_host(c, rank + a.gt_base, a.rank, (size_t)ids));
+    if (eligible) HIP_TRY(c, to_host(c, eligible + a.r0, a.eligible, (size_t)a.n));
+    if (mrr) HIP_TRY(c, to_host(c, mrr + a.r0, a.mrr, (size_t)a.n));
+    if (auc) HIP_TRY(c, to_host(c, auc + a.r0, a.auc, (size_t)a.n));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  // scoring flops at the logical dim; bytes: the ground truth read, the ranks
+  // and the three values per row written
+  add_work(c, "rank_positions", 2.0 * (double)n * (double)m * (double)c->dim,
+           (double)gt_ptr[n] * 4.0 + ((double)n + 1.0) * 8.0 + (double)gt_ptr[n] * 4.0 +
+               (double)n * 12.0,
+           n);
   return FRECSYS_OK;
 }
 

@@ -50,7 +50,7 @@ EXPORTS = (
     "frecsys_cg_iterations", "frecsys_list_metrics", "frecsys_metric_cvar",
     "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
     "frecsys_similar", "frecsys_sample_negatives", "frecsys_rank_candidates_metrics",
-    "frecsys_sampled_metrics",
+    "frecsys_sampled_metrics", "frecsys_position_metrics", "frecsys_rank_positions",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -65,6 +65,7 @@ MODEL_EXPORTS = (
     "frecsys_model_similar_items", "frecsys_model_similar_users",
     "frecsys_model_evaluate_candidates", "frecsys_model_evaluate_candidates_fold_in",
     "frecsys_model_evaluate_sampled", "frecsys_model_evaluate_sampled_fold_in",
+    "frecsys_model_evaluate_ranks", "frecsys_model_evaluate_ranks_fold_in",
 )
 
 
@@ -196,6 +197,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                             [P, I32, P, I64, P, P, I32, P, P, P, P, I32, P, P]),
         "frecsys_sampled_metrics": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, I32,
                                                    ctypes.c_uint64, P, I32, P, P, P, P]),
+        "frecsys_position_metrics": (ctypes.c_int, [P, P, P, I64, P, P]),
+        "frecsys_rank_positions": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -247,6 +250,10 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_evaluate_sampled_fold_in": (
             ctypes.c_int,
             [P, P, P, I64, P, P, I32, ctypes.c_uint64, P, I32, P, I32, I32, P, P, P, P]),
+        "frecsys_model_evaluate_ranks": (
+            ctypes.c_int, [P, P, I64, P, P, P, I32, I32, P, P, P, P, P, P]),
+        "frecsys_model_evaluate_ranks_fold_in": (
+            ctypes.c_int, [P, P, P, I64, P, P, P, I32, I32, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -352,6 +359,26 @@ def sample_negatives(n_items: int, gt_ptr, gt_items, n_neg: int, seed: int = 0, 
     if rc:
         raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
     return cnt, neg
+
+
+def position_metrics(rank, gt_ptr, eligible) -> Tuple[np.ndarray, np.ndarray]:
+    """(mrr, auc) float32 [n] of full-catalogue positions (rank int32
+    [gt_ptr[n]], 0-based, -1 = not eligible; eligible int32 [n]: the eligible
+    items per row) -- frecsys_position_metrics on the host, no GPU needed; what
+    Context.rank_positions computes on the device, bit for bit."""
+    lib = load_library()
+    rk = np.ascontiguousarray(rank, dtype=np.int32).reshape(-1)
+    gp = np.ascontiguousarray(gt_ptr, dtype=np.int64).reshape(-1)
+    el = np.ascontiguousarray(eligible, dtype=np.int32).reshape(-1)
+    n = len(gp) - 1
+    assert len(el) == n, (len(el), n)
+    assert n < 1 or len(rk) == gp[-1], (len(rk), gp[-1])
+    mrr = np.zeros(n, dtype=np.float32)
+    auc = np.zeros(n, dtype=np.float32)
+    rc = lib.frecsys_position_metrics(_ptr(rk), _ptr(gp), _ptr(el), n, _ptr(mrr), _ptr(auc))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    return mrr, auc
 
 
 def metric_cvar(values, alphas) -> np.ndarray:
@@ -648,6 +675,35 @@ class Context:
                                                   _ptr(mk), _ptr(gp), _ptr(gi), _ptr(ks), len(ks),
                                                   _ptr(rec), _ptr(ndcg)))
         return rec, ndcg
+
+    def rank_positions(self, side: int, gt_ptr, gt_items, rows=None,
+                       exclude_history: bool = True, item_mask=None, metrics: bool = True):
+        """(rank int32 [gt_ptr[n]], eligible int32 [n], mrr float32 [n], auc
+        float32 [n]) -- without the last two when metrics is False: the exact
+        0-based position of every ground-truth entry among the eligible items
+        of its query row (the slot recommend would list it in if its k were
+        large enough; -1: the item is masked out or in the excluded history),
+        the eligible count, and position_metrics of those ranks computed on
+        the GPU -- frecsys_rank_positions, a fused score-and-count scan.  rows,
+        exclude_history and item_mask as for recommend; ground-truth row i (CSR
+        gt_ptr / gt_items; not empty) belongs to query row i."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        rank = np.full(len(gi), -1, dtype=np.int32)
+        elig = np.zeros(n, dtype=np.int32)
+        mrr = np.zeros(n, dtype=np.float32) if metrics else None
+        auc = np.zeros(n, dtype=np.float32) if metrics else None
+        self._check(self.lib.frecsys_rank_positions(self.h, side, _ptr(r), n,
+                                                    REC_EXCLUDE_HISTORY if exclude_history else 0,
+                                                    _ptr(mk), _ptr(gp), _ptr(gi), _ptr(rank),
+                                                    _ptr(elig), _ptr(mrr), _ptr(auc)))
+        return (rank, elig, mrr, auc) if metrics else (rank, elig)
 
     def score_pairs(self, side: int, rows, items) -> np.ndarray:
         """float32 [n]: the score of item items[i] for row rows[i] of `side`
@@ -1116,6 +1172,51 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return self._evaluation(n, ks, al, rec, ndcg, summary)
+
+    def _eval_ranks(self, fn, head, n, gt_ptr, gt_items, alpha_list, exclude_seen, item_mask):
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
+        na = len(al)
+        mk = self._mask(item_mask)
+        rank = np.full(len(gi), -1, dtype=np.int32)
+        elig = np.zeros(n, dtype=np.int32)
+        mrr = np.zeros(n, dtype=np.float32)
+        auc = np.zeros(n, dtype=np.float32)
+        summary = np.zeros(2 + 2 * na, dtype=np.float32)
+        rc = fn(self.h, *[_ptr(x) for x in head], n, _ptr(gp), _ptr(gi), _ptr(al), na,
+                int(bool(exclude_seen)), _ptr(mk), _ptr(rank), _ptr(elig), _ptr(mrr), _ptr(auc),
+                _ptr(summary))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return {"rank": rank, "eligible": elig, "mrr": mrr, "auc": auc, "alpha_list": al,
+                "mean_mrr": float(summary[0]), "mean_auc": float(summary[1]),
+                "mrr_cvar": summary[2:2 + na].copy(), "auc_cvar": summary[2 + na:].copy()}
+
+    def evaluate_ranks(self, users, gt_ptr, gt_items, alpha_list=EVAL_ALPHA_LIST,
+                       exclude_seen: bool = True, item_mask=None):
+        """Full-catalogue ranking quality of trained users
+        (frecsys_model_evaluate_ranks): a dict of "rank" int32 [gt_ptr[n]] (the
+        exact 0-based position recommend would list each held-out item at with
+        a large enough k; -1 = not eligible), "eligible" int32 [n], per-user
+        "mrr" and "auc" float32 [n], and "mean_mrr", "mean_auc", "mrr_cvar",
+        "auc_cvar" [na] by evaluate()'s own mean and cvar().  Unlike Recall@K /
+        NDCG@K these tell apart users whose held-out items rank below 1024."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        return self._eval_ranks(self.lib.frecsys_model_evaluate_ranks, [u], len(u), gt_ptr,
+                                gt_items, alpha_list, exclude_seen, item_mask)
+
+    def evaluate_ranks_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items,
+                               alpha_list=EVAL_ALPHA_LIST, exclude_seen: bool = True,
+                               item_mask=None):
+        """The same for unseen users given by their histories (CSR hist_ptr /
+        hist_items): the model's fold-in projection, then the positions of the
+        projected rows (frecsys_model_evaluate_ranks_fold_in).  The projected
+        rows stay in the EVAL side."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        return self._eval_ranks(self.lib.frecsys_model_evaluate_ranks_fold_in, [hp, hi],
+                                len(hp) - 1, gt_ptr, gt_items, alpha_list, exclude_seen, item_mask)
 
     def _eval_lists(self, fn, head, n, cand, gt_ptr, gt_items, sample, k_list, alpha_list,
                     exclude_seen, item_mask):

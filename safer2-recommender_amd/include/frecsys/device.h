@@ -270,6 +270,14 @@ class DeviceContext {
     return frecsys_sampled_metrics(ctx_, side, rows, n, flags, mask, gt_ptr, gt_items, n_neg, seed,
                                    k_list, nk, recall, ndcg, nullptr, nullptr);
   }
+  // Exact positions of the ground truth among all eligible items, with mrr /
+  // auc per row (frecsys_rank_positions): the status code.
+  int TryRankPositions(int side, const int64_t* rows, int64_t n, int flags, const uint8_t* mask,
+                       const int64_t* gt_ptr, const int32_t* gt_items, int32_t* rank,
+                       int32_t* eligible, float* mrr, float* auc) {
+    return frecsys_rank_positions(ctx_, side, rows, n, flags, mask, gt_ptr, gt_items, rank,
+                                  eligible, mrr, auc);
+  }
   struct Metrics {
     MatrixXf recall, ndcg;  // rows x |k_list|
   };

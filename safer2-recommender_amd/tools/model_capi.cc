@@ -315,16 +315,17 @@ namespace {
 
 // The argument checks of the two evaluate entry points, before any device
 // call (the C++ layer treats a failed device call as fatal); "" when fine.
-std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
-                                const int32_t* gt_items, const int32_t* k_list, int32_t nk,
-                                const float* alpha_list, int32_t na, const float* recall,
-                                const float* ndcg) {
-  if (n < 0 || !gt_ptr || gt_ptr[0] != 0) return "bad arguments (n < 0, gt_ptr)";
-  if (!k_list || nk < 1 || nk > 32) return "k_list must hold 1 to 32 cut-offs";
-  for (int32_t q = 0; q < nk; ++q)
-    if (k_list[q] < 1 || k_list[q] > 1024) return "cut-offs must be in [1, 1024]";
-  if (na < 0 || (na > 0 && !alpha_list)) return "bad alpha_list";
-  if (n > 0 && (!recall || !ndcg || !gt_items)) return "null gt_items / recall / ndcg";
+// Its pieces, shared with the rank evaluation: the row count and the head of
+// the ground-truth CSR, the alphas, and the CSR's rows and ids (gt_items not
+// null when there are rows: the caller's check).
+std::string truth_head_error(int64_t n, const int64_t* gt_ptr) {
+  return n < 0 || !gt_ptr || gt_ptr[0] != 0 ? "bad arguments (n < 0, gt_ptr)" : "";
+}
+std::string alpha_error(const float* alpha_list, int32_t na) {
+  return na < 0 || (na > 0 && !alpha_list) ? "bad alpha_list" : "";
+}
+std::string truth_rows_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
+                             const int32_t* gt_items) {
   for (int64_t i = 0; i < n; ++i)
     if (gt_ptr[i + 1] <= gt_ptr[i])
       return "gt_ptr not monotone or no ground truth at row " + std::to_string(i);
@@ -332,6 +333,19 @@ std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_pt
     if (gt_items[p] < 0 || gt_items[p] >= n_items)
       return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
   return "";
+}
+std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
+                                const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                const float* alpha_list, int32_t na, const float* recall,
+                                const float* ndcg) {
+  std::string e = truth_head_error(n, gt_ptr);
+  if (!e.empty()) return e;
+  if (!k_list || nk < 1 || nk > 32) return "k_list must hold 1 to 32 cut-offs";
+  for (int32_t q = 0; q < nk; ++q)
+    if (k_list[q] < 1 || k_list[q] > 1024) return "cut-offs must be in [1, 1024]";
+  if (!(e = alpha_error(alpha_list, na)).empty()) return e;
+  if (n > 0 && (!recall || !ndcg || !gt_items)) return "null gt_items / recall / ndcg";
+  return truth_rows_error(n, n_items, gt_ptr, gt_items);
 }
 
 // Metrics of `n` query rows of `side` into recall / ndcg, then the summary
@@ -453,9 +467,67 @@ int evaluate_lists(frecsys_model* m, const std::string& w, const int64_t* users,
   return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
 }
 
+// frecsys_model_evaluate_ranks and its fold-in form (users != nullptr: trained
+// users).  The summary is summarize()'s with one column: mrr in recall's
+// place, auc in ndcg's.
+int evaluate_ranks(frecsys_model* m, const std::string& w, const int64_t* users,
+                   const int64_t* hist_ptr, const int32_t* hist_items, bool fold_in, int64_t n,
+                   const int64_t* gt_ptr, const int32_t* gt_items, const float* alpha_list,
+                   int32_t na, int32_t exclude_seen, const uint8_t* item_mask, int32_t* rank,
+                   int32_t* eligible, float* mrr, float* auc, float* summary) {
+  if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  frecsys::DeviceContext& dev = dm->device();
+  const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
+  const int32_t one = 1;  // summarize()'s one column
+  std::string e = fold_in ? hist_args_error(n, n_items, hist_ptr, hist_items) : "";
+  if (e.empty()) e = truth_head_error(n, gt_ptr);
+  if (e.empty()) e = alpha_error(alpha_list, na);
+  if (e.empty() && n > 0 && !gt_items) e = "null gt_items";
+  if (e.empty() && n > 0 && !rank && !eligible && !mrr && !auc) e = "null outputs";
+  if (e.empty() && summary && n > 0 && (!mrr || !auc)) e = "summary needs mrr and auc";
+  if (e.empty()) e = truth_rows_error(n, n_items, gt_ptr, gt_items);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (n == 0) return summarize(n, &one, 1, alpha_list, na, mrr, auc, summary);
+  int side = FRECSYS_SIDE_USER;
+  if (fold_in) {
+    frecsys::Csr csr;
+    csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+    csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+    dm->FoldIn(csr);
+    side = FRECSYS_SIDE_EVAL;
+  }
+  const int rc = dev.TryRankPositions(side, users, n, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
+                                      item_mask, gt_ptr, gt_items, rank, eligible, mrr, auc);
+  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
+  return summarize(n, &one, 1, alpha_list, na, mrr, auc, summary);
+}
+
 }  // namespace
 
 extern "C" {
+
+int frecsys_model_evaluate_ranks(frecsys_model* m, const int64_t* users, int64_t n,
+                                 const int64_t* gt_ptr, const int32_t* gt_items,
+                                 const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                 const uint8_t* item_mask, int32_t* rank, int32_t* eligible,
+                                 float* mrr, float* auc, float* summary) {
+  return evaluate_ranks(m, "frecsys_model_evaluate_ranks: ", users, nullptr, nullptr, false, n,
+                        gt_ptr, gt_items, alpha_list, na, exclude_seen, item_mask, rank, eligible,
+                        mrr, auc, summary);
+}
+
+int frecsys_model_evaluate_ranks_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                         const int32_t* hist_items, int64_t n,
+                                         const int64_t* gt_ptr, const int32_t* gt_items,
+                                         const float* alpha_list, int32_t na,
+                                         int32_t exclude_seen, const uint8_t* item_mask,
+                                         int32_t* rank, int32_t* eligible, float* mrr,
+                                         float* auc, float* summary) {
+  return evaluate_ranks(m, "frecsys_model_evaluate_ranks_fold_in: ", nullptr, hist_ptr, hist_items,
+                        true, n, gt_ptr, gt_items, alpha_list, na, exclude_seen, item_mask, rank,
+                        eligible, mrr, auc, summary);
+}
 
 int frecsys_model_evaluate_candidates(frecsys_model* m, const int64_t* users, int64_t n,
                                       const int64_t* cand_ptr, const int32_t* cand_items,
