@@ -58,6 +58,8 @@ extern "C" {
 #define FRECSYS_ERR_NAN 5         /* NaN detected (reference: LOG(ERROR) + exit) */
 #define FRECSYS_ERR_UNSUPPORTED 6 /* e.g. dim beyond the kernels built */
 #define FRECSYS_ERR_NO_DEVICE 7   /* no HIP device visible */
+#define FRECSYS_ERR_IO 8          /* open / read / write / rename of a file failed
+                                     (model checkpoints, frecsys_model.h) */
 
 /* ---- sides ---- */
 #define FRECSYS_SIDE_USER 0 /* train by_user: rows = users, cols = items */

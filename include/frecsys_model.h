@@ -16,6 +16,8 @@
  *                                loop (run_model.cc:258-266), `epochs` times
  *   frecsys_model_context     -- the device context (include/frecsys_hip.h)
  *                                the model runs on: embeddings, timers
+ *   frecsys_model_save / _load -- checkpoints: exact resume, serve-only load,
+ *                                warm start (no reference counterpart)
  *
  * Conditions the reference treats as fatal (a failed LLT, ials.h:141; NaN
  * losses, ials.h:291-296) end the process as they do there.  The tuples
@@ -253,6 +255,62 @@ int frecsys_model_evaluate_sampled_fold_in(frecsys_model* m, const int64_t* hist
                                            int32_t nk, const float* alpha_list, int32_t na,
                                            int32_t exclude_seen, const uint8_t* item_mask,
                                            float* recall, float* ndcg, float* summary);
+/* ---- checkpoints (format, version 1: safer2-recommender_amd/include/frecsys/
+ * checkpoint.h and DESIGN.md 3.16) ----
+ *
+ * frecsys_model_save writes the whole model to `path`: configuration, U, V,
+ * the dual state of frecsys_model_dual_state, the state that lives across
+ * Train() calls (xi, the SNR generator, the epoch count) and, unless
+ * FRECSYS_SAVE_NO_DATA is set, the training tuples.  The file is written
+ * beside `path` under a temporary name, flushed, fsynced and renamed over
+ * `path`; a failure removes the temporary file and leaves an existing `path`
+ * as it was.  At most one table is held on the host at a time.  Any rank of
+ * a multi-rank model may save: every rank holds the full tables and vectors
+ * and the file holds nothing rank-specific.  FRECSYS_ERR_IO: open / write /
+ * rename failed. */
+#define FRECSYS_SAVE_NO_DATA 1 /* leave USERS / ITEMS out */
+int frecsys_model_save(frecsys_model* m, const char* path, int32_t flags);
+/* A model from a file.  The whole file is validated first, on the host
+ * (FRECSYS_ERR_INVALID for a malformed file, FRECSYS_ERR_IO for an open or
+ * read failure; FRECSYS_ERR_NO_DEVICE only for a good file).
+ *   cfg NULL: the stored configuration, default device / world / rank /
+ *     comm_id; else cfg as given (frecsys_model_file_info, edit, load):
+ *     model_name and dim must be the file's, parity_quirks too unless
+ *     FRECSYS_LOAD_TABLES_ONLY.
+ *   flags 0, resume: the tuples come from the file (users NULL) or from the
+ *     caller, whose count and checksum must be the stored ones.  The model is
+ *     in exactly the saved state and initialised (frecsys_model_initialize is
+ *     a no-op), its training CSR loaded, so exclude_seen works before any
+ *     Train(); frecsys_model_epochs continues; the next Train() is the saved
+ *     run's next one, bit for bit.
+ *   flags 0, users NULL, a file without tuples: serve-only.  Tables, Gramians
+ *     and dual state are restored; frecsys_model_train and every call on
+ *     trained users with exclude_seen != 0 return FRECSYS_ERR_INVALID;
+ *     everything else works (the fold-in calls exclude the history they are
+ *     given; frecsys_model_initialize is the same no-op).
+ *   FRECSYS_LOAD_TABLES_ONLY, warm start: the caller's tuples are required
+ *     and may span more users / items than the file (not fewer).  The model
+ *     is what frecsys_model_create makes of them, seeded init included, with
+ *     rows [0, stored n) of U and V replaced from the file; no dual state,
+ *     epochs 0, frecsys_model_initialize as for a new model. */
+#define FRECSYS_LOAD_TABLES_ONLY 1 /* warm start: U and V only */
+int frecsys_model_load(const char* path, const frecsys_model_config* cfg, const int32_t* users,
+                       const int32_t* items, int64_t n_tuples, int32_t flags,
+                       frecsys_model** out);
+typedef struct {
+  char model_name[16];
+  frecsys_model_config config; /* config.model_name points at model_name above */
+  int64_t n_users, n_items, n_tuples, epochs_trained;
+  uint64_t flags; /* bit 0: the file holds the training tuples */
+  uint64_t tuples_checksum;
+  uint32_t version;
+} frecsys_model_file_info_t; /* _t: a C typedef cannot share the function's name */
+/* What a file holds.  Host only: no device, no context.  verify = 0: header,
+ * directory (bounds, alignment, overlap, section sizes) and CONFIG; verify
+ * != 0: every section's checksum, the zero gaps and the tuple ids too. */
+int frecsys_model_file_info(const char* path, int32_t verify, frecsys_model_file_info_t* info);
+/* Train() calls so far, those before a resumed model's save included. */
+int64_t frecsys_model_epochs(const frecsys_model* m);
 void frecsys_model_destroy(frecsys_model* m);
 const char* frecsys_model_last_error(void);
 

@@ -27,6 +27,9 @@ KIND_IALS, KIND_WEIGHTED_U, KIND_WEIGHTED_V, KIND_CVAR_GRAD_U, KIND_CVAR_GRAD_V 
 
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_RCCL, ERR_NOT_SPD, ERR_NAN, ERR_UNSUPPORTED, ERR_NO_DEVICE = range(1, 8)
+ERR_IO = 8
+SAVE_NO_DATA = 1
+LOAD_TABLES_ONLY = 1
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfrecsys_hip.so")
 MODEL_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfrecsys_model.so")
@@ -66,6 +69,8 @@ MODEL_EXPORTS = (
     "frecsys_model_evaluate_candidates", "frecsys_model_evaluate_candidates_fold_in",
     "frecsys_model_evaluate_sampled", "frecsys_model_evaluate_sampled_fold_in",
     "frecsys_model_evaluate_ranks", "frecsys_model_evaluate_ranks_fold_in",
+    "frecsys_model_save", "frecsys_model_load", "frecsys_model_file_info",
+    "frecsys_model_epochs",
 )
 
 
@@ -122,6 +127,14 @@ class _ModelConfig(ctypes.Structure):
                 ("rank", ctypes.c_int32), ("comm_id", ctypes.c_void_p),
                 ("use_cg", ctypes.c_int32), ("cg_error_tolerance", ctypes.c_float),
                 ("cg_max_iterations", ctypes.c_int32)]
+
+
+class _ModelFileInfo(ctypes.Structure):
+    _fields_ = [("model_name", ctypes.c_char * 16), ("config", _ModelConfig),
+                ("n_users", ctypes.c_int64), ("n_items", ctypes.c_int64),
+                ("n_tuples", ctypes.c_int64), ("epochs_trained", ctypes.c_int64),
+                ("flags", ctypes.c_uint64), ("tuples_checksum", ctypes.c_uint64),
+                ("version", ctypes.c_uint32)]
 
 
 _lib = None
@@ -254,6 +267,10 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
             ctypes.c_int, [P, P, I64, P, P, P, I32, I32, P, P, P, P, P, P]),
         "frecsys_model_evaluate_ranks_fold_in": (
             ctypes.c_int, [P, P, P, I64, P, P, P, I32, I32, P, P, P, P, P, P]),
+        "frecsys_model_save": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
+        "frecsys_model_load": (ctypes.c_int, [ctypes.c_char_p, P, P, P, I64, I32, P]),
+        "frecsys_model_file_info": (ctypes.c_int, [ctypes.c_char_p, I32, P]),
+        "frecsys_model_epochs": (I64, [P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -393,6 +410,30 @@ def metric_cvar(values, alphas) -> np.ndarray:
     if rc:
         raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
     return out
+
+
+# the stored fields of frecsys_model_config (CONFIG of a checkpoint)
+_STORED_FLAGS = tuple(n for n, _ in _ModelConfig._fields_
+                      if n not in ("model_name", "device", "world", "rank", "comm_id"))
+
+
+def model_file_info(path: str, verify: bool = True) -> dict:
+    """What the checkpoint at `path` holds (frecsys_model_file_info; host only,
+    no device): model_name, n_users, n_items, n_tuples, epochs_trained, flags,
+    has_data, tuples_checksum, version and `config`, a dict of the stored
+    model flags.  verify=False checks the header, the directory and CONFIG;
+    verify=True every section's checksum too."""
+    lib = load_model_library()
+    info = _ModelFileInfo()
+    rc = lib.frecsys_model_file_info(os.fsencode(path), int(bool(verify)), ctypes.byref(info))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_model_last_error().decode())
+    return {"model_name": info.model_name.decode(), "n_users": info.n_users,
+            "n_items": info.n_items, "n_tuples": info.n_tuples,
+            "epochs_trained": info.epochs_trained, "flags": info.flags,
+            "has_data": bool(info.flags & 1), "tuples_checksum": info.tuples_checksum,
+            "version": info.version,
+            "config": {n: getattr(info.config, n) for n in _STORED_FLAGS}}
 
 
 def unique_id() -> bytes:
@@ -934,15 +975,7 @@ class Model:
         self._name = model_name.encode()
         cfg.model_name = self._name
         self._cid = None
-        for k, v in flags.items():
-            if k == "comm_id":
-                if v is not None:
-                    self._cid = (ctypes.c_uint8 * 128).from_buffer_copy(v)
-                    cfg.comm_id = ctypes.cast(self._cid, ctypes.c_void_p)
-                continue
-            if not hasattr(cfg, k):
-                raise TypeError(f"unknown model flag {k}")
-            setattr(cfg, k, int(v) if isinstance(v, bool) else v)
+        self._apply_flags(cfg, flags)
         u = np.ascontiguousarray(users, dtype=np.int32)
         it = np.ascontiguousarray(items, dtype=np.int32)
         assert u.shape == it.shape
@@ -955,6 +988,76 @@ class Model:
         self.dim = cfg.dim
         self.n_users = int(u.max()) + 1
         self.n_items = int(it.max()) + 1
+
+    def _apply_flags(self, cfg, flags):
+        for k, v in flags.items():
+            if k == "comm_id":
+                if v is not None:
+                    self._cid = (ctypes.c_uint8 * 128).from_buffer_copy(v)
+                    cfg.comm_id = ctypes.cast(self._cid, ctypes.c_void_p)
+                continue
+            if not hasattr(cfg, k):
+                raise TypeError(f"unknown model flag {k}")
+            setattr(cfg, k, int(v) if isinstance(v, bool) else v)
+
+    def save(self, path: str, include_data: bool = True):
+        """Write the model to `path` (frecsys_model_save): tables, dual state,
+        everything an exact resume needs and, with include_data, the training
+        tuples.  Atomic: an existing file is replaced only by a complete one."""
+        rc = self.lib.frecsys_model_save(self.h, os.fsencode(path),
+                                         0 if include_data else SAVE_NO_DATA)
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+
+    @classmethod
+    def load(cls, path: str, users=None, items=None, tables_only: bool = False, **flags):
+        """A model from a checkpoint (frecsys_model_load).  Without tuples: the
+        file's own (resume), or none when it holds none (serve-only: no train,
+        no exclude_seen).  With the saved run's tuples: resume, checked against
+        the file's checksum.  tables_only: a new model of the caller's tuples
+        (which may span more users / items) whose U and V start from the
+        file's.  `flags` are Model(...)'s, applied on top of the stored ones;
+        model_name and dim cannot change."""
+        self = cls.__new__(cls)
+        self.lib = load_model_library()
+        info = _ModelFileInfo()
+        rc = self.lib.frecsys_model_file_info(os.fsencode(path), 0, ctypes.byref(info))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        cfg = _ModelConfig()
+        ctypes.pointer(cfg)[0] = info.config
+        self._name = bytes(info.model_name.decode(), "ascii")
+        cfg.model_name = self._name
+        self._cid = None
+        name = flags.pop("model_name", None)
+        if name is not None:
+            self._name = name.encode()
+            cfg.model_name = self._name
+        self._apply_flags(cfg, flags)
+        if (users is None) != (items is None):
+            raise TypeError("users and items go together")
+        u = it = None
+        if users is not None:
+            u = np.ascontiguousarray(users, dtype=np.int32)
+            it = np.ascontiguousarray(items, dtype=np.int32)
+            assert u.shape == it.shape
+        h = ctypes.c_void_p()
+        rc = self.lib.frecsys_model_load(os.fsencode(path), ctypes.byref(cfg), _ptr(u), _ptr(it),
+                                         0 if u is None else len(u),
+                                         LOAD_TABLES_ONLY if tables_only else 0, ctypes.byref(h))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self.h = h
+        self.dim = cfg.dim
+        self.n_users, self.n_items = info.n_users, info.n_items
+        if tables_only:
+            self.n_users, self.n_items = int(u.max()) + 1, int(it.max()) + 1
+        return self
+
+    @property
+    def epochs(self) -> int:
+        """Train() calls so far, those before a resumed model's save included."""
+        return int(self.lib.frecsys_model_epochs(self.h))
 
     def initialize(self):
         rc = self.lib.frecsys_model_initialize(self.h)

@@ -129,6 +129,15 @@ class CVaRMFRecommender : public detail::DeviceModel {
   float xi() const { return prev_xi_; }
   const VectorXf& dual_weight() const { return dual_weight_; }
 
+  void CaptureState(std::map<std::string, std::string>* kv) override {
+    (*kv)["xi_bits"] = FloatBits(prev_xi_);
+    (*kv)["weight_epoch"] = std::to_string(weight_epoch_);
+  }
+  bool RestoreState(const std::map<std::string, std::string>& kv, std::string* err) override {
+    return StateFloatBits(kv, "xi_bits", &prev_xi_, err) &&
+           StateU64(kv, "weight_epoch", UINT64_MAX, &weight_epoch_, err);
+  }
+
  protected:
   void OnEmbeddingsSet() override { dev_->Gramian(DeviceContext::ITEM); }
 

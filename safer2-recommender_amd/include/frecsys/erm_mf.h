@@ -117,6 +117,13 @@ class ERMMFRecommender : public detail::DeviceModel {
 
   float GetMeanWeight() const { return dual_weight_.mean(); }
 
+  void CaptureState(std::map<std::string, std::string>* kv) override {
+    (*kv)["weight_epoch"] = std::to_string(weight_epoch_);
+  }
+  bool RestoreState(const std::map<std::string, std::string>& kv, std::string* err) override {
+    return StateU64(kv, "weight_epoch", UINT64_MAX, &weight_epoch_, err);
+  }
+
  protected:
   void OnEmbeddingsSet() override { dev_->Gramian(DeviceContext::ITEM); }
 

@@ -8,9 +8,12 @@
 // one-row context (ProjectOnDevice).
 #pragma once
 
+#include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -54,6 +57,30 @@ class DeviceModel : public Recommender {
   const VectorXf& dual_weights() const { return dual_weight_; }
   const VectorXf& item_regularization() const { return item_reg_; }
   DeviceContext& device() { return *dev_; }
+
+  // ---- checkpoints (frecsys/checkpoint.h) ----
+  // The scalar state that lives across Train() calls beside the tables and
+  // the three vectors above, as STATE's name=value pairs (checkpoint.h lists
+  // the names); RestoreState is false with *err set on a bad value.
+  virtual void CaptureState(std::map<std::string, std::string>* kv) { (void)kv; }
+  virtual bool RestoreState(const std::map<std::string, std::string>& kv, std::string* err) {
+    (void)kv;
+    (void)err;
+    return true;
+  }
+  // One table at a time, then TablesSet() once: what set_embeddings does.
+  void SetTable(int side, const MatrixXf& m) { dev_->Set(side, m); }
+  void TablesSet() { OnEmbeddingsSet(); }
+  // The saved vectors (omega / item_reg: nullptr for a model without dual
+  // state); with the saved run's tuples also |H_u| (ComputeHistoryStats, whose
+  // item_reg_ is then replaced by the saved one: the same values).
+  void RestoreVectors(const float* loss, const float* omega, const float* item_reg,
+                      const Dataset* data) {
+    if (data && omega) ComputeHistoryStats(*data);
+    std::memcpy(user_loss_.data(), loss, sizeof(float) * (size_t)user_loss_.size());
+    if (omega) std::memcpy(dual_weight_.data(), omega, sizeof(float) * (size_t)dual_weight_.size());
+    if (item_reg) std::memcpy(item_reg_.data(), item_reg, sizeof(float) * (size_t)item_reg_.size());
+  }
 
   // The model's projection of held-out users (the fold-in of its
   // EvaluateDataset: ials.h:148-174 and the model variants): row r of `csr`
@@ -114,6 +141,37 @@ class DeviceModel : public Recommender {
   }
 
   virtual void OnEmbeddingsSet() {}
+
+  // STATE values (checkpoint.h): a float travels as its bit pattern.
+  static std::string FloatBits(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, 4);
+    return std::to_string(b);
+  }
+  // The u64 / float named `name`; false with *err set when absent or malformed.
+  static bool StateU64(const std::map<std::string, std::string>& kv, const char* name,
+                       uint64_t max, uint64_t* v, std::string* err) {
+    const auto it = kv.find(name);
+    char* e = nullptr;
+    errno = 0;
+    const unsigned long long x =
+        it == kv.end() || it->second.empty() || it->second[0] == '-' ? 0
+                                                                     : strtoull(it->second.c_str(), &e, 10);
+    if (!e || *e || errno || x > max) {
+      *err = std::string(name) + " is missing or malformed";
+      return false;
+    }
+    *v = x;
+    return true;
+  }
+  static bool StateFloatBits(const std::map<std::string, std::string>& kv, const char* name,
+                             float* x, std::string* err) {
+    uint64_t b;
+    if (!StateU64(kv, name, UINT32_MAX, &b, err)) return false;
+    const uint32_t b32 = (uint32_t)b;
+    std::memcpy(x, &b32, 4);
+    return true;
+  }
 
   // FoldIn of the models that project with one solve (ials.h:148-185 and its
   // variants): the EVAL rows solved with `params`.

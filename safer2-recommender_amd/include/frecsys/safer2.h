@@ -14,6 +14,9 @@
 #include <cstdlib>
 #include <future>
 #include <random>
+#include <sstream>
+#include <string>
+#include <map>
 #include <tuple>
 #include <vector>
 
@@ -334,7 +337,64 @@ class SAFER2Recommender : public detail::DeviceModel {
   float xi() const { return prev_xi_; }
   const VectorXf& dual_weight() const { return dual_weight_; }
 
+  // xi, the weighted-Gramian tag and the SNR generator.  Indices already
+  // drawn ahead from snr_rng_ (StartSnrDraws) belong to the generator's
+  // state: the generator has moved past them and ComputeXi has not used them
+  // yet, so they are saved beside it and handed to the next ComputeXi as a
+  // ready future.  Between two Train() calls none are pending (each call
+  // consumes what it started); the case is kept exact all the same.
+  void CaptureState(std::map<std::string, std::string>* kv) override {
+    (*kv)["xi_bits"] = FloatBits(prev_xi_);
+    (*kv)["weight_epoch"] = std::to_string(weight_epoch_);
+    if (snr_draws_.valid()) {
+      const std::vector<int> idx = snr_draws_.get();  // joins the helper thread
+      SetPendingDraws(idx);
+      std::string s;
+      for (int v : idx) s += (s.empty() ? "" : " ") + std::to_string(v);
+      (*kv)["snr_pending"] = s;
+    }
+    std::ostringstream os;
+    os << snr_rng_;
+    (*kv)["snr_rng"] = os.str();
+  }
+  bool RestoreState(const std::map<std::string, std::string>& kv, std::string* err) override {
+    if (!StateFloatBits(kv, "xi_bits", &prev_xi_, err) ||
+        !StateU64(kv, "weight_epoch", UINT64_MAX, &weight_epoch_, err))
+      return false;
+    const auto rng = kv.find("snr_rng");
+    std::mt19937 g;
+    std::istringstream is(rng == kv.end() ? std::string() : rng->second);
+    if (!(is >> g)) {
+      *err = "snr_rng is missing or malformed";
+      return false;
+    }
+    if (snr_draws_.valid()) snr_draws_.get();  // drawn from the generator being replaced
+    const auto pend = kv.find("snr_pending");
+    if (pend != kv.end()) {
+      std::vector<int> idx;
+      std::istringstream ps(pend->second);
+      long long v;
+      while (ps >> v) {
+        if (v < 0 || v >= num_users_) break;
+        idx.push_back((int)v);
+      }
+      if (!ps.eof() || idx.size() > ((size_t)1 << 28)) {
+        *err = "snr_pending is malformed or out of range";
+        return false;
+      }
+      SetPendingDraws(idx);
+    }
+    snr_rng_ = g;
+    return true;
+  }
+
  protected:
+  void SetPendingDraws(const std::vector<int>& idx) {
+    std::promise<std::vector<int>> p;
+    p.set_value(idx);
+    snr_draws_ = p.get_future();
+  }
+
   void OnEmbeddingsSet() override { dev_->Gramian(DeviceContext::ITEM); }
 
  protected:

@@ -10,13 +10,19 @@
 #include <string>
 #include <vector>
 
+#include "frecsys/checkpoint.h"
 #include "frecsys/factory.h"
 #include "frecsys_model.h"
 
 struct frecsys_model {
   std::string name;
-  std::unique_ptr<frecsys::Dataset> train;
+  frecsys::checkpoint::Config config;       // what a checkpoint's CONFIG holds
+  std::unique_ptr<frecsys::Dataset> train;  // null: loaded without tuples (serve-only)
   std::unique_ptr<frecsys::Recommender> rec;
+  int64_t epochs = 0;            // Train() calls so far, a loaded model's included
+  bool restored = false;         // loaded in its saved state: already initialised
+  int64_t n_tuples = 0;          // of a loaded model's file, for a save without a dataset
+  uint64_t tuples_checksum = 0;
 };
 
 namespace {
@@ -61,6 +67,132 @@ void frecsys_model_config_default(frecsys_model_config* c) {
   c->cg_max_iterations = p.cg_max_iterations;
 }
 
+}  // extern "C"
+
+namespace {
+
+namespace ck = frecsys::checkpoint;
+
+// The stored fields of a C config (device / world / rank / comm_id stay out).
+ck::Config stored_config(const frecsys_model_config& c, const std::string& name) {
+  ck::Config k;
+  k.model_name = name;
+  k.dim = c.dim;
+  k.l2_reg = c.l2_reg;
+  k.l2_reg_exp = c.l2_reg_exp;
+  k.uobs_weight = c.uobs_weight;
+  k.stdev = c.stdev;
+  k.alpha = c.alpha;
+  k.bandwidth = c.bandwidth;
+  k.stepsize = c.stepsize;
+  k.sampling_ratio = c.sampling_ratio;
+  k.block_size = c.block_size;
+  k.xi_iterations = c.xi_iterations;
+  k.pd_iterations = c.pd_iterations;
+  k.use_epanechnikov = c.use_epanechnikov != 0;
+  k.use_snr = c.use_snr != 0;
+  k.print_train_stats = c.print_train_stats != 0;
+  k.print_residual_stats = c.print_residual_stats != 0;
+  k.print_var_stats = c.print_var_stats != 0;
+  k.seed = c.seed;
+  k.parity_quirks = c.parity_quirks != 0;
+  k.use_cg = c.use_cg != 0;
+  k.cg_error_tolerance = c.cg_error_tolerance;
+  k.cg_max_iterations = c.cg_max_iterations;
+  return k;
+}
+// ... and back, on top of the defaults; model_name is left to the caller.
+void c_config(const ck::Config& k, frecsys_model_config* c) {
+  frecsys_model_config_default(c);
+  c->dim = k.dim;
+  c->l2_reg = k.l2_reg;
+  c->l2_reg_exp = k.l2_reg_exp;
+  c->uobs_weight = k.uobs_weight;
+  c->stdev = k.stdev;
+  c->alpha = k.alpha;
+  c->bandwidth = k.bandwidth;
+  c->stepsize = k.stepsize;
+  c->sampling_ratio = k.sampling_ratio;
+  c->block_size = k.block_size;
+  c->xi_iterations = k.xi_iterations;
+  c->pd_iterations = k.pd_iterations;
+  c->use_epanechnikov = k.use_epanechnikov;
+  c->use_snr = k.use_snr;
+  c->print_train_stats = k.print_train_stats;
+  c->print_residual_stats = k.print_residual_stats;
+  c->print_var_stats = k.print_var_stats;
+  c->seed = k.seed;
+  c->parity_quirks = k.parity_quirks;
+  c->use_cg = k.use_cg;
+  c->cg_error_tolerance = k.cg_error_tolerance;
+  c->cg_max_iterations = k.cg_max_iterations;
+}
+
+// The use_cg and block_size rules of a configuration, which need no device
+// (conditions the C++ constructors treat as fatal); FRECSYS_OK when fine.
+int config_check(const frecsys_model_config* c, const std::string& name) {
+  const bool cg_model = name == "ials" || name == "safer2";
+  if ((name == "ialspp" || name == "safer2pp") && (c->block_size < 1 || c->block_size > 128))
+    return model_fail(FRECSYS_ERR_INVALID, "block_size must be in [1, 128] (got " +
+                                               std::to_string(c->block_size) + ")");
+  if (c->use_cg && name == "erm_mf")  // fatal in the C++ constructor; before any device call
+    return model_fail(FRECSYS_ERR_UNSUPPORTED,
+                      "erm_mf: use_cg is not supported (the reference's BiCGSTAB path, "
+                      "erm_mf.h:103-145, is not built)");
+  if (c->use_cg && cg_model &&
+      (c->cg_max_iterations < 0 || !(c->cg_error_tolerance >= 0.0f)))
+    return model_fail(FRECSYS_ERR_INVALID,
+                      "cg_max_iterations and cg_error_tolerance must be >= 0 (and not NaN)");
+  if (c->use_cg && cg_model && c->dim > 256)
+    return model_fail(FRECSYS_ERR_UNSUPPORTED,
+                      "use_cg: the conjugate-gradient path is built for dim <= 256");
+  return FRECSYS_OK;
+}
+
+int device_check() {
+  int32_t ndev = 0;  // the C++ layer aborts on a missing device; report it instead
+  if (frecsys_device_count(&ndev) != FRECSYS_OK || ndev == 0)
+    return model_fail(FRECSYS_ERR_NO_DEVICE, "no HIP device visible");
+  return FRECSYS_OK;
+}
+
+// The model of a checked configuration, sized n_users x n_items, with its
+// dataset (nullptr: a serve-only model).
+std::unique_ptr<frecsys_model> make_model(const frecsys_model_config* c, const std::string& name,
+                                          int64_t n_users, int64_t n_items,
+                                          std::unique_ptr<frecsys::Dataset> train) {
+  frecsys::DeviceOptions o;
+  o.seed = c->seed;
+  o.device = c->device;
+  o.parity_quirks = c->parity_quirks != 0;
+  o.world = c->world;
+  o.rank = c->rank;
+  if (c->comm_id) {
+    o.has_comm_id = true;
+    std::memcpy(o.comm_id.data(), c->comm_id, 128);
+  }
+  auto m = std::make_unique<frecsys_model>();
+  m->name = name;
+  m->config = stored_config(*c, name);
+  m->train = std::move(train);
+  m->rec.reset(frecsys::MakeRecommender(name, (int)n_users, (int)n_items, ck::ToParams(m->config), o));
+  return m;
+}
+
+// exclude_seen / Train() need the training tuples: a model loaded without
+// them answers with an error instead of reaching the C++ layer, where a
+// failed device call is fatal.
+int needs_data(const frecsys_model* m, const char* what) {
+  if (m->train) return FRECSYS_OK;
+  return model_fail(FRECSYS_ERR_INVALID,
+                    std::string(what) + ": the model was loaded without training tuples "
+                                        "(serve-only): no training and no exclude_seen");
+}
+
+}  // namespace
+
+extern "C" {
+
 int frecsys_model_create(const frecsys_model_config* c, const int32_t* users, const int32_t* items,
                          int64_t n_tuples, frecsys_model** out) {
   if (!c || !out || n_tuples <= 0 || !users || !items || !c->model_name)
@@ -74,71 +206,168 @@ int frecsys_model_create(const frecsys_model_config* c, const int32_t* users, co
   for (int64_t k = 0; k < n_tuples; ++k)
     if (users[k] < 0 || items[k] < 0)
       return model_fail(FRECSYS_ERR_INVALID, "negative id in tuple " + std::to_string(k));
-  const bool cg_model = name == "ials" || name == "safer2";
-  if (c->use_cg && name == "erm_mf")  // fatal in the C++ constructor; before any device call
-    return model_fail(FRECSYS_ERR_UNSUPPORTED,
-                      "erm_mf: use_cg is not supported (the reference's BiCGSTAB path, "
-                      "erm_mf.h:103-145, is not built)");
-  if (c->use_cg && cg_model &&
-      (c->cg_max_iterations < 0 || !(c->cg_error_tolerance >= 0.0f)))
-    return model_fail(FRECSYS_ERR_INVALID,
-                      "cg_max_iterations and cg_error_tolerance must be >= 0 (and not NaN)");
-  if (c->use_cg && cg_model && c->dim > 256)
-    return model_fail(FRECSYS_ERR_UNSUPPORTED,
-                      "use_cg: the conjugate-gradient path is built for dim <= 256");
-  int32_t ndev = 0;  // the C++ layer aborts on a missing device; report it instead
-  if (frecsys_device_count(&ndev) != FRECSYS_OK || ndev == 0)
-    return model_fail(FRECSYS_ERR_NO_DEVICE, "no HIP device visible");
-  frecsys::ModelParams p;
-  p.dim = c->dim;
-  p.l2_reg = c->l2_reg;
-  p.l2_reg_exp = c->l2_reg_exp;
-  p.uobs_weight = c->uobs_weight;
-  p.stdev = c->stdev;
-  p.alpha = c->alpha;
-  p.bandwidth = c->bandwidth;
-  p.stepsize = c->stepsize;
-  p.sampling_ratio = c->sampling_ratio;
-  p.block_size = c->block_size;
-  p.xi_iterations = c->xi_iterations;
-  p.pd_iterations = c->pd_iterations;
-  p.use_epanechnikov = c->use_epanechnikov != 0;
-  p.use_snr = c->use_snr != 0;
-  p.print_train_stats = c->print_train_stats != 0;
-  p.print_residual_stats = c->print_residual_stats != 0;
-  p.print_var_stats = c->print_var_stats != 0;
-  p.use_cg = c->use_cg != 0;
-  p.cg_error_tolerance = c->cg_error_tolerance;
-  p.cg_max_iterations = c->cg_max_iterations;
-  frecsys::DeviceOptions o;
-  o.seed = c->seed;
-  o.device = c->device;
-  o.parity_quirks = c->parity_quirks != 0;
-  o.world = c->world;
-  o.rank = c->rank;
-  if (c->comm_id) {
-    o.has_comm_id = true;
-    std::memcpy(o.comm_id.data(), c->comm_id, 128);
-  }
-  auto m = std::make_unique<frecsys_model>();
-  m->name = name;
-  m->train = std::make_unique<frecsys::Dataset>(std::vector<int32_t>(users, users + n_tuples),
-                                                std::vector<int32_t>(items, items + n_tuples));
-  m->rec.reset(frecsys::MakeRecommender(name, m->train->max_user() + 1,
-                                        m->train->max_item() + 1, p, o));
-  *out = m.release();
+  if (int rc = config_check(c, name)) return rc;
+  if (int rc = device_check()) return rc;
+  auto train = std::make_unique<frecsys::Dataset>(std::vector<int32_t>(users, users + n_tuples),
+                                                  std::vector<int32_t>(items, items + n_tuples));
+  const int64_t nu = train->max_user() + 1, ni = train->max_item() + 1;
+  *out = make_model(c, name, nu, ni, std::move(train)).release();
   return FRECSYS_OK;
 }
 
 int frecsys_model_initialize(frecsys_model* m) {
   if (!m) return model_fail(FRECSYS_ERR_INVALID, "null model");
+  if (m->restored) return FRECSYS_OK;  // a loaded model comes back initialised
+  if (int rc = needs_data(m, "frecsys_model_initialize")) return rc;
   frecsys::InitializeRecommender(m->name, m->rec.get(), *m->train);
   return FRECSYS_OK;
 }
 
 int frecsys_model_train(frecsys_model* m, int32_t epochs) {
   if (!m || epochs < 0) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_train: bad arguments");
-  for (int32_t e = 0; e < epochs; ++e) m->rec->Train(*m->train);
+  if (int rc = needs_data(m, "frecsys_model_train")) return rc;
+  for (int32_t e = 0; e < epochs; ++e) {
+    m->rec->Train(*m->train);
+    ++m->epochs;
+  }
+  return FRECSYS_OK;
+}
+
+int64_t frecsys_model_epochs(const frecsys_model* m) { return m ? m->epochs : -1; }
+
+int frecsys_model_save(frecsys_model* m, const char* path, int32_t flags) {
+  if (!m || !path || !*path || (flags & ~FRECSYS_SAVE_NO_DATA))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_save: bad arguments");
+  ck::Tuples t;
+  t.n = m->n_tuples;
+  t.checksum = m->tuples_checksum;
+  if (m->train) {
+    t.n = m->train->num_tuples();
+    t.checksum = ck::TuplesChecksum(m->train->users().data(), m->train->items().data(), t.n);
+    if (!(flags & FRECSYS_SAVE_NO_DATA)) {
+      t.users = m->train->users().data();
+      t.items = m->train->items().data();
+    }
+  }
+  std::string err;
+  const ck::Status s = ck::SaveModel(m->config, frecsys::AsDeviceModel(m->rec.get()), t, m->epochs,
+                                     path, &err);
+  return s == ck::kOk ? FRECSYS_OK : model_fail((int)s, "frecsys_model_save: " + err);
+}
+
+int frecsys_model_file_info(const char* path, int32_t verify, frecsys_model_file_info_t* info) {
+  if (!path || !info) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_file_info: bad arguments");
+  ck::Reader r;
+  std::string err;
+  const ck::Status s = r.Open(path, verify != 0, &err);
+  if (s != ck::kOk) return model_fail((int)s, err);
+  const ck::Info& in = r.info();
+  std::memset(info, 0, sizeof(*info));
+  snprintf(info->model_name, sizeof(info->model_name), "%s", in.config.model_name.c_str());
+  c_config(in.config, &info->config);
+  info->config.model_name = info->model_name;
+  info->n_users = in.n_users;
+  info->n_items = in.n_items;
+  info->n_tuples = in.n_tuples;
+  info->epochs_trained = in.epochs_trained;
+  info->flags = in.flags;
+  info->tuples_checksum = in.tuples_checksum;
+  info->version = in.version;
+  return FRECSYS_OK;
+}
+
+int frecsys_model_load(const char* path, const frecsys_model_config* cfg, const int32_t* users,
+                       const int32_t* items, int64_t n_tuples, int32_t flags,
+                       frecsys_model** out) {
+  const std::string w = "frecsys_model_load: ";
+  if (!path || !out || (flags & ~FRECSYS_LOAD_TABLES_ONLY) || (users != nullptr) != (items != nullptr) ||
+      (users && n_tuples <= 0))
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  *out = nullptr;
+  const bool tables_only = (flags & FRECSYS_LOAD_TABLES_ONLY) != 0;
+  // the whole file is validated before the first device call
+  ck::Reader r;
+  std::string err;
+  ck::Status s = r.Open(path, true, &err);
+  if (s != ck::kOk) return model_fail((int)s, w + err);
+  const ck::Info& in = r.info();
+  frecsys_model_config c;
+  const std::string name = in.config.model_name;
+  if (cfg) {
+    c = *cfg;
+    if (!c.model_name || name != c.model_name)
+      return model_fail(FRECSYS_ERR_INVALID, w + "model_name differs from the file's (" + name + ")");
+    if (c.dim != in.config.dim)
+      return model_fail(FRECSYS_ERR_INVALID, w + "dim " + std::to_string(c.dim) +
+                                                 " differs from the file's (" +
+                                                 std::to_string(in.config.dim) + ")");
+    if (!tables_only && (c.parity_quirks != 0) != (in.config.parity_quirks != 0))
+      return model_fail(FRECSYS_ERR_INVALID, w + "parity_quirks differs from the file's");
+  } else {
+    c_config(in.config, &c);
+  }
+  c.model_name = name.c_str();
+  if (int rc = config_check(&c, name)) return rc;
+
+  std::unique_ptr<frecsys::Dataset> train;
+  int64_t nu = in.n_users, ni = in.n_items;
+  if (users) {
+    int32_t mu = -1, mi = -1;
+    for (int64_t k = 0; k < n_tuples; ++k) {
+      if (users[k] < 0 || items[k] < 0)
+        return model_fail(FRECSYS_ERR_INVALID, w + "negative id in tuple " + std::to_string(k));
+      mu = std::max(mu, users[k]);
+      mi = std::max(mi, items[k]);
+    }
+    if (tables_only) {
+      if (mu + 1 < in.n_users || mi + 1 < in.n_items)
+        return model_fail(FRECSYS_ERR_INVALID,
+                          w + "the tuples span fewer users or items than the stored tables hold");
+      nu = (int64_t)mu + 1;
+      ni = (int64_t)mi + 1;
+    } else {
+      if (n_tuples != in.n_tuples)
+        return model_fail(FRECSYS_ERR_INVALID,
+                          w + "the tuples passed are not the saved run's: " + std::to_string(n_tuples) +
+                              " tuples, the file was written for " + std::to_string(in.n_tuples));
+      if (ck::TuplesChecksum(users, items, n_tuples) != in.tuples_checksum || mu >= in.n_users ||
+          mi >= in.n_items)
+        return model_fail(FRECSYS_ERR_INVALID,
+                          w + "the tuples passed are not the saved run's: their checksum differs "
+                              "from the file's tuples_checksum (other ids or another order)");
+    }
+    train = std::make_unique<frecsys::Dataset>(std::vector<int32_t>(users, users + n_tuples),
+                                               std::vector<int32_t>(items, items + n_tuples));
+  } else if (tables_only) {
+    return model_fail(FRECSYS_ERR_INVALID, w + "FRECSYS_LOAD_TABLES_ONLY needs the caller's tuples");
+  } else if (r.has_tuples()) {
+    std::vector<int32_t> u((size_t)in.n_tuples), it((size_t)in.n_tuples);
+    if ((s = r.Read("USERS", u.data(), u.size() * 4, &err)) != ck::kOk ||
+        (s = r.Read("ITEMS", it.data(), it.size() * 4, &err)) != ck::kOk)
+      return model_fail((int)s, w + err);
+    // read a second time after the verification pass: checked again
+    if (ck::TuplesChecksum(u.data(), it.data(), in.n_tuples) != in.tuples_checksum)
+      return model_fail(FRECSYS_ERR_INVALID, w + "the file changed while it was read");
+    for (int64_t k = 0; k < in.n_tuples; ++k)
+      if (u[k] < 0 || u[k] >= in.n_users || it[k] < 0 || it[k] >= in.n_items)
+        return model_fail(FRECSYS_ERR_INVALID, w + "the file changed while it was read");
+    train = std::make_unique<frecsys::Dataset>(std::move(u), std::move(it));
+  }
+  if (int rc = device_check()) return rc;
+
+  auto m = make_model(&c, name, nu, ni, std::move(train));
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  if (tables_only) {
+    s = ck::RestoreTables(r, dm, &err);
+  } else {
+    s = ck::RestoreModel(r, dm, m->train.get(), &err);
+    m->restored = true;
+    m->epochs = in.epochs_trained;
+    m->n_tuples = in.n_tuples;
+    m->tuples_checksum = in.tuples_checksum;
+  }
+  if (s != ck::kOk) return model_fail((int)s, w + err);
+  *out = m.release();
   return FRECSYS_OK;
 }
 
@@ -185,6 +414,8 @@ int frecsys_model_recommend(frecsys_model* m, const int64_t* users, int64_t n, i
                             float* scores) {
   if (!m || n < 0 || (n > 0 && !users))
     return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend: bad arguments");
+  if (exclude_seen)
+    if (int rc = needs_data(m, "frecsys_model_recommend")) return rc;
   frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
   const int rc = dev.TryRecommend(FRECSYS_SIDE_USER, users, n, k,
                                   exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
@@ -239,6 +470,8 @@ int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_
                                   float* scores) {
   if (!m || n < 0 || (n > 0 && !users))
     return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_rank_candidates: bad arguments");
+  if (exclude_seen)
+    if (int rc = needs_data(m, "frecsys_model_rank_candidates")) return rc;
   frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
   const int rc = dev.TryRankCandidates(FRECSYS_SIDE_USER, users, n, cand_ptr, cand_items, k,
                                        exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
@@ -440,6 +673,8 @@ int evaluate_lists(frecsys_model* m, const std::string& w, const int64_t* users,
                    const float* alpha_list, int32_t na, int32_t exclude_seen,
                    const uint8_t* item_mask, float* recall, float* ndcg, float* summary) {
   if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  if (exclude_seen && !fold_in)
+    if (int rc = needs_data(m, "frecsys_model_evaluate_candidates / _sampled")) return rc;
   frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
   frecsys::DeviceContext& dev = dm->device();
   const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
@@ -476,6 +711,8 @@ int evaluate_ranks(frecsys_model* m, const std::string& w, const int64_t* users,
                    int32_t na, int32_t exclude_seen, const uint8_t* item_mask, int32_t* rank,
                    int32_t* eligible, float* mrr, float* auc, float* summary) {
   if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  if (exclude_seen && !fold_in)
+    if (int rc = needs_data(m, "frecsys_model_evaluate_ranks")) return rc;
   frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
   frecsys::DeviceContext& dev = dm->device();
   const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
@@ -584,6 +821,8 @@ int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
                            float* recall, float* ndcg, float* summary) {
   if (!m || (n > 0 && !users))
     return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate: bad arguments");
+  if (exclude_seen)
+    if (int rc = needs_data(m, "frecsys_model_evaluate")) return rc;
   frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
   const std::string e =
       evaluate_args_error(n, dev.rows(frecsys::DeviceContext::ITEM), gt_ptr, gt_items, k_list, nk,

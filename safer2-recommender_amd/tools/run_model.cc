@@ -11,6 +11,12 @@
 // RANK / LOCAL_RANK from the environment (torchrun-style), RCCL id through
 // FRECSYS_COMM_FILE.  iALS++ / SAFER2++ (ialspp.h, safer2pp.h) run on the
 // GPU block-step kernels.
+//
+// Checkpoints (frecsys/checkpoint.h): --save_model PATH writes the model after
+// the last epoch; --load_model PATH resumes one: the model and its settings
+// come from the file, --train_data supplies the tuples (checked against the
+// file's count and checksum), Initialize is skipped, --epoch more epochs are
+// trained and the "Epoch: N" lines continue from the stored count.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -19,6 +25,7 @@
 #include <string>
 #include <sys/stat.h>
 
+#include "frecsys/checkpoint.h"
 #include "frecsys/factory.h"
 
 namespace {
@@ -163,6 +170,8 @@ int main(int argc, char* argv[]) {
   app.add("--seed", "-1");
   app.add("--device", "-1");
   app.add("--parity_quirks", "1");
+  app.add("--save_model", "");
+  app.add("--load_model", "");
   if (!app.parse(argc, argv)) return 106;
 
   std::string model_name = app.str("--model_name");
@@ -188,14 +197,56 @@ int main(int argc, char* argv[]) {
   opts.seed = std::atoll(app.str("--seed").c_str());
   opts.device = app.i("--device");
   opts.parity_quirks = app.b("--parity_quirks");
-  frecsys::Recommender* recommender = frecsys::MakeRecommender(
-      model_name, train.max_user() + 1, train.max_item() + 1, model_params(app), opts);
-  setbuf(stdout, NULL);
+  namespace ck = frecsys::checkpoint;
+  const std::string load_path = app.str("--load_model"), save_path = app.str("--save_model");
+  const uint64_t train_checksum =
+      load_path.empty() && save_path.empty()
+          ? 0
+          : ck::TuplesChecksum(train.users().data(), train.items().data(), train.num_tuples());
+  ck::Config config;
+  frecsys::Recommender* recommender = nullptr;
+  int first_epoch = 0;  // Train() calls before this run
+  if (load_path.empty()) {
+    config = ck::FromParams(model_name, model_params(app), opts.seed, opts.parity_quirks);
+    recommender = frecsys::MakeRecommender(model_name, train.max_user() + 1, train.max_item() + 1,
+                                           model_params(app), opts);
+    setbuf(stdout, NULL);
+    frecsys::InitializeRecommender(model_name, recommender, train);  // run_model.cc:246-257
+  } else {
+    ck::Reader file;
+    std::string err;
+    if (file.Open(load_path, true, &err) != ck::kOk) {
+      fprintf(stderr, "--load_model: %s\n", err.c_str());
+      return 105;
+    }
+    const ck::Info& in = file.info();
+    if (in.config.model_name != model_name) {
+      fprintf(stderr, "--load_model: %s holds a %s model, --model_name is %s\n", load_path.c_str(),
+              in.config.model_name.c_str(), model_name.c_str());
+      return 105;
+    }
+    if (in.n_tuples != train.num_tuples() || in.tuples_checksum != train_checksum ||
+        train.max_user() >= in.n_users || train.max_item() >= in.n_items) {
+      fprintf(stderr, "--load_model: --train_data is not the data %s was trained on (tuple count "
+                      "or tuples_checksum differs)\n", load_path.c_str());
+      return 105;
+    }
+    config = in.config;
+    opts.seed = config.seed;
+    opts.parity_quirks = config.parity_quirks != 0;
+    recommender = frecsys::MakeRecommender(model_name, (int)in.n_users, (int)in.n_items,
+                                           ck::ToParams(config), opts);
+    setbuf(stdout, NULL);
+    if (ck::RestoreModel(file, frecsys::AsDeviceModel(recommender), &train, &err) != ck::kOk) {
+      fprintf(stderr, "--load_model: %s\n", err.c_str());
+      return 105;
+    }
+    first_epoch = (int)in.epochs_trained;
+  }
 
-  frecsys::InitializeRecommender(model_name, recommender, train);  // run_model.cc:246-257
-  const int epochs = app.i("--epoch");
+  const int epochs = first_epoch + app.i("--epoch");
   const bool print_eval = app.b("--print_evaluation_stats");
-  for (int epoch = 0; epoch < epochs; ++epoch) {
+  for (int epoch = first_epoch; epoch < epochs; ++epoch) {
     auto t0 = std::chrono::steady_clock::now();
     recommender->Train(train);
     auto t1 = std::chrono::steady_clock::now();
@@ -203,6 +254,19 @@ int main(int argc, char* argv[]) {
         std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count();
     LOG(INFO) << fmt::format("Epoch: {0}, Timer: Train={1}", epoch, train_time);
     if (print_eval) evaluate(epoch, recommender, test_tr, test_te);
+  }
+  if (!save_path.empty()) {
+    ck::Tuples t;
+    t.users = train.users().data();
+    t.items = train.items().data();
+    t.n = train.num_tuples();
+    t.checksum = train_checksum;
+    std::string err;
+    if (ck::SaveModel(config, frecsys::AsDeviceModel(recommender), t, epochs, save_path, &err) !=
+        ck::kOk) {
+      fprintf(stderr, "--save_model: %s\n", err.c_str());
+      return 105;
+    }
   }
   LOG(INFO) << "Validation Results";
   evaluate(epochs, recommender, test_tr, test_te);
