@@ -478,6 +478,50 @@ int frecsys_rank_positions(frecsys_ctx* ctx, int32_t side, const int64_t* rows, 
  * item row per pair) + 12 pairs (ids) + 4 pairs (scores). */
 int frecsys_score_pairs(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
                         const int32_t* items, int64_t n_pairs, float* scores);
+/* Explanations (no reference counterpart): a score split exactly over the
+ * history entries of a row.  The projection frecsys_solve_side computes for
+ * `params` (kinds IALS and WEIGHTED_U) solves A x = b with
+ *   A = s_G G + sum_j c_j y_j y_j^T + lambda I,   b = sum_j c_j y_j
+ * over the history rows y_j of the row (s_G, c_j, lambda per kind as tabulated
+ * at frecsys_solve_side_cg), so the score of an item t is
+ *   v_t . x = sum_j contrib_j(t),   contrib_j(t) = c_j y_j^T A^-1 v_t.
+ * Query row i -- CSR row rows[i] of `side` (USER or EVAL), or row i when rows
+ * is NULL -- is explained for its targets tgt_items[tgt_ptr[i] ..
+ * tgt_ptr[i+1]); pairs are numbered in that order.  Solved against the ITEM
+ * table and G[ITEM] as the context holds them (frecsys_solve_side's contract
+ * on those sides; from_snapshot is ignored); the embeddings of `side` are
+ * neither read nor written.  Repeated rows and targets are allowed, every pair
+ * is independent.  score: [pairs], the sum of the pair's contributions (lane l
+ * of a wave adds the entries l, l + 64, ... in CSR order, then a fixed
+ * butterfly over the 64 partial sums) -- the score of the exact projection of
+ * that history against the current item table, not U[row] . V[t].  top_items /
+ * top_contrib: [pairs * top], the `top` (1..32) largest contributions by
+ * (contribution descending, CSR position ascending) with their history item
+ * ids, -1 / 0 behind the row's history length; a row with an empty history
+ * has score 0 and only fill.  full: NULL, or the h contributions of every pair
+ * in CSR order, pairs in order (sum over pairs of their row's h floats).  The
+ * bits of a pair depend on the row's history, the parameters and the tables
+ * only -- not on the batch, the other rows or targets, their grouping, `top`,
+ * FRECSYS_RECOMMEND_WS_MB or the side.  Rank-local at any world size: no
+ * collective.  Zero rows or zero targets return FRECSYS_OK without a launch.
+ * FRECSYS_ERR_INVALID, before any device call: a null context, side ITEM, a
+ * kind other than IALS / WEIGHTED_U, top out of range, a null pointer, no CSR
+ * on the side, a row id or target id out of range, tgt_ptr not starting at 0
+ * or not monotone.  FRECSYS_ERR_UNSUPPORTED: dim > 256.  FRECSYS_ERR_NOT_SPD:
+ * a failed pivot (entity via frecsys_last_error_entity).  Timer key "explain"
+ * (one launch group per batch); frecsys_work("explain"): per row with h
+ * entries and m targets h d^2 + d^3 / 3 + 2 d^2 m + 2 h d m flops, bytes = the
+ * history rows gathered (once to assemble, once per 32 targets) + the target
+ * rows. */
+int frecsys_explain(frecsys_ctx* ctx, int32_t side, const frecsys_solve_params* params,
+                    const int64_t* rows, int64_t n_rows, const int64_t* tgt_ptr,
+                    const int32_t* tgt_items, int32_t top, float* score, int32_t* top_items,
+                    float* top_contrib, float* full);
+/* Host-only: lengths[i] = the history length of CSR row rows[i] of `side` (row
+ * i when rows is NULL) as loaded -- what sizes frecsys_explain's `full`.
+ * FRECSYS_ERR_INVALID: no CSR on the side, a row id out of range. */
+int frecsys_csr_row_lengths(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                            int64_t* lengths);
 /* Ranking of caller-supplied candidate lists (the second stage of a
  * retrieve-then-rank pipeline; no reference counterpart): query row i --
  * rows[i] of `side`, or row i when rows is NULL -- ranks the DISTINCT eligible

@@ -117,6 +117,36 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
  * (frecsys_score_pairs, frecsys_hip.h; its errors). */
 int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
                         float* scores);
+/* Why an item scores what it does (frecsys_explain, frecsys_hip.h; its errors):
+ * for trained user users[i] (n of them, repeats allowed) and each of its
+ * targets tgt_items[tgt_ptr[i] .. tgt_ptr[i+1]) (tgt_ptr[0] = 0), the score
+ * split exactly over the user's training history: score: host [pairs],
+ * top_items / top_contrib: host [pairs * top] (top in 1..32: the largest
+ * contributions with their history item ids, -1 / 0 fill), full: NULL or the
+ * h contributions of every pair in CSR order.  The model supplies the solve
+ * parameters of its own fold-in (omega = 1 where the fold-in uses it) against
+ * the current item table and its Gramian.  `score` is therefore the score of
+ * the model's EXACT projection of that history against the current item table
+ * -- what frecsys_model_recommend_fold_in lists for the same history -- and not
+ * frecsys_model_score's U[user] . V[item]: a trained row of U was solved
+ * against the item table of the previous half-step.  iALS++ and SAFER2++ use
+ * the parameters of the objective their block steps descend, so theirs is the
+ * explanation of that objective's exact minimiser; their own fold-in stops
+ * after 8 block epochs and is only near it.  The training CSR must be loaded
+ * (the model trained here, or loaded with its tuples): FRECSYS_ERR_INVALID on
+ * a serve-only model. */
+int frecsys_model_explain(frecsys_model* m, const int64_t* users, int64_t n,
+                          const int64_t* tgt_ptr, const int32_t* tgt_items, int32_t top,
+                          float* score, int32_t* top_items, float* top_contrib, float* full);
+/* The same for n unseen users given by their histories (as
+ * frecsys_model_recommend_fold_in): the histories are loaded as the EVAL side
+ * of the context (the projected EVAL rows of an earlier fold-in are zeroed, as
+ * by any load) and target list i belongs to history row i.  Bit for bit
+ * frecsys_model_explain's result for a user with the same history. */
+int frecsys_model_explain_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                  const int32_t* hist_items, int64_t n, const int64_t* tgt_ptr,
+                                  const int32_t* tgt_items, int32_t top, float* score,
+                                  int32_t* top_items, float* top_contrib, float* full);
 /* The k best of each trained user's own candidate list (users[i]: a row of U;
  * cand_items[cand_ptr[i] .. cand_ptr[i+1]): the candidates of users[i],
  * cand_ptr[0] = 0; repeats count once) with their scores, items / scores:

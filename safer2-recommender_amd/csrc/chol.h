@@ -285,6 +285,81 @@ __device__ __forceinline__ f32x16 tile_pqT_x6(const float* P, const float* Q, in
   return u;
 }
 
+// The product without the transpose, u = P Q, in exact fp32 (the back
+// substitution of explain.hip against stored lower tiles): lane (lo, hi)
+// supplies k = 2s + hi of row lo of P and of column lo of Q.
+__device__ __forceinline__ f32x16 tile_pq(const float* P, const float* Q, int lo, int hi) {
+  f32x16 u = f32x16{0.f};
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    const f32x4v pv = row_gran(P, lo, g);
+    u = mfma32(hi ? pv[1] : pv[0], Q[sw(4 * g + hi, lo)], u);
+    u = mfma32(hi ? pv[3] : pv[2], Q[sw(4 * g + 2 + hi, lo)], u);
+  }
+  return u;
+}
+
+// ---------------------------------------------------------------------
+// The factorisation of chol_solve_tiles alone, for a tile count known at run
+// time (explain.hip: the factor is kept and substituted against afterwards):
+// A = L L^T for the SPD matrix whose lower T (T + 1) / 2 tiles sit in LDS
+// (tile (I, J) at tiles + tidx(I, J) * 1024, swizzled), NW waves.  The same
+// phases between the same barriers -- panel TRSM as a product with L_pp^-1,
+// wave 0 updating and factoring tile (p+1, p+1) while the others finish the
+// trailing update -- with the split-bf16 products and the blocked diagonal
+// factor of the dataflow solve.
+// In: tiles, *flag = 0, a barrier since they were written.
+// Out: tile (I, J), I > J, holds L_IJ and tile (p, p) holds L_pp^-1 (upper
+// part zero); *flag = 1 on a non-positive pivot.  Ends with a barrier.
+// ---------------------------------------------------------------------
+template <int NW>
+__device__ __forceinline__ void chol_factor_tiles(float* tiles, int T, int* flag, int tid) {
+  const int lane = tid & 63, lo = lane & 31, hi = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (wave == 0) {
+    if (!diag_factor_inv<true>(tiles, lane) && lane == 0) flag[0] = 1;
+  }
+  lds_barrier();
+#pragma unroll 1
+  for (int p = 0; p + 1 < T; ++p) {
+    const float* Tpp = tiles + tidx(p, p) * 1024;
+    const int npan = T - 1 - p;
+    // TRSM by MFMA: L_Ip = A_Ip (L_pp^-1)^T
+    for (int t = wave; t < npan; t += NW) {
+      float* Aip = tiles + tidx(p + 1 + t, p) * 1024;
+      const f32x16 u = tile_pqT_x6(Aip, Tpp, lo, hi);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) Aip[sw(acc_row(q, hi), lo)] = u[q];
+    }
+    lds_barrier();
+    // trailing update A_IJ -= L_Ip L_Jp^T; tile (p+1, p+1) is index 0
+    const int ntr = npan * (npan + 1) / 2;
+    if (wave == 0) {
+      float* A11 = tiles + tidx(p + 1, p + 1) * 1024;
+      const float* L1 = tiles + tidx(p + 1, p) * 1024;
+      const f32x16 u = tile_pqT_x6<true>(L1, L1, lo, hi);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) A11[sw(acc_row(q, hi), lo)] -= u[q];
+      wave_lds_sync();
+      if (!diag_factor_inv<true>(A11, lane) && lane == 0) flag[0] = 1;
+    } else {
+      for (int tt = wave; tt < ntr; tt += NW - 1) {
+        int Ir = 0;
+        while ((Ir + 1) * (Ir + 2) / 2 <= tt) ++Ir;
+        const int Jr = tt - Ir * (Ir + 1) / 2;
+        const int I = p + 1 + Ir, J = p + 1 + Jr;
+        const float* Li = tiles + tidx(I, p) * 1024;
+        const float* Lj = tiles + tidx(J, p) * 1024;
+        const f32x16 u = I == J ? tile_pqT_x6<true>(Li, Li, lo, hi) : tile_pqT_x6(Li, Lj, lo, hi);
+        float* Aij = tiles + tidx(I, J) * 1024;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) Aij[sw(acc_row(q, hi), lo)] -= u[q];
+      }
+    }
+    lds_barrier();
+  }
+}
+
 // ---------------------------------------------------------------------
 // Barrier-phased solve (pp.hip's block steps, TB <= 4 tiles): A x = b for
 // the SPD matrix whose lower T(T+1)/2 tiles sit in LDS (tile (I, J) at

@@ -199,6 +199,54 @@ size_t cg_lds_bytes(int Dp);
 void cg_plan_batches(const QueueRec* order, int64_t n, std::vector<int32_t>* bstart);
 hipError_t launch_cg(const CgArgs& a, hipStream_t s);
 
+// Explanations (explain.hip; Dp <= 256): per query row the d x d system of
+// frecsys_solve_side (kinds IALS / WEIGHTED_U) assembled and factored once,
+// W = A^-1 V_targets^T by substitution in groups of kExplainGroup targets,
+// and contrib[j][t] = c_j (y_j . w_t) for every history entry j.  Query row i
+// of the batch is row qrows[r0 + i] (or r0 + i) of the side's CSR; its
+// targets are tgt[tgt_ptr[r0 + i] - tgt_base .. tgt_ptr[r0 + i + 1] - tgt_base).
+// Pair p of the batch (the targets of its rows in order) has its h
+// contributions, in CSR order, at contrib[coff[i] + t h ..), t its index
+// among the row's targets.  launch_explain fills contrib; launch_explain_select
+// reads it: score[p] (the sum of the pair's contributions), and the `top`
+// largest by (contribution descending, CSR position ascending) with their
+// history item ids, -1 / 0 behind them.
+constexpr int kExplainGroup = 32;   // right-hand sides of one substitution
+constexpr int kExplainChunk = 256;  // history rows one sweep of the second pass takes (8 waves x 32)
+constexpr int kExplainMaxTop = 32;
+struct ExplainArgs {
+  int kind;                  // FRECSYS_KIND_IALS / WEIGHTED_U
+  int Dp;
+  const int64_t* row_ptr;    // CSR of the explained side
+  const int32_t* col;
+  const int64_t* qrows;      // CSR row of every query row of the call, or nullptr
+  int64_t r0, n;             // this batch: query rows r0 .. r0 + n - 1
+  const int64_t* tgt_ptr;    // [rows of the call + 1]
+  const int32_t* tgt;        // the batch's target ids, each in [0, n_other)
+  int64_t tgt_base;          // tgt_ptr[r0]
+  const int64_t* coff;       // [n] first contribution of every row of the batch
+  const int32_t* prow;       // [pairs of the batch] row of the batch (select)
+  const int32_t* order;      // [n] the rows of the batch, most work first (a permutation)
+  const float* X;            // items, ld = Dp
+  int64_t n_other;
+  const float* G;            // Dp x Dp Gramian of the items
+  float reg, reg_exp, w;
+  int lambda_is_reg;
+  const float* entity_weight;  // [rows of side] omega, or nullptr (-> 1)
+  float* wws;                // [workgroups][kExplainGroup][explain_ld(Dp)]: W of the group in flight
+  float* contrib;            // the batch's contributions
+  unsigned long long* fail;  // atomicMin(entity + 1) on a non-SPD pivot
+  int top;                   // 1 .. kExplainMaxTop
+  float* score;              // [pairs of the batch]
+  int32_t* top_items;        // [pairs][top]
+  float* top_contrib;        // [pairs][top]
+};
+int explain_ld(int Dp);       // floats per row of a W slot: Dp rounded up to whole tiles
+size_t explain_lds_bytes(int Dp);
+// `grid` workgroups, each with its own W slot, take the rows grid apart.
+hipError_t launch_explain(const ExplainArgs& a, int grid, hipStream_t s);
+hipError_t launch_explain_select(const ExplainArgs& a, int64_t n_pairs, hipStream_t s);
+
 hipError_t launch_solve(int Dp, const SolveArgs& a, hipStream_t s);
 // Diagnostics: n 32x32 tiles (row-major) -> L^-1 of each (blk: the
 // MFMA-blocked diagonal factor, else the lane recurrence), ok[n].

@@ -1,11 +1,11 @@
 // serve.hip -- host side of the ranking and evaluation calls of the C-ABI
 // (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
 // frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
-// frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions, and the
-// host-only frecsys_sample_negatives, frecsys_list_metrics,
-// frecsys_position_metrics, frecsys_metric_cvar.  No kernels here:
-// recommend.hip, similar.hip, rerank.hip, sampled.hip, metrics.hip and
-// positions.hip hold them (kernels.h).
+// frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions,
+// frecsys_explain, and the host-only frecsys_sample_negatives,
+// frecsys_list_metrics, frecsys_position_metrics, frecsys_metric_cvar.  No
+// kernels here: recommend.hip, similar.hip, rerank.hip, sampled.hip,
+// metrics.hip, positions.hip and explain.hip hold them (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -23,7 +23,9 @@
 //     while their fixed bytes and ids fit the budget (cut_by_candidates);
 //   positions (rank_positions): the same cut by the ground-truth entries;
 //   sampled lists (sampled_metrics): rows by their fixed bytes within half the
-//     budget, then sub-batches whose ids fit the other half.
+//     budget, then sub-batches whose ids fit the other half;
+//   explanations (explain): the same cut by the contributions, h floats per
+//     (row, target) pair.
 // Rows are independent, so the batch size never changes a result.
 //
 // Checks.  Each entry point keeps its own order of checks and its own point
@@ -1258,6 +1260,187 @@ int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int
         counter++;
       }
     }
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_csr_row_lengths(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                            int64_t* lengths) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "csr_row_lengths: null context");
+  const std::string w = "csr_row_lengths: ";
+  if (side < 0 || side > 2) return fail(c, FRECSYS_ERR_INVALID, w + "bad side");
+  if (n_rows < 0 || (n_rows > 0 && !lengths))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments");
+  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, w + "no CSR loaded on the side");
+  const std::vector<int64_t>& hrp = side == 2 ? c->host_rp_eval : c->host_rp[side];
+  const int64_t ns = (int64_t)hrp.size() - 1;
+  if (!rows && n_rows > ns) return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
+  for (int64_t i = 0; i < n_rows; ++i) {
+    const int64_t e = rows ? rows[i] : i;
+    if (e < 0 || e >= ns)
+      return fail(c, FRECSYS_ERR_INVALID, w + "row id " + std::to_string(e) + " out of range");
+    lengths[i] = hrp[(size_t)e + 1] - hrp[(size_t)e];
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_explain(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
+                    const int64_t* rows, int64_t n_rows, const int64_t* tgt_ptr,
+                    const int32_t* tgt_items, int32_t top, float* score, int32_t* top_items,
+                    float* top_contrib, float* full) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "explain: null context");
+  const std::string w = "explain: ";
+  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, nullptr, 0, 0);
+  if (rc) return rc;
+  if (!p) return fail(c, FRECSYS_ERR_INVALID, w + "null params");
+  if (p->kind != FRECSYS_KIND_IALS && p->kind != FRECSYS_KIND_WEIGHTED_U)
+    return fail(c, FRECSYS_ERR_INVALID, w + "kind must be IALS or WEIGHTED_U");
+  if (top < 1 || top > kExplainMaxTop)
+    return fail(c, FRECSYS_ERR_INVALID,
+                w + "top must be in [1, " + std::to_string(kExplainMaxTop) + "]");
+  if (c->dim > 256)
+    return fail(c, FRECSYS_ERR_UNSUPPORTED,
+                w + "explanations are built for dim <= 256 (dim " + std::to_string(c->dim) + ")");
+  if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n_rows == 0) return FRECSYS_OK;
+  if (!tgt_ptr) return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, w + "no CSR loaded on the side");
+  const int64_t m = c->n[1], n = n_rows;
+  if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, false, rows, n))) return rc;
+  if ((rc = check_candidates(c, w, tgt_ptr, tgt_items, n, m))) return rc;
+  const int64_t pairs = tgt_ptr[n];
+  if (pairs == 0) return FRECSYS_OK;
+  if (!score || !top_items || !top_contrib)
+    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const std::vector<int64_t>& hrp = side == 2 ? c->host_rp_eval : c->host_rp[side];
+  auto hist = [&](int64_t i) {
+    const int64_t e = rows ? rows[i] : i;
+    return hrp[(size_t)e + 1] - hrp[(size_t)e];
+  };
+  // Rows cut in the manner of cut_by_candidates, by the contributions (h per
+  // pair) and the per-pair outputs of a batch; at least one row each.
+  const size_t per_pair = 4 + (size_t)top * 8 + 4 + 4, budget = workspace_budget();
+  std::vector<int64_t> cuts{0};
+  int64_t max_rows = 0, max_pairs = 0, max_contrib = 0;
+  for (int64_t r0 = 0; r0 < n;) {
+    size_t bytes = 0;
+    int64_t r1 = r0, contrib = 0;
+    while (r1 < n) {
+      const int64_t mt = tgt_ptr[r1 + 1] - tgt_ptr[r1];
+      const size_t add = 8 + (size_t)mt * per_pair + (size_t)mt * (size_t)hist(r1) * 4;
+      if (r1 > r0 && bytes + add > budget) break;
+      bytes += add;
+      contrib += mt * hist(r1);
+      ++r1;
+    }
+    max_rows = std::max(max_rows, r1 - r0);
+    max_pairs = std::max(max_pairs, tgt_ptr[r1] - tgt_ptr[r0]);
+    max_contrib = std::max(max_contrib, contrib);
+    cuts.push_back(r1);
+    r0 = r1;
+  }
+  int dev_cus = 256;
+  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int grid = (int)std::min<int64_t>(max_rows, 4 * (int64_t)dev_cus);
+  const bool ukind = p->kind == FRECSYS_KIND_WEIGHTED_U;
+  ExplainArgs a{};
+  a.kind = p->kind;
+  a.Dp = c->Dp;
+  a.row_ptr = c->rp[side];
+  a.col = c->col[side];
+  a.X = c->emb[1];
+  a.n_other = m;
+  a.G = c->gram[1];
+  a.reg = p->reg;
+  a.reg_exp = p->reg_exp;
+  a.w = p->unobserved_weight;
+  a.lambda_is_reg = p->lambda_is_reg;
+  a.fail = c->d_fail;
+  a.top = top;
+  int32_t *d_prow = nullptr, *d_tgt = nullptr, *d_order = nullptr;
+  int64_t* d_coff = nullptr;
+  float* d_weight = nullptr;
+  rc = Carver::run(c, [&](Carver& cv) {
+    a.contrib = cv.take<float>((size_t)max_contrib);
+    a.score = cv.take<float>((size_t)max_pairs);
+    a.top_items = cv.take<int32_t>((size_t)max_pairs * top);
+    a.top_contrib = cv.take<float>((size_t)max_pairs * top);
+    d_prow = cv.take<int32_t>((size_t)max_pairs);
+    d_tgt = cv.take<int32_t>((size_t)max_pairs);
+    d_coff = cv.take<int64_t>((size_t)max_rows);
+    d_order = cv.take<int32_t>((size_t)max_rows);
+    a.wws = cv.take<float>((size_t)grid * kExplainGroup * explain_ld(c->Dp));
+    a.tgt_ptr = cv.take<int64_t>((size_t)n + 1);
+    a.qrows = cv.take_if<int64_t>(rows != nullptr, (size_t)n);
+    d_weight = cv.take_if<float>(ukind && p->entity_weight, (size_t)c->n[side]);
+  });
+  if (rc) return rc;
+  a.prow = d_prow;
+  a.tgt = d_tgt;
+  a.coff = d_coff;
+  a.order = d_order;
+  a.entity_weight = d_weight;
+  HIP_TRY(c, to_device(c, a.tgt_ptr, tgt_ptr, (size_t)n + 1));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  if (d_weight) HIP_TRY(c, to_device(c, a.entity_weight, p->entity_weight, (size_t)c->n[side]));
+  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<int32_t> prow, order;
+  std::vector<int64_t> coff, cost;
+  int64_t full_at = 0;
+  double flops = 0.0, bytes = 0.0;
+  const double d = c->dim;
+  for (size_t b = 0; b + 1 < cuts.size(); ++b) {  // one timed launch group per row batch
+    a.r0 = cuts[b];
+    a.n = cuts[b + 1] - cuts[b];
+    a.tgt_base = tgt_ptr[a.r0];
+    const int64_t np = tgt_ptr[a.r0 + a.n] - a.tgt_base;
+    if (np == 0) continue;
+    prow.clear();
+    coff.assign((size_t)a.n, 0);
+    cost.assign((size_t)a.n, 0);
+    order.resize((size_t)a.n);
+    int64_t contrib = 0;
+    for (int64_t i = 0; i < a.n; ++i) {
+      const int64_t mt = tgt_ptr[a.r0 + i + 1] - tgt_ptr[a.r0 + i], h = hist(a.r0 + i);
+      coff[(size_t)i] = contrib;
+      contrib += mt * h;
+      prow.insert(prow.end(), (size_t)mt, (int32_t)i);
+      order[(size_t)i] = (int32_t)i;
+      // history rows streamed: once to assemble, once per group of targets
+      cost[(size_t)i] = mt > 0 ? h * (1 + (mt + kExplainGroup - 1) / kExplainGroup) : 0;
+      if (mt > 0 && h > 0) {
+        const double groups = (double)((mt + kExplainGroup - 1) / kExplainGroup);
+        flops += (double)h * d * d + d * d * d / 3.0 + 2.0 * d * d * (double)mt +
+                 2.0 * (double)h * d * (double)mt;
+        bytes += (1.0 + groups) * (double)h * (d * 4.0 + 4.0) + (double)mt * d * 4.0;
+      }
+    }
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t x, int32_t y) { return cost[(size_t)x] > cost[(size_t)y]; });
+    HIP_TRY(c, to_device(c, a.order, order.data(), order.size()));
+    HIP_TRY(c, to_device(c, a.prow, prow.data(), prow.size()));
+    HIP_TRY(c, to_device(c, a.coff, coff.data(), coff.size()));
+    HIP_TRY(c, to_device(c, a.tgt, tgt_items + a.tgt_base, (size_t)np));
+    ScopedTimer t(c, "explain");
+    HIP_TRY(c, launch_explain(a, (int)std::min<int64_t>(a.n, grid), c->stream));
+    HIP_TRY(c, launch_explain_select(a, np, c->stream));
+    t.stop();
+    HIP_TRY(c, to_host(c, score + a.tgt_base, a.score, (size_t)np));
+    HIP_TRY(c, to_host(c, top_items + a.tgt_base * top, a.top_items, (size_t)np * top));
+    HIP_TRY(c, to_host(c, top_contrib + a.tgt_base * top, a.top_contrib, (size_t)np * top));
+    if (full && contrib > 0) HIP_TRY(c, to_host(c, full + full_at, a.contrib, (size_t)contrib));
+    full_at += contrib;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  unsigned long long f = ~0ull;
+  HIP_TRY(c, hipMemcpy(&f, c->d_fail, sizeof(f), hipMemcpyDeviceToHost));
+  add_work(c, "explain", flops, bytes, n);
+  if (f != ~0ull) {
+    c->err_entity = (int64_t)f - 1;
+    return fail(c, FRECSYS_ERR_NOT_SPD, w + "LLT failed (matrix not SPD) for entity " +
+                                            std::to_string(c->err_entity));
   }
   return FRECSYS_OK;
 }

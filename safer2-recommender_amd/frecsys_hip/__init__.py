@@ -54,6 +54,7 @@ EXPORTS = (
     "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
     "frecsys_similar", "frecsys_sample_negatives", "frecsys_rank_candidates_metrics",
     "frecsys_sampled_metrics", "frecsys_position_metrics", "frecsys_rank_positions",
+    "frecsys_explain", "frecsys_csr_row_lengths",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -70,7 +71,7 @@ MODEL_EXPORTS = (
     "frecsys_model_evaluate_sampled", "frecsys_model_evaluate_sampled_fold_in",
     "frecsys_model_evaluate_ranks", "frecsys_model_evaluate_ranks_fold_in",
     "frecsys_model_save", "frecsys_model_load", "frecsys_model_file_info",
-    "frecsys_model_epochs",
+    "frecsys_model_epochs", "frecsys_model_explain", "frecsys_model_explain_fold_in",
 )
 
 
@@ -212,6 +213,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                    ctypes.c_uint64, P, I32, P, P, P, P]),
         "frecsys_position_metrics": (ctypes.c_int, [P, P, P, I64, P, P]),
         "frecsys_rank_positions": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, P, P, P]),
+        "frecsys_explain": (ctypes.c_int, [P, I32, P, P, I64, P, P, I32, P, P, P, P]),
+        "frecsys_csr_row_lengths": (ctypes.c_int, [P, I32, P, I64, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -271,6 +274,9 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_load": (ctypes.c_int, [ctypes.c_char_p, P, P, P, I64, I32, P]),
         "frecsys_model_file_info": (ctypes.c_int, [ctypes.c_char_p, I32, P]),
         "frecsys_model_epochs": (I64, [P]),
+        "frecsys_model_explain": (ctypes.c_int, [P, P, I64, P, P, I32, P, P, P, P]),
+        "frecsys_model_explain_fold_in": (ctypes.c_int,
+                                          [P, P, P, I64, P, P, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -282,6 +288,14 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _explain_full(lengths: np.ndarray, tgt_ptr: np.ndarray):
+    """The buffer of explain's `full` and its pair pointer: pair p of row i
+    holds lengths[i] contributions."""
+    per_pair = np.repeat(lengths, np.diff(tgt_ptr))
+    fp = np.concatenate([[0], np.cumsum(per_pair)]).astype(np.int64)
+    return np.zeros(int(fp[-1]), dtype=np.float32), fp
 
 
 def device_count() -> int:
@@ -758,6 +772,51 @@ class Context:
                                                  _ptr(out)))
         return out
 
+    def csr_row_lengths(self, side: int, rows=None, n: Optional[int] = None) -> np.ndarray:
+        """int64 [n]: the history length of CSR row rows[i] of `side` (row i
+        without rows) as loaded -- frecsys_csr_row_lengths."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = len(r) if r is not None else int(n)
+        out = np.zeros(n, dtype=np.int64)
+        self._check(self.lib.frecsys_csr_row_lengths(self.h, side, _ptr(r), n, _ptr(out)))
+        return out
+
+    def explain(self, side: int, kind: int, reg: float, unobserved_weight: float, tgt_ptr,
+                tgt_items, rows=None, top: int = 10, full: bool = False, reg_exp: float = 1.0,
+                lambda_is_reg: bool = False, entity_weight=None):
+        """(score float32 [pairs], top_items int32 [pairs, top], top_contrib
+        float32 [pairs, top][, full float32, full_ptr int64 [pairs + 1]]): the
+        score of every (query row, target) pair split exactly over the row's
+        history entries -- frecsys_explain.  Query row i is CSR row rows[i] of
+        `side` (SIDE_USER or SIDE_EVAL; row i without rows) with the targets
+        tgt_items[tgt_ptr[i]:tgt_ptr[i + 1]]; kind (KIND_IALS / KIND_WEIGHTED_U)
+        and the parameters are solve_side's.  score is the score of the exact
+        projection of the history against the current item table and G[ITEM];
+        the lists hold the `top` largest contributions (ties by CSR position)
+        with their history item ids, -1 / 0 behind the history length; with
+        full, pair p's contributions in CSR order are
+        full[full_ptr[p]:full_ptr[p + 1]] and sum to score[p]."""
+        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
+        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
+        n = len(tp) - 1
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        assert r is None or len(r) == n, (len(r), n)
+        ew = None if entity_weight is None else np.ascontiguousarray(entity_weight, np.float32)
+        p = _SolveParams(kind, reg, reg_exp, unobserved_weight, 0.0, 0.0, 0,
+                         1 if lambda_is_reg else 0, None if ew is None else ew.ctypes.data,
+                         None, None)
+        pairs = int(tp[-1]) if n >= 0 and len(tp) else 0
+        score = np.zeros(max(pairs, 0), dtype=np.float32)
+        items = np.full((max(pairs, 0), max(top, 0)), -1, dtype=np.int32)
+        contrib = np.zeros(items.shape, dtype=np.float32)
+        fl = fp = None
+        if full:
+            fl, fp = _explain_full(self.csr_row_lengths(side, r, n), tp)
+        self._check(self.lib.frecsys_explain(self.h, side, ctypes.byref(p), _ptr(r), n, _ptr(tp),
+                                             _ptr(ti), top, _ptr(score), _ptr(items),
+                                             _ptr(contrib), _ptr(fl)))
+        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
+
     def rank_candidates(self, side: int, k: int, cand_ptr, cand_items, rows=None,
                         exclude_history: bool = True,
                         item_mask=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -1131,6 +1190,65 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return items, scores
+
+    def _explain_out(self, tp, top):
+        pairs = int(tp[-1])
+        items = np.full((pairs, max(top, 0)), -1, dtype=np.int32)
+        return np.zeros(pairs, dtype=np.float32), items, np.zeros(items.shape, dtype=np.float32)
+
+    def explain(self, users, tgt_ptr, tgt_items, top: int = 10, full: bool = False):
+        """(score, top_items, top_contrib[, full, full_ptr]) for trained users
+        (frecsys_model_explain; outputs as Context.explain's): why item
+        tgt_items[tgt_ptr[i]:tgt_ptr[i + 1]] scores what it does for users[i],
+        split exactly over the user's training history.  The model supplies the
+        solve parameters of its own fold-in (omega = 1), so `score` is the
+        score of the exact projection of that history against the current item
+        table -- recommend_fold_in's score for the same history -- not score()'s
+        U[user] . V[item].  For ialspp / safer2pp it is the exact minimiser of
+        the objective their block steps descend; their own fold-in stops after
+        8 block epochs.  Needs the training tuples (not a serve-only model)."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
+        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
+        assert len(tp) == len(u) + 1, (len(tp), len(u))
+        score, items, contrib = self._explain_out(tp, top)
+        fl = fp = None
+        if full:
+            # a call without rows loads the training CSR if Train() has not
+            rc = self.lib.frecsys_model_explain(self.h, None, 0, None, None, top, None, None, None,
+                                                None)
+            if rc:
+                raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+            fl, fp = _explain_full(self.context().csr_row_lengths(SIDE_USER, u), tp)
+        rc = self.lib.frecsys_model_explain(self.h, _ptr(u), len(u), _ptr(tp), _ptr(ti), top,
+                                            _ptr(score), _ptr(items), _ptr(contrib), _ptr(fl))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
+
+    def explain_fold_in(self, hist_ptr, hist_items, tgt_ptr, tgt_items, top: int = 10,
+                        full: bool = False):
+        """The same for unseen users given by their histories (CSR hist_ptr /
+        hist_items; target list i belongs to history row i):
+        frecsys_model_explain_fold_in.  Bit for bit explain()'s result for a
+        user with the same history.  The histories are loaded as the EVAL side
+        of the model's context."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
+        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        assert len(tp) == n + 1, (len(tp), n)
+        score, items, contrib = self._explain_out(tp, top)
+        fl = fp = None
+        if full:
+            fl, fp = _explain_full(np.diff(hp), tp)
+        rc = self.lib.frecsys_model_explain_fold_in(self.h, _ptr(hp), _ptr(hi), n, _ptr(tp),
+                                                    _ptr(ti), top, _ptr(score), _ptr(items),
+                                                    _ptr(contrib), _ptr(fl))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
 
     def score(self, users, items) -> np.ndarray:
         """float32 [n]: the model's score of items[i] for trained user

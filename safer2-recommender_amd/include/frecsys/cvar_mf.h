@@ -55,6 +55,9 @@ class CVaRMFRecommender : public detail::DeviceModel {
                                           unobserved_weight_);  // StepU_eval, omega = 1
     FoldInSolve(csr, p);
   }
+  frecsys_solve_params ExplainParams() const override {
+    return solve_params(FRECSYS_KIND_WEIGHTED_U, regularization_, unobserved_weight_);
+  }
 
   void Train(const Dataset& data) override {
     dev_->LoadTraining(data);

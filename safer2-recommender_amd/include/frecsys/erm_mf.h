@@ -70,6 +70,9 @@ class ERMMFRecommender : public detail::DeviceModel {
                                           unobserved_weight_);  // omega = 1 (erm_mf.h:235-244)
     FoldInSolve(csr, p);
   }
+  frecsys_solve_params ExplainParams() const override {
+    return solve_params(FRECSYS_KIND_WEIGHTED_U, regularization_, unobserved_weight_);
+  }
 
   void Train(const Dataset& data) override {
     dev_->LoadTraining(data);

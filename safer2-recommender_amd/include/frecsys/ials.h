@@ -55,6 +55,7 @@ class IALSRecommender : public detail::DeviceModel {
     dev_->Gramian(DeviceContext::ITEM);  // Step's V^T V (ials.h:321)
     FoldInSolve(csr, params());
   }
+  frecsys_solve_params ExplainParams() const override { return params(); }
 
   void Train(const Dataset& data) override {
     dev_->LoadTraining(data);

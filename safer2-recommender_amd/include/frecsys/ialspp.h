@@ -60,6 +60,9 @@ class IALSppRecommender : public detail::DeviceModel {
       }
     }
   }
+  // The iALS objective the block steps descend: Explain() explains its exact
+  // minimiser, which the 8 block epochs above only approach.
+  frecsys_solve_params ExplainParams() const override { return params(); }
 
   void Train(const Dataset& data) override {
     dev_->PPLoad(data);

@@ -108,6 +108,36 @@ class DeviceModel : public Recommender {
                            exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
   }
 
+  // The solve parameters of the model's own fold-in projection -- the ones
+  // its FoldIn passes, omega = 1 where the fold-in uses it.  iALS++ and
+  // SAFER2++ give the parameters of the objective their block steps descend:
+  // their explanation is that of its exact minimiser, which their own fold-in
+  // (8 block epochs from zero) only approaches.
+  virtual frecsys_solve_params ExplainParams() const = 0;
+
+  // Why an item scores what it does (frecsys_explain): the score of the exact
+  // projection of a user's history against the current item table, split over
+  // the history entries.  targets: row i holds the targets of users[i] / of
+  // history row i; outputs as frecsys_explain's (full may be nullptr).  The
+  // status code, for callers that report errors.  Explain needs the training
+  // CSR on the device (Train() loads it).
+  int Explain(const int64_t* users, int64_t n, const int64_t* tgt_ptr, const int32_t* tgt_items,
+              int top, float* score, int32_t* top_items, float* top_contrib, float* full) {
+    dev_->Gramian(DeviceContext::ITEM);
+    const frecsys_solve_params p = ExplainParams();
+    return frecsys_explain(dev_->raw(), DeviceContext::USER, &p, users, n, tgt_ptr, tgt_items, top,
+                           score, top_items, top_contrib, full);
+  }
+  // The same for unseen users given by their histories, loaded as the EVAL side.
+  int ExplainFoldIn(const Csr& csr, const int64_t* tgt_ptr, const int32_t* tgt_items, int top,
+                    float* score, int32_t* top_items, float* top_contrib, float* full) {
+    dev_->LoadEval(csr);
+    dev_->Gramian(DeviceContext::ITEM);
+    const frecsys_solve_params p = ExplainParams();
+    return frecsys_explain(dev_->raw(), DeviceContext::EVAL, &p, nullptr, csr.rows(), tgt_ptr,
+                           tgt_items, top, score, top_items, top_contrib, full);
+  }
+
   // Ranking quality of trained users on the device (frecsys_rank_metrics):
   // row i of `gt` is the ground truth of users[i]; Recall@K / NDCG@K of
   // Recommend's ranking at every cut-off of k_list, per user, in the

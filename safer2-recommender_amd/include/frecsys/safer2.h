@@ -212,6 +212,9 @@ class SAFER2Recommender : public detail::DeviceModel {
 
   // StepU with omega = 1 and the cached item gramian (safer2.h:246-252)
   void FoldIn(const Csr& csr) override { FoldInSolve(csr, u_params(false)); }
+  // (SAFER2++ inherits this: the objective its block steps descend, whose
+  // exact minimiser its 8-epoch fold-in only approaches)
+  frecsys_solve_params ExplainParams() const override { return u_params(false); }
 
   void Train(const Dataset& data) override {
     // FRECSYS_HOST_PROF (diagnostics): wall ms of each Train() phase on stderr

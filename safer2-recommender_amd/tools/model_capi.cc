@@ -464,6 +464,45 @@ int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* i
   return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
 }
 
+int frecsys_model_explain(frecsys_model* m, const int64_t* users, int64_t n,
+                          const int64_t* tgt_ptr, const int32_t* tgt_items, int32_t top,
+                          float* score, int32_t* top_items, float* top_contrib, float* full) {
+  if (!m || n < 0 || (n > 0 && (!users || !tgt_ptr)))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_explain: bad arguments");
+  if (int rc = needs_data(m, "frecsys_model_explain")) return rc;
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  dm->device().LoadTraining(*m->train);  // once per dataset; Train() has usually done it
+  const int rc = dm->Explain(users, n, tgt_ptr, tgt_items, top, score, top_items, top_contrib, full);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_explain_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                  const int32_t* hist_items, int64_t n, const int64_t* tgt_ptr,
+                                  const int32_t* tgt_items, int32_t top, float* score,
+                                  int32_t* top_items, float* top_contrib, float* full) {
+  const std::string w = "frecsys_model_explain_fold_in: ";
+  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0 || !tgt_ptr)
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  // checked here: the C++ layer treats a bad EVAL CSR as fatal
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i])
+      return model_fail(FRECSYS_ERR_INVALID, w + "hist_ptr not monotone");
+  if (hist_ptr[n] > 0 && !hist_items) return model_fail(FRECSYS_ERR_INVALID, w + "null hist_items");
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return model_fail(FRECSYS_ERR_INVALID,
+                        w + "item id " + std::to_string(hist_items[p]) + " out of range");
+  if (n == 0) return FRECSYS_OK;
+  frecsys::Csr csr;
+  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+  const int rc =
+      dm->ExplainFoldIn(csr, tgt_ptr, tgt_items, top, score, top_items, top_contrib, full);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
 int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_t n,
                                   const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                                   int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
