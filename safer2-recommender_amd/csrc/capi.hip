@@ -11,18 +11,18 @@
 //   counts, in place).
 //
 // What lives here: the context's life cycle, the data loaders, the Gramian
-// and its exchange, the solve drivers (d-space, history space, wide, CG), the
-// iALS++ block step, the losses and train statistics, frecsys_eval_topk, the
-// timers / work / counters queries, and the one definition of the functions
-// ctx.h declares.  The ranking and evaluation calls (frecsys_recommend and
-// what followed it) are in serve.hip.
+// and its exchange with the basis it feeds (prepare_basis, early builds), the
+// losses and train statistics, frecsys_eval_topk, the timers / work / counters
+// queries, and the one definition of the functions ctx.h declares.  The solve
+// drivers (d-space, history space, wide, CG) and the iALS++ block step are in
+// train.hip; the ranking and evaluation calls (frecsys_recommend and what
+// followed it) are in serve.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,35 +71,6 @@ void partition_rows(int64_t n_rows, const int64_t* row_ptr, int parts, int64_t* 
   bounds[parts] = n_rows;
 }
 
-}  // namespace frecsys_hip
-
-namespace {
-
-// SURVEY 8(d) per entity of h assembly rows at dim d: d-space SYRK
-// h d (d+1) and LLT d^3/3 + 2 d^2 flops; gather bytes h d 4 (rows) + h 4
-// (ids) + 8 (row offset) + d 4 (the solution written).
-// (SYRK and gather are linear in h: summed from the queue prefix sums,
-// heff_sums below.)
-double dspace_solve_flops(double d) { return d * d * d / 3.0 + 2.0 * d * d; }
-
-// ensure() that reports an out-of-memory hipMalloc instead of failing
-// (DevBuf::try_reserve): *oom is set and the buffer left empty.
-template <typename T>
-int try_ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count, bool* oom) {
-  const hipError_t e = b.try_reserve(count, oom);
-  if (e == hipSuccess) return FRECSYS_OK;
-  return fail(c, FRECSYS_ERR_HIP,
-              std::string(b ? "hipFree(*p): " : "hipMalloc: ") + hipGetErrorString(e));
-}
-
-// A fresh allocation of `count` elements whatever the buffer held (a table
-// replaced as a whole: CSR arrays, queues).
-template <typename T>
-hipError_t renew(DevBuf<T>& b, size_t count) {
-  const hipError_t e = b.release();
-  return e != hipSuccess ? e : b.reserve(count);
-}
-
 // Bytes one wide workspace may take now: FRECSYS_WIDE_WS_MB, capped at a
 // quarter of the device memory that is free (plus what the workspace
 // already holds), so several contexts or other tenants of the device leave
@@ -137,33 +108,9 @@ bool below_headroom() {
   return fr < kRuntimeHeadroom;
 }
 
-// A workspace of *batch slots of `per` elements: a failed hipMalloc halves
-// the batch (counted in ws_shrinks) until one slot does not fit either, and a
-// batch that fits only after such a cut is halved on while it leaves less
-// than kRuntimeHeadroom free.  Entities are independent, so the batch size
-// never changes a result.
-template <typename T>
-int ensure_batch(frecsys_ctx* c, DevBuf<T>& b, size_t per, int64_t* batch) {
-  bool cut = false;
-  while (true) {
-    bool oom = false;
-    int rc = try_ensure(c, b, per * (size_t)*batch, &oom);
-    if (rc) return rc;
-    if (!oom) {
-      if (!cut || *batch <= 1 || !below_headroom()) return FRECSYS_OK;
-      HIP_TRY(c, b.release());
-    } else if (*batch <= 1) {
-      return fail(c, FRECSYS_ERR_HIP, "hipMalloc: out of memory for one workspace slot");
-    }
-    *batch = (*batch + 1) / 2;
-    ++c->ws_shrinks;
-    cut = true;
-  }
-}
-
 bool valid_side(int side) { return side >= 0 && side <= 2; }
 
-void refresh_bounds(frecsys_ctx* c, int side) {
+static void refresh_bounds(frecsys_ctx* c, int side) {
   if (side > 1) return;
   c->bounds[side].assign(c->world + 1, 0);
   if (!c->host_rp[side].empty()) {
@@ -221,10 +168,6 @@ int build_order(frecsys_ctx* c, int side) {
 
 // Sums of h_eff, h_eff^2, h_eff^3 and of the non-empty entities over queue
 // positions [lo, hi) of `side` (vq: the V kinds' tail-quirk h_eff).
-struct HeffSums {
-  double h1 = 0, h2 = 0, h3 = 0;
-  int64_t nz = 0;
-};
 HeffSums heff_sums(frecsys_ctx* c, int side, bool vq, int64_t lo, int64_t hi) {
   frecsys_ctx::WorkPrefix& p = c->wprefix[side][vq ? 1 : 0];
   const std::vector<int32_t>& hs = c->order_h[side];
@@ -235,9 +178,7 @@ HeffSums heff_sums(frecsys_ctx* c, int side, bool vq, int64_t lo, int64_t hi) {
     p.h3.assign(n + 1, 0.0);
     p.nz.assign(n + 1, 0);
     for (size_t i = 0; i < n; ++i) {
-      const int64_t h0 = hs[i];
-      const double h = (double)((vq && c->quirks && h0 > 128 && (h0 % 128) != 0)
-                                    ? h0 + 128 - (h0 % 128) : h0);
+      const double h = (double)queue_heff(c->quirks, vq, hs[i]);
       p.h1[i + 1] = p.h1[i] + h;
       p.h2[i + 1] = p.h2[i] + h * h;
       p.h3[i + 1] = p.h3[i] + h * h * h;
@@ -252,74 +193,6 @@ HeffSums heff_sums(frecsys_ctx* c, int side, bool vq, int64_t lo, int64_t hi) {
   s.h3 = p.h3[hi] - p.h3[lo];
   s.nz = p.nz[hi] - p.nz[lo];
   return s;
-}
-
-// Long-history split of the d-space queue prefix [0, n): entities with
-// more than 2*C assembly rows get their SYRK cut into C-row slabs done by
-// separate workgroups (launch_split_syrk / wide_syrk2_kernel<2>) before the
-// solve; at most max_slabs slabs of slab_floats each (longest entities first;
-// shrink: fewer when their allocation fails -- only where the split does not
-// change the sums' order, the wide dims).
-int plan_split(frecsys_ctx* c, const std::vector<int32_t>& hs, int64_t n,
-               const std::function<int64_t(int64_t)>& heff, SolveArgs* a, int64_t C,
-               size_t slab_floats, int64_t max_slabs, hipStream_t s, bool shrink = false) {
-  a->split = nullptr;
-  a->n_split = 0;
-  a->slabs = nullptr;
-  a->work = nullptr;
-  a->n_work = 0;
-  if (c->split_rows <= 0 || C <= 0 || c->Dp < 32) return FRECSYS_OK;
-  int32_t slab = 0;
-  bool cut = false;
-  while (true) {
-    c->h_split.clear();
-    c->h_work.clear();
-    slab = 0;
-    for (int64_t i = 0; i < n && heff(hs[i]) > 2 * C; ++i) {
-      const int64_t ne = heff(hs[i]);
-      if (slab + (ne + C - 1) / C > max_slabs) break;
-      const int32_t first = slab;
-      for (int64_t k = 0; k < ne; k += C)
-        c->h_work.push_back(SplitWork{(int32_t)i, (int32_t)k, (int32_t)std::min(ne, k + C), slab++});
-      c->h_split.push_back(int2{first, slab - first});
-    }
-    if (c->h_split.empty()) return FRECSYS_OK;
-    if (!shrink) {
-      int rc = ensure(c, c->d_slabs, (size_t)slab * slab_floats);
-      if (rc) return rc;
-      break;
-    }
-    // the wide dims (split and unsplit SYRKs are bit-identical there): fewer
-    // slabs when the allocation fails
-    bool oom = false;
-    int rc = try_ensure(c, c->d_slabs, (size_t)slab * slab_floats, &oom);
-    if (rc) return rc;
-    if (!oom) {  // as ensure_batch: a cut allocation leaves kRuntimeHeadroom free
-      if (!cut || slab <= 1 || !below_headroom()) break;
-      HIP_TRY(c, c->d_slabs.release());
-    }
-    ++c->ws_shrinks;
-    max_slabs = slab / 2;
-    cut = true;
-  }
-  int rc = ensure(c, c->d_split, c->h_split.size());
-  if (rc) return rc;
-  rc = ensure(c, c->d_work, c->h_work.size());
-  if (rc) return rc;
-  // on the solve's own stream: a blocking hipMemcpy went through a queue that
-  // could be FIFO-behind the basis chain, holding the d-space launch back
-  // (h_split / h_work live in the context until the next call, after the
-  // stream has been synchronised)
-  HIP_TRY(c, hipMemcpyAsync(c->d_split, c->h_split.data(), sizeof(int2) * c->h_split.size(),
-                            hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(c->d_work, c->h_work.data(), sizeof(SplitWork) * c->h_work.size(),
-                            hipMemcpyHostToDevice, s));
-  a->split = c->d_split;
-  a->n_split = (int64_t)c->h_split.size();
-  a->slabs = c->d_slabs;
-  a->work = c->d_work;
-  a->n_work = (int64_t)c->h_work.size();
-  return FRECSYS_OK;
 }
 
 // Stream s waits (on the device) for the early basis builds still running
@@ -337,9 +210,8 @@ void emb_written(frecsys_ctx* c, int side) { c->emb_ver[side] = ++c->ver_counter
 // Basis of the other side's Gramian, G = Q T Q^T, and the other side
 // rotated into it (X Q): the inputs of the history-space solve.  Rebuilt
 // only when the Gramian (basis) or the rows (rotation) changed since.
-int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int mode = 0,
-                  float mu = 0.f, float lam = 0.f, const QueueRec* rows = nullptr,
-                  int64_t nrows = 0, uint64_t sub = 0) {
+int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int mode, float mu,
+                  float lam, const QueueRec* rows, int64_t nrows, uint64_t sub) {
   const int Dp = c->Dp;
   int rc = ensure(c, c->q[other], (size_t)Dp * Dp);
   if (!rc) rc = ensure(c, c->tri[other], (size_t)2 * Dp);
@@ -476,7 +348,7 @@ int hspace_rows(frecsys_ctx* c, int side, int other, int64_t q0, int64_t q1,
 // A Gramian of side g was just formed on c->stream: build its basis on
 // stream5 now if the side that consumes it took the history-space path last
 // time and will want it again.
-int maybe_start_eager(frecsys_ctx* c, int g) {
+static int maybe_start_eager(frecsys_ctx* c, int g) {
   const int consumer = 1 - g;
   if (!c->eager_on || c->dual_serial || !c->dual_on || c->Dp < 64 || c->dual_max_h <= 0 ||
       !c->dual_used[consumer] || c->eager_pending[g])
@@ -574,7 +446,7 @@ int upload(frecsys_ctx* c, UploadBuf& b, const float* host, size_t n) {
 
 // Event pair around one launch on any stream; resolved by flush_ktimers
 // after the stream has been synchronised.
-hipEvent_t pool_event(frecsys_ctx* c) {
+static hipEvent_t pool_event(frecsys_ctx* c) {
   if (!c->event_pool.empty()) {
     hipEvent_t e = c->event_pool.back();
     c->event_pool.pop_back();
@@ -610,6 +482,10 @@ void flush_ktimers(frecsys_ctx* c) {
   }
   c->pending.clear();
 }
+
+}  // namespace frecsys_hip
+
+namespace {
 
 // Group slabs of [r's groups] broadcast from their owners (an all-gather
 // with uneven counts, in place).
@@ -1216,618 +1092,6 @@ int frecsys_set_gramian(frecsys_ctx* c, int32_t side, const float* host, int64_t
   return FRECSYS_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// The d-space solve of the queue prefix ap.order[0..ap.n_rows): the tiled
-// one-workgroup-per-entity kernels (long histories split) up to Dp = 256,
-// the HBM-workspace batches of wide.hip at Dp = 512 / 1024.
-// aux (Dp <= 256, optional): an idle stream for the long histories' slabs
-// and then their entities' solves, so the slabs run beside the other
-// entities' solve instead of before it (s waits for aux at the end).
-int launch_dspace(frecsys_ctx* c, SolveArgs ap, const std::vector<int32_t>& hs,
-                  const std::function<int64_t(int64_t)>& heff, hipStream_t s,
-                  const std::string& pre, bool can_split, int side, bool vq,
-                  hipStream_t aux = nullptr) {
-  if (wide_dim(c->Dp)) {
-    const size_t slot = wide_slot_floats(c->Dp);
-    const int64_t budget =
-        (int64_t)(ws_budget(c, c->wide_ws.cap() * sizeof(float)) / (slot * sizeof(float)));
-    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(ap.n_rows, budget));
-    int rc = ensure_batch(c, c->wide_ws, slot, &batch);
-    if (rc) return rc;
-    if (can_split) {  // long histories of the first batch cut into slabs (a budget of their own)
-      const size_t sf = wide_slab_floats(c->Dp);
-      // (an empty shard has an empty queue but still a batch of one slot)
-      rc = plan_split(c, hs, std::min<int64_t>(batch, ap.n_rows), heff, &ap, wide_slab_rows(), sf,
-                      (int64_t)(ws_budget(c, c->d_slabs.cap() * sizeof(float)) / (sf * sizeof(float))),
-                      s, true);
-      if (rc) return rc;
-    }
-    static const bool wprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-    DevBuf<unsigned long long>& w_prof = c->w_prof;
-    if (wprof && !w_prof) {
-      HIP_TRY(c, w_prof.reserve(16));
-      HIP_TRY(c, hipMemset(w_prof, 0, sizeof(unsigned long long) * 16));
-    }
-    ap.prof = wprof ? w_prof.get() : nullptr;
-    char* xs = nullptr;
-    if (c->wide_presplit && ap.n_rows > 0) {
-      // no room for the table: the register-staged SYRK (bit-identical)
-      bool oom = false;
-      rc = try_ensure(c, c->wide_xs, wide_xsplit_bytes(c->Dp, ap.n_other), &oom);
-      if (rc) return rc;
-      if (oom) ++c->ws_shrinks;
-      xs = c->wide_xs;
-    }
-    const size_t k = ktimer_begin(c, pre + ".dspace", s);
-    HIP_TRY(c, launch_wide_solve(c->Dp, ap, c->wide_ws, batch, s, xs));
-    ktimer_end(c, k, s);
-    if (wprof) {  // diagnostics (ablation builds): wide SYRK cycles per chunk and phase
-      unsigned long long hp[16];
-      HIP_TRY(c, hipStreamSynchronize(s));
-      HIP_TRY(c, hipMemcpy(hp, w_prof, sizeof(hp), hipMemcpyDeviceToHost));
-      HIP_TRY(c, hipMemset(w_prof, 0, sizeof(hp)));
-      for (int pt = 0; pt < 2; ++pt)
-        for (int wv = 0; wv < 2; ++wv) {
-          const unsigned long long* q = hp + 8 * pt + 4 * wv;
-          const double n = (double)std::max<unsigned long long>(q[3], 1);
-          fprintf(stderr, "[wide-prof] %s %s wave %d chunks %llu cycles/chunk: mfma+stage %.0f "
-                  "ring+loads %.0f barrier %.0f\n", pre.c_str(), pt ? "diag" : "offdiag",
-                  wv ? 7 : 0, q[3], q[0] / n, q[1] / n, q[2] / n);
-        }
-    }
-    // SURVEY 8(d) per entity: dspace_syrk_flops + dspace_solve_flops, gather_bytes
-    // (empty histories untouched); both linear in h, so from the prefix sums
-    const double d = c->dim;
-    const HeffSums hsum = heff_sums(c, side, vq, 0, ap.n_rows);
-    add_work(c, pre + ".dspace", d * (d + 1.0) * hsum.h1 + hsum.nz * dspace_solve_flops(d),
-             (d * 4.0 + 4.0) * hsum.h1 + hsum.nz * (8.0 + d * 4.0), hsum.nz);  // one timed call
-    return FRECSYS_OK;
-  }
-  if (can_split) {
-    int rc = plan_split(c, hs, ap.n_rows, heff, &ap, c->split_rows, split_slab_floats(c->Dp),
-                        INT64_MAX, s);
-    if (rc) return rc;
-  }
-  const bool side_split = ap.n_work > 0 && aux != nullptr;
-  if (side_split) {
-    // slabs, then the split entities' solves (they start from the slabs) on
-    // aux; the other entities on s meanwhile
-    HIP_TRY(c, hipEventRecord(c->ev_fork, s));
-    HIP_TRY(c, hipStreamWaitEvent(aux, c->ev_fork, 0));
-    const size_t k = ktimer_begin(c, pre + ".split", aux);
-    HIP_TRY(c, launch_split_syrk(c->Dp, ap, aux));
-    ktimer_end(c, k, aux);
-  } else if (ap.n_work > 0) {
-    const size_t k = ktimer_begin(c, pre + ".split", s);
-    HIP_TRY(c, launch_split_syrk(c->Dp, ap, s));
-    ktimer_end(c, k, s);
-  }
-  static const bool dprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-  DevBuf<unsigned long long>& d_prof = c->d_prof;
-  if (dprof && !d_prof) {
-    HIP_TRY(c, d_prof.reserve(16));
-    HIP_TRY(c, hipMemset(d_prof, 0, sizeof(unsigned long long) * 16));
-  }
-  ap.prof = dprof ? d_prof.get() : nullptr;
-  const size_t k = ktimer_begin(c, pre + ".dspace", s);
-  if (side_split) {
-    SolveArgs af = ap;  // queue positions [0, n_split): the split entities
-    af.n_rows = ap.n_split;
-    HIP_TRY(c, launch_solve(c->Dp, af, aux));
-    HIP_TRY(c, hipEventRecord(c->ev_join, aux));
-    SolveArgs ar = ap;  // positions [n_split, n_rows)
-    ar.order = ap.order + ap.n_split;
-    ar.n_rows = ap.n_rows - ap.n_split;
-    ar.split = nullptr;
-    ar.n_split = 0;
-    ar.work = nullptr;
-    ar.n_work = 0;
-    HIP_TRY(c, launch_solve(c->Dp, ar, s));
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join, 0));
-  } else {
-    HIP_TRY(c, launch_solve(c->Dp, ap, s));
-  }
-  ktimer_end(c, k, s);
-  {  // the split entities' SYRK is the split kernel's work, their solve this one's
-    const double d = c->dim;
-    const HeffSums sp = heff_sums(c, side, vq, 0, ap.n_split);
-    const HeffSums rest = heff_sums(c, side, vq, ap.n_split, ap.n_rows);
-    const int64_t ne = sp.nz + rest.nz;
-    add_work(c, pre + ".dspace",
-             d * (d + 1.0) * rest.h1 + (double)ne * dspace_solve_flops(d),
-             (d * 4.0 + 4.0) * rest.h1 + (double)ne * (8.0 + d * 4.0), ne);
-    if (ap.n_work > 0)
-      add_work(c, pre + ".split", d * (d + 1.0) * sp.h1, (d * 4.0 + 4.0) * sp.h1, sp.nz);
-  }
-  if (dprof) {  // diagnostics: mean cycles per entity and phase
-    unsigned long long hp[16];
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipMemcpy(hp, d_prof, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemset(d_prof, 0, sizeof(hp)));
-    const double n = (double)std::max<unsigned long long>(hp[4], 1);
-    fprintf(stderr, "[dspace-prof] %s n %llu mean h %.0f cycles/entity: setup %.0f syrk %.0f "
-            "epilogue %.0f (rhs %.0f tiles %.0f) chol %.0f | chain %.0f workers %.0f factored %.0f\n",
-            pre.c_str(), hp[4], hp[8] / n, hp[0] / n, hp[1] / n, (hp[2] + hp[9] + hp[10]) / n,
-            hp[9] / n, hp[10] / n, hp[3] / n, hp[5] / n, hp[6] / n, hp[7] / n);
-    fprintf(stderr, "[dspace-prof] %s chain: waits %.0f trsm %.0f update %.0f factor %.0f | "
-            "worker waits %.0f\n",
-            pre.c_str(), hp[11] / n, hp[12] / n, hp[13] / n, hp[14] / n, hp[15] / n);
-  }
-  return FRECSYS_OK;
-}
-
-// The argument checks frecsys_solve_side and frecsys_solve_side_cg share
-// (pre: the call's message prefix; frecsys_pp_step has texts of its own).
-int check_solve_args(frecsys_ctx* c, const std::string& pre, int side,
-                     const frecsys_solve_params* p) {
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, pre + "no CSR loaded for side");
-  const int kind = p->kind;
-  if (kind < FRECSYS_KIND_IALS || kind > FRECSYS_KIND_CVAR_GRAD_V)
-    return fail(c, FRECSYS_ERR_INVALID, pre + "bad kind");
-  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  const bool grad = kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  if (vkind && (!p->entity_reg || !p->other_weight))
-    return fail(c, FRECSYS_ERR_INVALID, pre + "V kinds need entity_reg and other_weight");
-  if (grad && side == 2) return fail(c, FRECSYS_ERR_INVALID, pre + "CVaR step on EVAL side");
-  if (p->from_snapshot && !c->snap[side == 1 ? 0 : 1])
-    return fail(c, FRECSYS_ERR_INVALID, pre + "from_snapshot without a snapshot");
-  return FRECSYS_OK;
-}
-
-// What every solve entry point does before its launches: the device, the
-// early basis builds of `eager_mask` joined, the per-entity vectors the kind
-// reads uploaded, the failure word reset.
-int begin_solve(frecsys_ctx* c, int side, const frecsys_solve_params* p, int eager_mask) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc = join_eager(c, eager_mask, c->stream);
-  if (rc) return rc;
-  const int kind = p->kind, other = side == 1 ? 0 : 1;
-  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U || kind == FRECSYS_KIND_CVAR_GRAD_U;
-  if (ukind && p->entity_weight) {
-    rc = upload(c, c->d_entity_weight, p->entity_weight, (size_t)c->n[side]);
-    if (rc) return rc;
-  }
-  if (vkind) {
-    rc = upload(c, c->d_entity_reg, p->entity_reg, (size_t)c->n[side]);
-    if (rc) return rc;
-    rc = upload(c, c->d_other_weight, p->other_weight, (size_t)c->n[other]);
-    if (rc) return rc;
-  }
-  // ~0ull by a device-side fill: an H2D copy from host memory at this point
-  // was observed starting only after the early basis build queued on another
-  // stream had finished, holding back the fork of the d-space solve
-  HIP_TRY(c, hipMemsetAsync(c->d_fail, 0xFF, sizeof(unsigned long long), c->stream));
-  return FRECSYS_OK;
-}
-
-// ... and after them: the failure word read back into *f (~0ull: none), the
-// solved rows all-gathered (gather: the call has not exchanged them itself),
-// the stream synchronised and the kernel timers resolved.
-int end_solve(frecsys_ctx* c, int side, bool gather, unsigned long long* f) {
-  HIP_TRY(c, hipMemcpyAsync(f, c->d_fail, sizeof(*f), hipMemcpyDeviceToHost, c->stream));
-  if (gather && side < 2 && (c->world > 1 || c->comm)) {
-    ScopedTimer t(c, "allgather");
-    int rc = allgather_rows(c, c->emb[side], side, c->Dp);
-    if (rc) return rc;
-    t.stop();
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  flush_ktimers(c);
-  return FRECSYS_OK;
-}
-
-int solve_side_impl(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
-                    bool force_dspace) {
-  if (!c || !valid_side(side) || !p) return fail(c, FRECSYS_ERR_INVALID, "solve: bad arguments");
-  int rc = check_solve_args(c, "solve: ", side, p);
-  if (rc) return rc;
-  const int kind = p->kind;
-  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U || kind == FRECSYS_KIND_CVAR_GRAD_U;
-  const bool grad = kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V;
-  const int other = side == 1 ? 0 : 1;
-  rc = begin_solve(c, side, p, side < 2 ? 1 << side : 0);  // a build still reading emb[side]
-  if (rc) return rc;
-  int64_t lo, hi;
-  shard(c, side, &lo, &hi);
-  rc = build_order(c, side);
-  if (rc) return rc;
-  SolveArgs a{};
-  a.kind = kind;
-  a.order = c->d_order[side];
-  a.counter = c->d_counter;
-  a.quirk = c->quirks;
-  a.row_ptr = c->rp[side];
-  a.col = c->col[side];
-  a.row_lo = lo;
-  a.n_rows = hi - lo;
-  a.X = p->from_snapshot ? c->snap[other] : c->emb[other];
-  a.n_other = c->n[other];
-  a.G = c->gram[other];
-  a.E = c->emb[side];
-  a.out = c->emb[side];
-  a.reg = p->reg;
-  a.reg_exp = p->reg_exp;
-  a.w = p->unobserved_weight;
-  a.alpha = p->alpha;
-  a.eta = p->stepsize;
-  a.lambda_is_reg = p->lambda_is_reg;
-  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
-  a.entity_reg = vkind ? c->d_entity_reg.dev.get() : nullptr;
-  a.other_weight = vkind ? c->d_other_weight.dev.get() : nullptr;
-  a.fail = c->d_fail;
-  a.split = nullptr;
-  a.n_split = 0;
-  a.slabs = nullptr;
-  a.work = nullptr;
-  a.n_work = 0;
-  a.debug_skip = c->debug_skip;
-  const unsigned long long none = ~0ull;
-  // Queue split: the queue is sorted by decreasing history, and h_eff (the
-  // rows the assembly reads, tail-quirk rows included) is monotone in h, so
-  // the d-space entities are a prefix, then the history-space buckets
-  // (32*(t-1) < h_eff <= 32*t, t = 8..1), then the empty histories.
-  const std::vector<int32_t>& hs = c->order_h[side];
-  auto heff = [&](int64_t h) -> int64_t {
-    return (vkind && c->quirks && h > 128 && (h % 128) != 0) ? h + 128 - (h % 128) : h;
-  };
-  auto first_le = [&](int64_t lim) {  // first queue index with h_eff <= lim
-    return (int64_t)(std::partition_point(hs.begin(), hs.end(),
-                                          [&](int32_t h) { return heff(h) > lim; }) -
-                     hs.begin());
-  };
-  // The history-space form needs M = mu*G + lam*I SPD for every entity:
-  // lam > 0 and mu >= 0 (G is PSD).  Otherwise (and when it reports a
-  // non-positive pivot) the call runs the d-space solve for everyone.
-  bool m_spd = p->reg > 0.0f && p->unobserved_weight >= 0.0f;
-  if (m_spd && ukind && p->entity_weight)
-    for (int64_t i = 0; i < c->n[side] && m_spd; ++i) m_spd = p->entity_weight[i] >= 0.0f;
-  if (m_spd && vkind && !p->lambda_is_reg) {
-    const float base = p->alpha * p->unobserved_weight * (float)c->n[other];
-    for (int64_t i = 0; i < c->n[side] && m_spd; ++i) m_spd = p->entity_reg[i] + base > 0.0f;
-  }
-  const bool dual = c->dual_on && !force_dspace && m_spd && !grad && c->Dp >= 64 &&
-                    c->dual_max_h_side[side] > 0 && (int64_t)hs.size() == c->order_n[side];
-  const int64_t n_dspace = dual ? first_le(c->dual_max_h_side[side]) : a.n_rows;
-  c->dual_used[side] = dual;
-  if (side < 2) emb_written(c, side);
-  const int64_t n_nonempty = dual ? first_le(0) : a.n_rows;
-  {
-    static const char* names[3] = {"solve_user", "solve_item", "solve_eval"};
-    const std::string pre = names[side];
-    ScopedTimer t(c, names[side]);
-    if (!dual || n_dspace >= n_nonempty) {
-      // stream2 (the mixed path's d-space stream) is idle here: the slabs of
-      // the long histories run on it beside the other entities' solve
-      rc = launch_dspace(c, a, hs, heff, c->stream, pre,
-                         c->Dp >= 32 && (int64_t)hs.size() == c->order_n[side], side, vkind,
-                         c->dual_serial ? nullptr : c->stream2);
-      if (rc) return rc;
-    } else {
-      // d-space solve of the long histories on stream2, concurrently with
-      // the basis change + history-space solve of the rest on stream
-      // the basis (one-workgroup tridiagonalisation first) is queued before
-      // the d-space kernels so its workgroup is not left waiting for a CU
-      // behind them; stream2 waits only for what preceded the fork
-      hipStream_t s2 = c->dual_serial ? c->stream : c->stream2;
-      if (n_dspace > 0) HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
-      // one M = mu*G + lam*I for every entity (iALS with l2_reg_exp = 0, or
-      // lambda = reg: ials.h:310-315): the Cholesky basis, no tridiagonal
-      // reduction, no per-entity LDL -- at every Dp the history space runs
-      // at (64..256, 512, 1024: chol_basis_kernel<T>, launch_chol_basis)
-      int bmode = 0;
-      float bmu = 0.f, blam = 0.f;
-      if (c->chol_basis_on && kind == FRECSYS_KIND_IALS &&
-          (p->lambda_is_reg || p->reg_exp == 0.0f)) {
-        bmode = 1;
-        bmu = p->unobserved_weight;
-        blam = p->reg;
-      }
-      c->want_mode[other] = bmode;
-      c->want_mu[other] = bmu;
-      c->want_lam[other] = blam;
-      const QueueRec* hrows = nullptr;
-      int64_t nhrows = 0;
-      uint64_t hsub = 0;
-      rc = hspace_rows(c, side, other, n_dspace, n_nonempty, &hrows, &nhrows, &hsub);
-      if (rc) return rc;
-      size_t k = ktimer_begin(c, pre + ".basis", c->stream);
-      rc = prepare_basis(c, other, a.X, c->stream, bmode, bmu, blam, hrows, nhrows, hsub);
-      if (rc) return rc;
-      ktimer_end(c, k, c->stream);
-      if (n_dspace > 0) {
-        HIP_TRY(c, hipStreamWaitEvent(s2, c->ev_fork, 0));
-        SolveArgs ap = a;
-        ap.n_rows = n_dspace;
-        rc = launch_dspace(c, ap, hs, heff, s2, pre, true, side, vkind);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev_join, s2));
-      }
-      DualArgs d{};
-      d.kind = kind;
-      d.quirk = c->quirks;
-      d.Dp = c->Dp;
-      d.col = a.col;
-      d.Xrot = c->xrot[other];
-      d.tdiag = c->tri[other];
-      d.toff = c->tri[other] + c->Dp;
-      d.unit_m = bmode;
-      d.basis_status = c->tri[other];
-      d.n_other = a.n_other;
-      d.reg = a.reg;
-      d.reg_exp = a.reg_exp;
-      d.w = a.w;
-      d.alpha = a.alpha;
-      d.lambda_is_reg = a.lambda_is_reg;
-      d.entity_weight = a.entity_weight;
-      d.entity_reg = a.entity_reg;
-      d.other_weight = a.other_weight;
-      d.fail = a.fail;
-      d.debug_skip = a.debug_skip;
-      static const bool dprof = getenv("FRECSYS_DUAL_PROF") != nullptr;
-      DevBuf<unsigned long long>& d_prof = c->dual_prof;
-      if (dprof && !d_prof) {
-        HIP_TRY(c, d_prof.reserve(16 * 9));
-        HIP_TRY(c, hipMemset(d_prof, 0, sizeof(unsigned long long) * 16 * 9));
-      }
-      const int64_t n_hs = n_nonempty - n_dspace;
-      const size_t n_blk = (size_t)((n_hs + 63) / 64) * 64;  // position-blocked buffers
-      rc = ensure(c, c->dual_table, n_blk * 3 * c->Dp);
-      if (rc) return rc;
-      rc = ensure(c, c->out_rot[side], n_blk * c->Dp);
-      if (rc) return rc;
-      d.out_rot = c->out_rot[side];
-      k = ktimer_begin(c, pre + ".hspace", c->stream);
-      d.order = a.order + n_dspace;
-      d.n_rows = n_hs;
-      d.table = c->dual_table;
-      d.pos0 = 0;
-      HIP_TRY(c, launch_dual_ldl(d, c->stream));
-      // buckets in two lanes (the long ones on stream, the short ones on
-      // stream3) so one bucket's tail and resource shape overlap another's
-      const bool two_lanes = !c->dual_serial;
-      if (two_lanes) {
-        HIP_TRY(c, hipEventRecord(c->ev_fork3, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream3, c->ev_fork3, 0));
-      }
-      int64_t lo = n_dspace;
-      if (c->dual_max_h_side[side] > 32 * kDualMaxTiles && lo < n_nonempty) {
-        // the wide bucket, 256 < h_eff <= 512, in batches of its workspace
-        const int64_t hi = std::min(n_nonempty, first_le(32 * kDualMaxTiles));
-        const size_t per = dual_wide_zs_bytes(c->Dp) + sizeof(float) * (dual_wide_slot_floats() + 512);
-        const size_t held = c->dw_zs.cap() + sizeof(float) * (c->dw_slots.cap() + c->dw_z.cap());
-        int64_t nbat = std::max<int64_t>(
-            1, std::min<int64_t>(hi - lo, (int64_t)(ws_budget(c, held) / per)));
-        if (hi > lo) {
-          rc = ensure_batch(c, c->dw_zs, dual_wide_zs_bytes(c->Dp), &nbat);
-          if (rc) return rc;
-          rc = ensure_batch(c, c->dw_slots, dual_wide_slot_floats(), &nbat);
-          if (rc) return rc;
-          rc = ensure_batch(c, c->dw_z, (size_t)512, &nbat);
-          if (rc) return rc;
-        }
-        for (int64_t b0 = lo; b0 < hi; b0 += nbat) {
-          d.order = a.order + b0;
-          d.n_rows = std::min(nbat, hi - b0);
-          d.pos0 = b0 - n_dspace;
-          d.prof = nullptr;
-          HIP_TRY(c, launch_dual_wide(d, c->dw_zs, c->dw_slots, c->dw_z, a.fail, c->stream));
-        }
-        lo = std::max(lo, hi);
-      }
-      for (int tiles = kDualMaxTiles; tiles >= 1 && lo < n_nonempty; --tiles) {
-        const int64_t hi = std::min(n_nonempty, first_le(32 * (tiles - 1)));
-        if (hi > lo) {
-          d.order = a.order + lo;
-          d.n_rows = hi - lo;
-          d.pos0 = lo - n_dspace;
-          d.prof = dprof ? d_prof + 16 * tiles : nullptr;
-          hipStream_t ls = (two_lanes && tiles <= 4) ? c->stream3 : c->stream;
-          HIP_TRY(c, launch_dual(tiles, d, ls));
-        }
-        lo = std::max(lo, hi);
-      }
-      if (two_lanes) {
-        HIP_TRY(c, hipEventRecord(c->ev_join3, c->stream3));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join3, 0));
-      }
-      d.order = a.order + n_dspace;
-      d.n_rows = n_hs;
-      d.pos0 = 0;
-      if (!bmode) HIP_TRY(c, launch_dual_sweep(d, c->stream));  // unit table: identity
-      ktimer_end(c, k, c->stream);
-      {  // h x h system per entity: S = I + Z D^-1 Z^T (h^2 d), its LLT (h^3 / 3),
-         // the recurrence and Y^T z (4 h d); rows read twice, the LDL row
-        const double dd = c->dim;
-        const HeffSums hsum = heff_sums(c, side, vkind, n_dspace, n_nonempty);
-        const double ne = (double)(n_nonempty - n_dspace);
-        add_work(c, pre + ".hspace", hsum.h2 * dd + hsum.h3 / 3.0 + 4.0 * hsum.h1 * dd,
-                 (2.0 * dd * 4.0 + 4.0) * hsum.h1 + ne * (8.0 + 3.0 * dd * 4.0 + dd * 4.0),
-                 n_nonempty - n_dspace);
-      }
-      k = ktimer_begin(c, pre + ".rotate", c->stream);
-      HIP_TRY(c, launch_rotate(c->out_rot[side], a.order + n_dspace, 0, n_nonempty - n_dspace,
-                               c->qsplit[other][1], a.out, c->Dp, c->stream, 1));
-      ktimer_end(c, k, c->stream);
-      if (n_dspace > 0) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    }
-    t.stop();
-  }
-  const bool collective = side < 2 && c->comm;
-  if (collective) {
-    // every rank takes the same retry / NOT_SPD decision below (the
-    // smallest failing entity over all ranks), so the collectives of a
-    // rerun stay matched
-    NCCL_TRY(c, ncclAllReduce(c->d_fail, c->d_fail, 1, ncclUint64, ncclMin, c->comm, c->stream));
-  }
-  unsigned long long f = none;
-  rc = end_solve(c, side, true, &f);
-  if (rc) return rc;
-  if (getenv("FRECSYS_DUAL_PROF") && dual && c->dual_prof) {
-    // diagnostics: mean cycles per entity and phase of the workgroup kernel
-    unsigned long long hp[16 * 9];
-    HIP_TRY(c, hipMemcpy(hp, c->dual_prof, sizeof(hp), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemset(c->dual_prof, 0, sizeof(hp)));
-    for (int t = 1; t <= 8; ++t) {
-      const unsigned long long n = hp[16 * t + 4];
-      if (!n) continue;
-      fprintf(stderr, "[dual-prof] side %d tiles %d n %llu cycles/entity: setup %.0f slabs %.0f chol %.0f "
-              "yz %.0f | chain %.0f workers %.0f factored %.0f\n", side, t, n,
-              (double)hp[16 * t] / n, (double)hp[16 * t + 1] / n, (double)hp[16 * t + 2] / n,
-              (double)hp[16 * t + 3] / n, (double)hp[16 * t + 5] / n, (double)hp[16 * t + 6] / n,
-              (double)hp[16 * t + 7] / n);
-    }
-  }
-  if (f != none && c->debug_skip) {
-    // ablation builds only (FRECSYS_DEBUG_SKIP): the skipped phases leave
-    // garbage matrices by design, so a failed pivot is expected and ignored
-    // -- a timing run must reach the end of the epoch, not abort on NOT_SPD
-    return FRECSYS_OK;
-  }
-  if (f != none && dual && (collective || n_dspace < n_nonempty)) {
-    // a history-space pivot failed (or a poisoned basis after a tagged-poll
-    // timeout): the verdict is the d-space solve's.  Counted (frecsys_counter
-    // "hspace_reruns"): the whole side pays a d-space solve
-    ++c->hspace_reruns;
-    return solve_side_impl(c, side, p, true);
-  }
-  if (f != none) {
-    c->err_entity = (int64_t)f - 1;
-    return fail(c, FRECSYS_ERR_NOT_SPD,
-                "LLT failed (matrix not SPD) for entity " + std::to_string(c->err_entity));
-  }
-  return FRECSYS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int frecsys_solve_side(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p) {
-  return solve_side_impl(c, side, p, false);
-}
-
-// Conjugate-gradient form of frecsys_solve_side (cg.hip): the same sharding,
-// queue, uploads and row all-gather; no factorisation, so no NOT_SPD.
-int frecsys_solve_side_cg(frecsys_ctx* c, int32_t side, const frecsys_solve_params* p,
-                          const frecsys_cg_params* cg) {
-  if (!c || !valid_side(side) || !p || !cg)
-    return fail(c, FRECSYS_ERR_INVALID, "solve_cg: bad arguments");
-  if (cg->max_iterations < 0 || !(cg->tolerance >= 0.0f))
-    return fail(c, FRECSYS_ERR_INVALID,
-                "solve_cg: max_iterations and tolerance must be >= 0 (and not NaN)");
-  const int kind = p->kind;
-  if (kind == FRECSYS_KIND_CVAR_GRAD_U || kind == FRECSYS_KIND_CVAR_GRAD_V)
-    return fail(c, FRECSYS_ERR_INVALID,
-                "solve_cg: the CVaR gradient kinds have no conjugate-gradient form");
-  if (c->dim > 256)
-    return fail(c, FRECSYS_ERR_UNSUPPORTED,
-                "solve_cg: the conjugate-gradient path is built for dim <= 256 (dim " +
-                    std::to_string(c->dim) + ")");
-  int rc = check_solve_args(c, "solve_cg: ", side, p);
-  if (rc) return rc;
-  const bool vkind = kind == FRECSYS_KIND_WEIGHTED_V;
-  const bool ukind = kind == FRECSYS_KIND_WEIGHTED_U;
-  const int other = side == 1 ? 0 : 1;
-  rc = begin_solve(c, side, p, side < 2 ? 1 << side : 0);  // a build still reading emb[side]
-  if (rc) return rc;
-  rc = build_order(c, side);
-  if (rc) return rc;
-  const int64_t n = c->n[side];
-  rc = ensure(c, c->d_cg_iters, (size_t)std::max<int64_t>(n, 1));
-  if (rc) return rc;
-  rc = ensure(c, c->d_cg_stats, (size_t)2);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->d_cg_iters, 0xFF, sizeof(int32_t) * std::max<int64_t>(n, 1),
-                            c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_cg_stats, 0, sizeof(unsigned long long) * 2, c->stream));
-  CgArgs a{};
-  a.kind = kind;
-  a.quirk = c->quirks;
-  a.Dp = c->Dp;
-  a.dim = c->dim;
-  a.order = c->d_order[side];
-  cg_plan_batches(c->h_order[side].data(), c->order_n[side], &c->cg_bstart);
-  rc = ensure(c, c->d_cg_bstart, c->cg_bstart.size());
-  if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->d_cg_bstart, c->cg_bstart.data(),
-                            sizeof(int32_t) * c->cg_bstart.size(), hipMemcpyHostToDevice,
-                            c->stream));
-  a.bstart = c->d_cg_bstart;
-  a.n_batches = (int64_t)c->cg_bstart.size() - 1;
-  a.col = c->col[side];
-  a.X = p->from_snapshot ? c->snap[other] : c->emb[other];
-  a.n_other = c->n[other];
-  a.G = c->gram[other];
-  a.out = c->emb[side];
-  a.reg = p->reg;
-  a.reg_exp = p->reg_exp;
-  a.w = p->unobserved_weight;
-  a.alpha = p->alpha;
-  a.lambda_is_reg = p->lambda_is_reg;
-  a.entity_weight = (ukind && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
-  a.entity_reg = vkind ? c->d_entity_reg.dev.get() : nullptr;
-  a.other_weight = vkind ? c->d_other_weight.dev.get() : nullptr;
-  a.max_iter = cg->max_iterations;
-  a.tol = cg->tolerance;
-  a.iters = c->d_cg_iters;
-  a.stats = c->d_cg_stats;
-  a.fail = c->d_fail;
-  if (side < 2) emb_written(c, side);
-  c->dual_used[side] = false;
-  static const char* names[3] = {"solve_user", "solve_item", "solve_eval"};
-  const std::string pre = names[side];
-  {
-    ScopedTimer t(c, names[side]);
-    const size_t k = ktimer_begin(c, pre + ".cg", c->stream);
-    HIP_TRY(c, launch_cg(a, c->stream));
-    ktimer_end(c, k, c->stream);
-    t.stop();
-  }
-  unsigned long long f = ~0ull, st[2] = {0, 0};
-  std::vector<int32_t>& it = c->cg_iters[side];
-  it.assign((size_t)n, -1);
-  HIP_TRY(c, hipMemcpyAsync(st, c->d_cg_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-  if (n)
-    HIP_TRY(c, hipMemcpyAsync(it.data(), c->d_cg_iters, sizeof(int32_t) * n, hipMemcpyDeviceToHost,
-                              c->stream));
-  rc = end_solve(c, side, true, &f);
-  if (rc) return rc;
-  c->cg_iterations += (int64_t)st[0];
-  c->cg_unconverged += (int64_t)st[1];
-  {  // per entity and iteration: G p (2 d^2) + two passes of the history rows (4 h d)
-    const double d = c->dim;
-    const std::vector<QueueRec>& q = c->h_order[side];
-    double fl = 0.0, by = 0.0;
-    int64_t ne = 0;
-    for (const QueueRec& r : q) {
-      const int32_t i = it[(size_t)r.entity];
-      if (i < 0) continue;
-      ++ne;
-      fl += (double)i * (2.0 * d * d + 4.0 * (double)r.h * d);
-      by += (double)i * ((double)r.h * d * 4.0 + (double)r.h * 4.0);
-    }
-    add_work(c, pre + ".cg", fl, by, ne);
-  }
-  if (f != ~0ull) {
-    c->err_entity = (int64_t)f - 1;
-    return fail(c, FRECSYS_ERR_NAN,
-                "solve_cg: non-finite result row for entity " + std::to_string(c->err_entity));
-  }
-  return FRECSYS_OK;
-}
-
-int frecsys_cg_iterations(frecsys_ctx* c, int32_t side, int32_t* host) {
-  if (!c || !valid_side(side) || !host)
-    return fail(c, FRECSYS_ERR_INVALID, "cg_iterations: bad arguments");
-  const std::vector<int32_t>& it = c->cg_iters[side];
-  for (int64_t i = 0; i < c->n[side]; ++i) host[i] = (size_t)i < it.size() ? it[(size_t)i] : -1;
-  return FRECSYS_OK;
-}
-
 int frecsys_user_loss(frecsys_ctx* c, int32_t side, float beta, int32_t half, float* host_out) {
   if (!c || (side != 0 && side != 2)) return fail(c, FRECSYS_ERR_INVALID, "loss: bad side");
   if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "loss: no CSR loaded");
@@ -1934,204 +1198,6 @@ int frecsys_eval_topk(frecsys_ctx* c, int32_t k, int32_t* topk) {
   return FRECSYS_OK;
 }
 
-int frecsys_pp_set_rating_index(frecsys_ctx* c, int32_t side, const int32_t* rix) {
-  if (!c || (side != 0 && side != 1) || !rix)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_set_rating_index: bad arguments");
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "pp_set_rating_index: no CSR");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int64_t nnz = c->nnz[side];
-  for (int64_t k = 0; k < nnz; ++k)
-    if (rix[k] < 0 || rix[k] >= nnz)
-      return fail(c, FRECSYS_ERR_INVALID, "pp_set_rating_index: index out of range");
-  HIP_TRY(c, renew(c->d_rix[side], (size_t)nnz));
-  if (nnz)
-    HIP_TRY(c, hipMemcpy(c->d_rix[side], rix, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
-  return ensure(c, c->d_pred[0], (size_t)std::max<int64_t>(nnz, 1));
-}
-
-namespace {
-PPArgs pp_args(frecsys_ctx* c, int side) {
-  const int other = side == 1 ? 0 : 1;
-  PPArgs a{};
-  a.col = c->col[side];
-  a.rix = side == 2 ? nullptr : c->d_rix[side];
-  a.pred = c->d_pred[side == 2 ? 1 : 0];
-  a.X = c->emb[other];
-  a.G = c->gram[other];
-  a.E = c->emb[side];
-  a.Dp = c->Dp;
-  a.n_other = c->n[other];
-  a.fail = c->d_fail;
-  return a;
-}
-}  // namespace
-
-int frecsys_pp_predict(frecsys_ctx* c, int32_t side) {
-  if (!c || (side != 0 && side != 2)) return fail(c, FRECSYS_ERR_INVALID, "pp_predict: bad side");
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "pp_predict: no CSR");
-  if (side == 0 && !c->d_rix[0])
-    return fail(c, FRECSYS_ERR_INVALID, "pp_predict: no rating index (pp_set_rating_index)");
-  if (c->pp_old_side != -1)  // the other ranks' updates of the last block are not in yet
-    return fail(c, FRECSYS_ERR_INVALID, "pp_predict: pp_sync pending for the last sharded block step");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (side == 2) {
-    int rc = ensure(c, c->d_pred[1], (size_t)std::max<int64_t>(c->nnz[2], 1));
-    if (rc) return rc;
-  }
-  PPArgs a = pp_args(c, side);
-  HIP_TRY(c, launch_pp_predict(a, c->rp[side], c->n[side], c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return FRECSYS_OK;
-}
-
-int frecsys_pp_step(frecsys_ctx* c, int32_t side, int32_t start, int32_t end,
-                    const frecsys_solve_params* p, double* residual) {
-  if (!c || !valid_side(side) || !p) return fail(c, FRECSYS_ERR_INVALID, "pp_step: bad arguments");
-  if (start < 0 || end > c->dim || end - start < 1 || end - start > 128)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: block must satisfy 0 <= start < end <= dim, "
-                                        "end - start <= 128");
-  if (!c->rp[side]) return fail(c, FRECSYS_ERR_INVALID, "pp_step: no CSR");
-  if (side != 2 && !c->d_rix[side])
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: no rating index (pp_set_rating_index)");
-  if (!c->d_pred[side == 2 ? 1 : 0])
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: no prediction vector (pp_predict)");
-  const int kind = p->kind;
-  if (kind != FRECSYS_KIND_IALS && kind != FRECSYS_KIND_WEIGHTED_U &&
-      kind != FRECSYS_KIND_WEIGHTED_V)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: kind must be IALS, WEIGHTED_U or WEIGHTED_V");
-  if (kind == FRECSYS_KIND_WEIGHTED_V && (!p->entity_reg || !p->other_weight))
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: WEIGHTED_V needs entity_reg and other_weight");
-  // external-exchange mode: a second step before frecsys_pp_sync would
-  // overwrite the snapshot the other ranks' prediction updates are replayed
-  // from, and this rank's predictions would drift from theirs
-  if (c->pp_old_side != -1)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_step: pp_sync pending for the last sharded block step");
-  int rc = begin_solve(c, side, p, 3);
-  if (rc) return rc;
-  if (side < 2) emb_written(c, side);
-  // world > 1 (USER / ITEM): this rank's shard of the rows -- the per-row
-  // block steps are independent given the predictions, which every rank then
-  // brings up to date for the other ranks' rows (pp_refresh_kernel, bitwise
-  // the owner's update); EVAL rows are not sharded
-  const bool sharded = side < 2 && c->world > 1;
-  const bool xchg = sharded && in_call_exchange(c);  // RCCL or the caller's transport
-  int64_t lo = 0, hi = c->n[side];
-  if (sharded) shard(c, side, &lo, &hi);
-  const int bw = end - start;
-  if (sharded) {  // the block columns before the step: the refresh replays Delta from them
-    rc = ensure(c, c->d_pp_old, (size_t)std::max<int64_t>(c->n[side], 1) * bw);
-    if (rc) return rc;
-    if (c->n[side])
-      HIP_TRY(c, hipMemcpy2DAsync(c->d_pp_old, sizeof(float) * bw, c->emb[side] + start,
-                                  sizeof(float) * c->Dp, sizeof(float) * bw, c->n[side],
-                                  hipMemcpyDeviceToDevice, c->stream));
-  }
-  std::vector<QueueRec> recs((size_t)(hi - lo));
-  const std::vector<int64_t>& rp = side == 2 ? c->host_rp_eval : c->host_rp[side];
-  for (int64_t i = lo; i < hi; ++i) recs[i - lo] = QueueRec{(int32_t)i, (int32_t)(rp[i + 1] - rp[i]), rp[i]};
-  std::stable_sort(recs.begin(), recs.end(),
-                   [](const QueueRec& x, const QueueRec& y) { return x.h > y.h; });
-  DevBuf<QueueRec> d_q;
-  HIP_TRY(c, d_q.reserve(recs.size()));
-  HIP_TRY(c, hipMemcpyAsync(d_q, recs.data(), sizeof(QueueRec) * recs.size(), hipMemcpyHostToDevice,
-                            c->stream));
-  rc = ensure(c, c->d_resid, std::max<size_t>(recs.size(), 1));
-  if (rc) return rc;
-  PPArgs a = pp_args(c, side);
-  a.order = d_q;
-  a.n_rows = (int64_t)recs.size();
-  a.start = start;
-  a.bw = end - start;
-  a.kind = kind;
-  a.reg = p->reg;
-  a.reg_exp = p->reg_exp;
-  a.w = p->unobserved_weight;
-  a.alpha = p->alpha;
-  a.entity_weight =
-      (kind == FRECSYS_KIND_WEIGHTED_U && p->entity_weight) ? c->d_entity_weight.dev.get() : nullptr;
-  a.entity_reg = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_entity_reg.dev.get() : nullptr;
-  a.other_weight = kind == FRECSYS_KIND_WEIGHTED_V ? c->d_other_weight.dev.get() : nullptr;
-  a.resid = c->d_resid;
-  const unsigned long long none = ~0ull;
-  {
-    ScopedTimer t(c, "pp_step");
-    HIP_TRY(c, launch_pp_step(a, c->stream));
-    if (sharded && !xchg) {  // the caller exchanges the rows, then frecsys_pp_sync
-      c->pp_old_side = side;
-      c->pp_old_start = start;
-      c->pp_old_bw = bw;
-    }
-    if (xchg) {
-      // the rows of every rank, then the other ranks' prediction updates
-      rc = xchg_rows(c, c->emb[side], side, c->Dp);
-      if (rc) return rc;
-      HIP_TRY(c, launch_pp_refresh(a, c->rp[side], c->d_pp_old, c->n[side], lo, hi, c->stream));
-    }
-    t.stop();
-  }
-  if (xchg) {  // every rank takes the same NOT_SPD verdict
-    rc = xchg_min_u64(c, c->d_fail);
-    if (rc) return rc;
-  }
-  std::vector<float> res(recs.size());
-  unsigned long long f = none;
-  if ((residual || xchg) && !recs.empty())
-    HIP_TRY(c, hipMemcpyAsync(res.data(), c->d_resid, sizeof(float) * recs.size(),
-                              hipMemcpyDeviceToHost, c->stream));
-  rc = end_solve(c, side, false, &f);  // the rows were exchanged under the step's timer
-  if (rc) return rc;
-  HIP_TRY(c, d_q.release());
-  if (f != none) {
-    c->err_entity = (int64_t)(f - 1);
-    return fail(c, FRECSYS_ERR_NOT_SPD, "pp_step: block matrix not SPD");
-  }
-  double s = 0.0;
-  if (xchg) {
-    // every rank's per-row residuals (all-gathered as a one-column table,
-    // whether or not this rank asked for the sum: the ranks' exchanges stay
-    // in step), summed in the single-rank queue order -- every row of the
-    // side by decreasing h: the world-1 sum bit for bit
-    const int64_t n = c->n[side];
-    std::vector<int32_t>& all = c->pp_order_all[side];
-    if ((int64_t)all.size() != n) {
-      all.resize((size_t)n);
-      for (int64_t i = 0; i < n; ++i) all[i] = (int32_t)i;
-      std::stable_sort(all.begin(), all.end(), [&](int32_t x, int32_t y) {
-        return rp[x + 1] - rp[x] > rp[y + 1] - rp[y];
-      });
-    }
-    std::vector<float> ent((size_t)std::max<int64_t>(n, 1), 0.0f);
-    for (size_t i = 0; i < recs.size(); ++i) ent[recs[i].entity] = res[i];
-    rc = ensure(c, c->d_resid_e, (size_t)std::max<int64_t>(n, 1));
-    if (rc) return rc;
-    if (n) HIP_TRY(c, hipMemcpyAsync(c->d_resid_e, ent.data(), sizeof(float) * n,
-                                     hipMemcpyHostToDevice, c->stream));
-    rc = xchg_rows(c, c->d_resid_e, side, 1);
-    if (rc) return rc;
-    if (n) HIP_TRY(c, hipMemcpyAsync(ent.data(), c->d_resid_e, sizeof(float) * n,
-                                     hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int32_t e : all) s += (double)ent[e];
-  } else {
-    for (float v : res) s += (double)v;  // zero rows (empty histories) stay 0
-  }
-  if (residual) *residual = s;
-  return FRECSYS_OK;
-}
-
-int frecsys_pp_get_predictions(frecsys_ctx* c, int32_t side, float* host) {
-  if (!c || (side != 0 && side != 2) || !host)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_get_predictions: bad arguments");
-  const float* p = c->d_pred[side == 2 ? 1 : 0];
-  if (!p) return fail(c, FRECSYS_ERR_INVALID, "pp_get_predictions: no prediction vector");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const int64_t nnz = c->nnz[side];
-  if (nnz)
-    HIP_TRY(c, hipMemcpyAsync(host, p, sizeof(float) * nnz, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return FRECSYS_OK;
-}
-
 int frecsys_set_transport(frecsys_ctx* c, const frecsys_transport* t) {
   if (!c) return FRECSYS_ERR_INVALID;
   if (t && (!t->allgather_rows || !t->allreduce_min_u64))
@@ -2140,22 +1206,6 @@ int frecsys_set_transport(frecsys_ctx* c, const frecsys_transport* t) {
     return fail(c, FRECSYS_ERR_INVALID, "set_transport: pp_sync pending");
   c->has_transport = t != nullptr;
   c->transport = t ? *t : frecsys_transport{};
-  return FRECSYS_OK;
-}
-
-int frecsys_pp_sync(frecsys_ctx* c, int32_t side) {
-  if (!c || (side != 0 && side != 1)) return fail(c, FRECSYS_ERR_INVALID, "pp_sync: bad side");
-  if (c->pp_old_side != side)
-    return fail(c, FRECSYS_ERR_INVALID, "pp_sync: no sharded block step of this side pending");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int64_t lo, hi;
-  shard(c, side, &lo, &hi);
-  PPArgs a = pp_args(c, side);
-  a.start = c->pp_old_start;
-  a.bw = c->pp_old_bw;
-  HIP_TRY(c, launch_pp_refresh(a, c->rp[side], c->d_pp_old, c->n[side], lo, hi, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->pp_old_side = -1;
   return FRECSYS_OK;
 }
 

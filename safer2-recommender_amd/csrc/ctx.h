@@ -1,7 +1,8 @@
 // ctx.h -- what every host translation unit of libfrecsys_hip.so shares: the
 // context behind the C-ABI's opaque frecsys_ctx, the error path, the work
-// accounting and the call timer.  Internal header.  The functions that are
-// not templates are defined once, in capi.hip.
+// accounting, the call timer, and the helpers of capi.hip that the solve
+// drivers of train.hip use too.  Internal header.  The functions that are
+// neither templates nor inline are defined once, in capi.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -273,6 +274,90 @@ int ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count) {
                             : "hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)): ") +
                   hipGetErrorString(e));
 }
+
+// From here on: what capi.hip shares with train.hip alone.  Hidden, so the
+// library's dynamic symbols stay the C-ABI and what they were.
+#pragma GCC visibility push(hidden)
+
+// ensure() that reports an out-of-memory hipMalloc instead of failing
+// (DevBuf::try_reserve): *oom is set and the buffer left empty.
+template <typename T>
+int try_ensure(frecsys_ctx* c, DevBuf<T>& b, size_t count, bool* oom) {
+  const hipError_t e = b.try_reserve(count, oom);
+  if (e == hipSuccess) return FRECSYS_OK;
+  return fail(c, FRECSYS_ERR_HIP,
+              std::string(b ? "hipFree(*p): " : "hipMalloc: ") + hipGetErrorString(e));
+}
+
+// A fresh allocation of `count` elements whatever the buffer held (a table
+// replaced as a whole: CSR arrays, queues).
+template <typename T>
+hipError_t renew(DevBuf<T>& b, size_t count) {
+  const hipError_t e = b.release();
+  return e != hipSuccess ? e : b.reserve(count);
+}
+
+// The wide workspaces' budget and the room a cut one leaves (capi.hip).
+size_t ws_budget(frecsys_ctx* c, size_t held);
+bool below_headroom();
+
+// A workspace of *batch slots of `per` elements: a failed hipMalloc halves
+// the batch (counted in ws_shrinks) until one slot does not fit either, and a
+// batch that fits only after such a cut is halved on while it leaves less
+// than kRuntimeHeadroom free.  Entities are independent, so the batch size
+// never changes a result.
+template <typename T>
+int ensure_batch(frecsys_ctx* c, DevBuf<T>& b, size_t per, int64_t* batch) {
+  bool cut = false;
+  while (true) {
+    bool oom = false;
+    int rc = try_ensure(c, b, per * (size_t)*batch, &oom);
+    if (rc) return rc;
+    if (!oom) {
+      if (!cut || *batch <= 1 || !below_headroom()) return FRECSYS_OK;
+      HIP_TRY(c, b.release());
+    } else if (*batch <= 1) {
+      return fail(c, FRECSYS_ERR_HIP, "hipMalloc: out of memory for one workspace slot");
+    }
+    *batch = (*batch + 1) / 2;
+    ++c->ws_shrinks;
+    cut = true;
+  }
+}
+
+// h_eff: the rows of the other side that the assembly of an entity with h
+// history entries reads (vq: the V kinds, whose tail quirk rounds a history
+// above 128 up to whole 128-row blocks).  Monotone in h.
+inline int64_t queue_heff(int quirks, bool vq, int64_t h) {
+  return (vq && quirks && h > 128 && (h % 128) != 0) ? h + 128 - (h % 128) : h;
+}
+struct HeffSums {
+  double h1 = 0, h2 = 0, h3 = 0;
+  int64_t nz = 0;
+};
+
+// Shared by capi.hip and train.hip; each is described at its definition.
+bool valid_side(int side);
+void shard(const frecsys_ctx* c, int side, int64_t* lo, int64_t* hi);
+int build_order(frecsys_ctx* c, int side);
+HeffSums heff_sums(frecsys_ctx* c, int side, bool vq, int64_t lo, int64_t hi);
+int join_eager(frecsys_ctx* c, int mask, hipStream_t s);
+void emb_written(frecsys_ctx* c, int side);
+int prepare_basis(frecsys_ctx* c, int other, const float* X, hipStream_t s, int mode = 0,
+                  float mu = 0.f, float lam = 0.f, const QueueRec* rows = nullptr,
+                  int64_t nrows = 0, uint64_t sub = 0);
+int hspace_rows(frecsys_ctx* c, int side, int other, int64_t q0, int64_t q1,
+                const QueueRec** rows, int64_t* nrows, uint64_t* sub);
+int allgather_rows(frecsys_ctx* c, float* base, int side, int64_t ld);
+bool in_call_exchange(const frecsys_ctx* c);
+int xchg_rows(frecsys_ctx* c, float* base, int side, int64_t ld);
+int xchg_min_u64(frecsys_ctx* c, unsigned long long* dval);
+int upload(frecsys_ctx* c, UploadBuf& b, const float* host, size_t n);
+size_t ktimer_begin(frecsys_ctx* c, const std::string& name, hipStream_t s);
+void ktimer_end(frecsys_ctx* c, size_t i, hipStream_t s);
+void flush_ktimers(frecsys_ctx* c);
+
+#pragma GCC visibility pop
 
 struct ScopedTimer {
   frecsys_ctx* c;

@@ -1,5 +1,5 @@
-// kernels.h -- launch interface between the C-ABI host code (capi.hip, serve.hip) and
-// the gfx950 kernels (solve.hip, gramian.hip, loss.hip).  Internal header.
+// kernels.h -- launch interface between the C-ABI host code (capi.hip, train.hip,
+// serve.hip) and the gfx950 kernels (solve.hip, gramian.hip, loss.hip).  Internal header.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 """One deterministic fixture that puts an entity on every history-length seam
-of the solve paths (capi.hip solve_side_impl queue split, solve.hip slabs,
+of the solve paths (train.hip plan_side queue split, solve.hip slabs,
 dual.hip buckets), and the float64 / oracle references of a half-step on it.
 
 The "seam entities" are the solved side: S histories over N_OTHER = 704 rows

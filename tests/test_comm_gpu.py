@@ -3,7 +3,7 @@ world-1 communicator (frecsys_comm_init with a unique id) makes every
 collective of a half-step run -- the grouped ncclBroadcast all-gather of the
 Gramian's group slabs, the all-gather of factor rows and of the user losses,
 and the ncclMin agreement on a failed pivot (include/frecsys_hip.h,
-capi.hip).  Results must be bit-identical to the communicator-free context.
+capi.hip, train.hip).  Results must be bit-identical to the communicator-free context.
 """
 import numpy as np
 import pytest

@@ -243,7 +243,7 @@ def test_eval_side_dual(monkeypatch, ml1m):
 
 def _buckets(h):
     """History-space bucket t (32 (t-1) < h <= 32 t) per entity, as the host
-    queue split in capi.hip solve_side_impl assigns them (iALS: h_eff = h)."""
+    queue split in train.hip plan_side assigns them (iALS: h_eff = h)."""
     b = np.ceil(np.asarray(h) / 32.0).astype(int)
     return [int(((b == t) & (np.asarray(h) > 0)).sum()) for t in range(1, 9)]
 

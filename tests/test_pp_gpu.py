@@ -83,6 +83,55 @@ def test_pp_fold_in_from_zero(ml1m, dim, bs):
     assert rel_rows(ctx.get_embeddings(fh.SIDE_EVAL), Ue).max() < TOL_ROW
 
 
+def test_pp_step_uses_side_queue(quirk_data):
+    """frecsys_pp_step runs on the side's own queue (build_order), the one
+    frecsys_solve_side builds and reuses.  (a) A context whose USER queue a
+    solve built gives, bit for bit, the block-step epoch of a fresh context
+    that starts from the same tables.  (b) On EVAL, loading another CSR (other
+    row count, other lengths) after a block step rebuilds the queue: the result
+    is bit for bit a fresh context's that only saw the second CSR."""
+    nu, ni, up, uc, ip, ic = quirk_data
+    dim, bs, reg, w = 32, 8, 0.003, 0.1
+    urix, _ = _rix(uc)
+
+    def user_epoch(ctx):
+        ctx.pp_set_rating_index(fh.SIDE_USER, urix)
+        ctx.pp_predict(fh.SIDE_USER)
+        res = [ctx.pp_step(fh.SIDE_USER, s, s + bs, reg, w) for s in range(0, dim, bs)]
+        return ctx.get_embeddings(fh.SIDE_USER), res
+
+    a, U, V = _ctx(dim, nu, ni, up, uc, ip, ic)
+    a.gramian(fh.SIDE_ITEM)
+    a.solve_side(fh.SIDE_USER, fh.KIND_IALS, reg, w)
+    U1 = a.get_embeddings(fh.SIDE_USER)
+    assert not np.array_equal(U1, U)
+    b, _, _ = _ctx(dim, nu, ni, up, uc, ip, ic)
+    b.set_embeddings(fh.SIDE_USER, U1)
+    b.gramian(fh.SIDE_ITEM)
+    Ua, ra = user_epoch(a)
+    Ub, rb = user_epoch(b)
+    np.testing.assert_array_equal(Ua, Ub)
+    assert ra == rb and not np.array_equal(Ua, U1)
+
+    def eval_epoch(ctx, r0, r1):
+        ep = (up[r0:r1 + 1] - up[r0]).astype(np.int64)
+        ctx.load_csr(fh.SIDE_EVAL, ep, uc[up[r0]:up[r1]])
+        ctx.set_embeddings(fh.SIDE_EVAL, np.zeros((r1 - r0, dim), np.float32))
+        ctx.pp_predict(fh.SIDE_EVAL)
+        res = [ctx.pp_step(fh.SIDE_EVAL, s, s + bs, reg, w) for s in range(0, dim, bs)]
+        return ctx.get_embeddings(fh.SIDE_EVAL), res
+
+    assert sorted(np.diff(up[0:51])) != sorted(np.diff(up[100:138]))
+    eval_epoch(a, 0, 50)
+    Ea, rea = eval_epoch(a, 100, 137)
+    Eb, reb = eval_epoch(b, 100, 137)
+    assert Ea.shape == (37, dim) and np.abs(Ea).max() > 0
+    np.testing.assert_array_equal(Ea, Eb)
+    assert rea == reb
+    a.close()
+    b.close()
+
+
 def test_pp_rejects_bad_block(quirk_data):
     nu, ni, up, uc, ip, ic = quirk_data
     ctx, U, V = _ctx(256, nu, ni, up, uc, ip, ic)

@@ -1,5 +1,5 @@
 """The iALS++ / SAFER2++ block step (csrc/pp.hip: pp_block_kernel<TB>,
-pp_predict_kernel, pp_refresh_kernel; frecsys_pp_* in capi.hip) at its seams
+pp_predict_kernel, pp_refresh_kernel; frecsys_pp_* in train.hip) at its seams
 against float64.
 
 One block step per case of tests/pp_ref.py on the seam fixture: every TB at

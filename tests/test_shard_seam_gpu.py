@@ -102,7 +102,7 @@ def _counts(ctx, c):
 
 
 def _assembly_rows(c):
-    """h_eff as capi.hip counts it: the tail quirk for both V kinds."""
+    """h_eff as ctx.h queue_heff counts it: the tail quirk for both V kinds."""
     return S.h_eff(c.h, c.quirk and c.kind in (fh.KIND_WEIGHTED_V, fh.KIND_CVAR_GRAD_V))
 
 
@@ -224,7 +224,7 @@ def test_seam_fixture_sharded_solve(monkeypatch, key, dim, world, mode):
     dual = fh.padded_dim(dim) >= 64 and c.kind < fh.KIND_CVAR_GRAD_U and mode == "default"
     live = [int((c.h[lo:hi] > 0).sum()) for lo, hi in D.shards(D.BOUNDS["seam", world])]
     if dual and world == 8 and fh.padded_dim(dim) <= 256 and (c.h_eff == c.h).all():
-        # the three branches of solve_side_impl: shard 0 wholly in history
+        # the three branches of train.hip solve_side: shard 0 wholly in history
         # space, shards 1-4 wholly in d-space, shard 5 mixed
         assert hs[0] == live[0] == 22 and hs[1:5] == [0, 0, 0, 0] and 0 < hs[5] < live[5]
     if dual and world == 3 and fh.padded_dim(dim) <= 256:

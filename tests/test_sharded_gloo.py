@@ -2,7 +2,7 @@
 (gloo; no GPU here -- tests/test_sharded_gloo_gpu.py runs the same exchange
 between processes driving the real HIP kernels on the GPU box).
 
-The product's N>1 path (capi.hip) is: the rank's groups of the partition-
+The product's N>1 path (capi.hip, train.hip) is: the rank's groups of the partition-
 independent Gramian plan (frecsys_gram_plan, called here through the real
 C-ABI: fixed leaves of rows, fixed groups of leaves, each rank a contiguous
 run of groups) -> all-gather of the group slabs -> every rank sums the slabs
