@@ -707,6 +707,111 @@ int frecsys_sampled_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
 #define FRECSYS_SIM_KEEP_SELF 2 /* without it a query row never lists itself */
 int frecsys_similar(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                     int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids, float* scores);
+/* Diversified lists: greedy maximal-marginal-relevance (MMR) re-ranking of a
+ * pool of items per query row (no reference counterpart).  The three calls
+ * below share one definition, fixed to the bit; frecsys_mmr_select is that
+ * definition in scalar C++ on the host, and the two device calls return its
+ * bits.
+ *   Pool.  A row has `pool` slots (1 <= k <= pool <= 1024) of an item id and
+ * an fp32 score.  A slot with a negative id is empty; ids may repeat, and each
+ * slot is a candidate of its own.  p = the number of filled slots.
+ *   Relevance.  With FRECSYS_DIV_RAW_SCORES rel_b = score_b.  Otherwise smax
+ * and smin are the largest and smallest score of the filled slots, range =
+ * smax - smin, and rel_b = range > 0 ? (score_b - smin) / range : 0.0f; the
+ * subtractions and the division are single correctly rounded fp32 operations.
+ *   Similarity of slot a (already selected) and slot b (a candidate), over
+ * the item table Y: g = dot(Y[id_a], Y[id_b]) is frecsys_similar's chain, acc
+ * = fma(Y[id_a][c], Y[id_b][c], acc) over c ascending from +0; n2_r =
+ * dot(r, r); inv_r = n2_r > 0 ? 1.0f / sqrtf(n2_r) : 0.0f with correctly
+ * rounded sqrt and division; cos(a, b) = (g * inv_a) * inv_b + 0.0f, the two
+ * fp32 multiplies in exactly that order.  A zero item row has cosine +0 with
+ * everything.
+ *   Greedy selection.  lam is in [0, 1], oml = 1.0f - lam, base_b = lam *
+ * rel_b.  Step 0: v_b = base_b + 0.0f.  Step t >= 1: m_b = fmaxf over the
+ * selected slots s_u, u < t, of cos(s_u, b) (m_b may be negative: it is not
+ * clamped at 0), and v_b = (base_b - oml * m_b) + 0.0f -- a separate fp32
+ * multiply and subtraction, never contracted into an fma.  s_t is the
+ * unselected filled slot with the largest word score_key(v_b) << 32 | ~b
+ * (score_key: the order-preserving map of the fp32 bits to uint32): the
+ * largest v, ties to the lower slot -- in a pool from frecsys_recommend that
+ * is the higher score, then the lower id.
+ *   Outputs (host), per row and t < k: items[t] = the id of s_t, scores[t] =
+ * its pool score with its bits unchanged, and, unless mmr is NULL, mmr[t] = v
+ * at its selection.  For t >= p: -1, -FLT_MAX and -FLT_MAX.  No output ever
+ * holds -0.0 in mmr.  At lam = 1 the selection is the first k slots of the
+ * pool in (score descending, slot ascending) order.
+ * No output bit depends on the batch, the grid, the workspace budget, the
+ * item splits, the other rows, or how the pool reached the device.
+ * FRECSYS_ERR_INVALID for all three: pool outside [1, 1024], k outside
+ * [1, pool], lam outside [0, 1] or NaN, an unknown flag bit, a negative row
+ * count, null outputs (items, scores) with rows > 0.  Zero rows return
+ * FRECSYS_OK and touch nothing.
+ *
+ * frecsys_mmr_select: host only -- no context, no HIP call.  item_table is
+ * row-major [n_items][ld] with ld >= dim >= 1; lists / list_scores are
+ * [n][pool]; items / scores / mmr are [n][k].  Also FRECSYS_ERR_INVALID: a
+ * null table or pool array, an id >= n_items, a non-finite score in a filled
+ * slot, and (without FRECSYS_DIV_RAW_SCORES) a non-finite range. */
+#define FRECSYS_DIV_RAW_SCORES 2 /* rel = the pool score; without it: min-max normalised */
+int frecsys_mmr_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
+                       int32_t k, float lam, int32_t flags, int32_t* items, float* scores,
+                       float* mmr);
+/* frecsys_mmr_select (above: the pool, the relevance, the cosine chain, the
+ * greedy steps, the tie order and the outputs are stated there in full and
+ * hold here to the bit) of caller-supplied pools against the context's ITEM
+ * table: lists / list_scores are host [n][pool] from anywhere
+ * (frecsys_rank_candidates, frecsys_similar, another retriever).  Per row
+ * batch the pools are uploaded, div_gram_kernel forms G = T T^T over the
+ * pool's item rows (v_mfma_f32_32x32x2_f32, one accumulator chain per element
+ * over the padded dim: the chain above, pad columns add +0), and
+ * div_select_kernel runs the greedy steps, one wave per row, reading row s_t
+ * of G per step.  Workspace: frecsys_recommend's buffer and budget
+ * (FRECSYS_RECOMMEND_WS_MB, read per call, changes no result bit); per row of a
+ * batch 8 pool + 4 pool^2 + 12 k bytes, at least one row per batch; released
+ * by frecsys_release_workspaces.  Rank-local: no collective.
+ * FRECSYS_DIVERSIFY_VARIANT (read per call, changes no result bit): "gram" is
+ * the pair above; "lazy" forms no Gramian -- the selection computes row s_t of
+ * it per step from the item table (k pool d products instead of pool^2 d / 2,
+ * no 4 pool^2 bytes, no "diversify.gram") -- and books 2 (k + 1) pool d + 5 k
+ * pool flops and 4 (k + 1) pool d + 8 pool + 8 k bytes per row; unset: "gram",
+ * the faster of the two at every shape measured.
+ * FRECSYS_ERR_INVALID, before any device call: the common cases above, a null
+ * context, a null pool array, an id >= items, a non-finite score in a filled
+ * slot, a non-finite range (normalised mode).  Timer keys "diversify.gram"
+ * and "diversify.select" (one launch each per Gramian sub-batch);
+ * frecsys_work("diversify"): per row pool (pool + 1) d + 5 k pool flops, bytes
+ * = 4 pool d + 4 pool^2 + 4 k pool + 8 pool + 8 k (12 k with mmr). */
+int frecsys_diversify(frecsys_ctx* ctx, const int32_t* lists, const float* list_scores, int64_t n,
+                      int32_t pool, int32_t k, float lam, int32_t flags, int32_t* items,
+                      float* scores, float* mmr);
+/* frecsys_recommend(side, rows, k = pool, flags & FRECSYS_REC_EXCLUDE_HISTORY,
+ * item_mask) followed by frecsys_mmr_select (above: pool, relevance, cosine
+ * chain, greedy steps, tie order and outputs as stated there, to the bit) on
+ * the lists and scores it returns -- with the pools never leaving the device:
+ * behind each row batch's scan the two kernels of frecsys_diversify run on the
+ * batch's lists where the scan left them, and only the [rows][k] selection
+ * goes to the host.  The slots beyond a row's eligible count are empty.  side
+ * is USER or EVAL; flags is a subset of FRECSYS_REC_EXCLUDE_HISTORY |
+ * FRECSYS_DIV_RAW_SCORES.  At lam = 1 items and scores are
+ * frecsys_recommend(k)'s.  Workspace, knobs and rejections are
+ * frecsys_recommend's, with 12 k more bytes per row of a batch, and the common
+ * cases above; the Gramians lie behind the batch regions and are formed for
+ * sub-batches of the batch's rows, 4 pool^2 bytes a row within a budget of the
+ * same size (at least one row), so that a large pool does not shorten the
+ * scan's batches: the workspace of this call is at most twice
+ * FRECSYS_RECOMMEND_WS_MB plus one Gramian and the per-call regions, not once
+ * as for frecsys_recommend.  FRECSYS_DIVERSIFY_VARIANT as in frecsys_diversify.
+ * Unlike frecsys_diversify this call cannot look at the pools before the
+ * device forms them: it assumes finite scores and a finite range.  A pool
+ * whose range overflows has rel = 0, one with a non-finite score follows the
+ * fp32 operations above as they come (frecsys_mmr_select rejects both).
+ * Timer keys "recommend", "diversify.gram",
+ * "diversify.select"; frecsys_work("recommend") as frecsys_recommend(k =
+ * pool), frecsys_work("diversify") as frecsys_diversify. */
+int frecsys_recommend_diverse(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                              int32_t k, int32_t pool, float lam, int32_t flags,
+                              const uint8_t* item_mask, int32_t* items, float* scores, float* mmr);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,

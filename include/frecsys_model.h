@@ -111,6 +111,41 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                     const int32_t* hist_items, int64_t n, int32_t k,
                                     int32_t exclude_seen, const uint8_t* item_mask,
                                     int32_t* items, float* scores);
+/* Diversified lists for n trained users: greedy maximal-marginal-relevance
+ * (MMR) re-ranking of each user's `pool` best items down to k
+ * (frecsys_recommend_diverse, frecsys_hip.h, where the pool, the relevance,
+ * the cosine chain, the greedy steps, the tie order and the outputs are fixed
+ * to the bit): frecsys_model_recommend(k = pool) followed by
+ * frecsys_mmr_select on its lists against the model's item table, with the
+ * pools never leaving the device.  1 <= k <= pool <= 1024; lam in [0, 1]
+ * (1: frecsys_model_recommend(k)'s lists); raw_scores != 0: relevance = the
+ * score itself instead of its min-max normalisation over the pool;
+ * exclude_seen and item_mask as in frecsys_model_recommend.  items / scores:
+ * host [n * k]; mmr: host [n * k] or NULL, the MMR value of each selection.
+ * The errors are frecsys_recommend_diverse's, reported before any device
+ * call. */
+int frecsys_model_recommend_diverse(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                    int32_t pool, float lam, int32_t raw_scores,
+                                    int32_t exclude_seen, const uint8_t* item_mask,
+                                    int32_t* items, float* scores, float* mmr);
+/* The same for n unseen users given by their histories (as
+ * frecsys_model_recommend_fold_in): the model's fold-in projection into the
+ * EVAL side of its context, where the projected rows stay, then the
+ * diversified lists of those rows; exclude_seen drops the given history.  A
+ * bad argument is reported before anything is projected. */
+int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                            const int32_t* hist_items, int64_t n, int32_t k,
+                                            int32_t pool, float lam, int32_t raw_scores,
+                                            int32_t exclude_seen, const uint8_t* item_mask,
+                                            int32_t* items, float* scores, float* mmr);
+/* The same selection from caller-supplied pools (frecsys_diversify,
+ * frecsys_hip.h; its errors): lists / list_scores: host [n * pool] item ids
+ * (negative: an empty slot; repeats are candidates of their own) and scores
+ * from anywhere -- frecsys_model_rank_candidates, frecsys_model_similar_items,
+ * another retriever --, diversified against the model's item table. */
+int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float* list_scores,
+                            int64_t n, int32_t pool, int32_t k, float lam, int32_t raw_scores,
+                            int32_t* items, float* scores, float* mmr);
 /* scores[i] = the model's score of items[i] for trained user users[i] (a row
  * of U), n pairs, any order, repeats allowed; host arrays [n].  Bit for bit
  * the score frecsys_model_recommend lists for that user and item

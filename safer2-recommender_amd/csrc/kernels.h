@@ -461,6 +461,35 @@ int positions_max_splits(int64_t m);
 // alone.
 hipError_t launch_row_inv_norm(const float* T, int64_t m, int Dp, float* inv, hipStream_t s);
 
+// Greedy MMR re-ranking of a pool per row (diversify.hip; the semantics are
+// frecsys_mmr_select's in include/frecsys_hip.h, to the bit).  Row i has the
+// slots ids[i*pool .. i*pool+pool) (negative: empty; repeats are slots of
+// their own) with the scores pool_scores[...].  launch_diversify_gram writes
+// G[i] = T T^T over the slots' item rows (an empty slot: a zero row), every
+// element the chain acc = fmaf(Y[a][c], Y[b][c], acc), c ascending from +0
+// over the padded dim; launch_diversify_select reads it and writes the k
+// selected ids, their pool scores and (unless out_mmr is null) their MMR
+// values, -1 / -FLT_MAX / -FLT_MAX beyond the filled count.
+constexpr int kDiversifyMaxPool = 1024;
+struct DiversifyArgs {
+  const float* Y;            // items, ld = Dp
+  int Dp;
+  int64_t n;                 // rows of this batch
+  int pool;                  // slots per row, 1 .. kDiversifyMaxPool
+  int k;                     // 1 .. pool
+  float lam;                 // in [0, 1]
+  int raw;                   // != 0: rel = score (FRECSYS_DIV_RAW_SCORES)
+  const int32_t* ids;        // [n][pool], each negative or in [0, items)
+  const float* pool_scores;  // [n][pool]
+  float* G;                  // [n][pool][pool] (workspace), or nullptr with lazy
+  int lazy;                  // != 0: no Gramian, its rows computed per step by the selection
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k]
+  float* out_mmr;            // [n][k], or nullptr
+};
+hipError_t launch_diversify_gram(const DiversifyArgs& a, hipStream_t s);
+hipError_t launch_diversify_select(const DiversifyArgs& a, hipStream_t s);
+
 // Scores of caller-supplied pairs and rankings of caller-supplied candidate
 // lists (rerank.hip).  Every score is the chain acc = fmaf(y[c], x[c], acc),
 // c ascending from +0 over the padded dim: recommend.hip's score of that row

@@ -2,10 +2,12 @@
 // (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
 // frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
 // frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions,
-// frecsys_explain, and the host-only frecsys_sample_negatives,
-// frecsys_list_metrics, frecsys_position_metrics, frecsys_metric_cvar.  No
+// frecsys_explain, frecsys_recommend_diverse, frecsys_diversify, and the
+// host-only frecsys_sample_negatives, frecsys_list_metrics,
+// frecsys_position_metrics, frecsys_metric_cvar, frecsys_mmr_select.  No
 // kernels here: recommend.hip, similar.hip, rerank.hip, sampled.hip,
-// metrics.hip, positions.hip and explain.hip hold them (kernels.h).
+// metrics.hip, positions.hip, explain.hip and diversify.hip hold them
+// (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -25,13 +27,18 @@
 //   sampled lists (sampled_metrics): rows by their fixed bytes within half the
 //     budget, then sub-batches whose ids fit the other half;
 //   explanations (explain): the same cut by the contributions, h floats per
-//     (row, target) pair.
+//     (row, target) pair;
+//   pools (diversify): budget / bytes per row (the pool, its Gramian, the
+//     selection), at least one row; recommend_diverse adds the selection to
+//     the scan's bytes per row and forms the Gramians in sub-batches of the
+//     batch, within a budget of their own.
 // Rows are independent, so the batch size never changes a result.
 //
 // Checks.  Each entry point keeps its own order of checks and its own point
 // of return for zero rows; the checkers below are its pieces.
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -447,18 +454,162 @@ struct MetricsStage {
   }
 };
 
+// What the MMR calls add to a ranking: the selection and where it goes (host).
+struct DiversifyRequest {
+  int32_t k;
+  float lam;
+  int32_t flags;
+  int32_t* items;
+  float* scores;
+  float* mmr;  // or nullptr
+};
+
+// The arguments every MMR call checks first: 1 <= k <= pool <= 1024, lam in
+// [0, 1] (a NaN fails both comparisons), the flags.
+int check_diversify(frecsys_ctx* c, const std::string& w, int32_t k, int32_t pool, float lam,
+                    int32_t flags, int32_t known_flags) {
+  if (pool < 1 || pool > kDiversifyMaxPool)
+    return fail(c, FRECSYS_ERR_INVALID, w + "pool must be in [1, 1024]");
+  if (k < 1 || k > pool) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, pool]");
+  if (!(lam >= 0.0f && lam <= 1.0f))
+    return fail(c, FRECSYS_ERR_INVALID, w + "lam must be in [0, 1]");
+  if (flags & ~known_flags) return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
+  return FRECSYS_OK;
+}
+
+// A pool array [n][pool] against a catalogue of m items: ids below m, finite
+// scores in the filled slots and, in normalised mode, a finite max - min per
+// row; "" when fine.
+std::string pool_error(const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
+                       int64_t m, bool raw) {
+  for (int64_t i = 0; i < n; ++i) {
+    float smax = -INFINITY, smin = INFINITY;
+    bool any = false;
+    for (int32_t b = 0; b < pool; ++b) {
+      const int32_t id = lists[i * pool + b];
+      if (id < 0) continue;
+      if (id >= m) return "item id " + std::to_string(id) + " out of range";
+      const float s = list_scores[i * pool + b];
+      if (!std::isfinite(s)) return "non-finite score in row " + std::to_string(i);
+      smax = std::fmax(smax, s);
+      smin = std::fmin(smin, s);
+      any = true;
+    }
+    if (any && !raw && !std::isfinite(smax - smin))
+      return "score range of row " + std::to_string(i) + " is not finite";
+  }
+  return "";
+}
+
+// The MMR selection behind pools of `pool` slots that are on the device:
+// div_gram_kernel writes the pool Gramians of a sub-batch of `gb` rows,
+// div_select_kernel reads them, and [cnt][k] outputs go to the host.  Per row
+// of a batch: the three output rows; per row of a sub-batch: the Gramian.  The
+// Gramians have a sub-batch of their own because they are 4 pool^2 bytes a
+// row -- 4 MiB at pool 1024, where they would cut the scan of
+// frecsys_recommend_diverse into batches of 59 rows, one 64-row block each.
+// FRECSYS_DIVERSIFY_VARIANT (read per call; changes no result bit): "gram"
+// forms the pool Gramians, "lazy" computes a Gramian row per step in the
+// selection and needs no Gramian workspace; unset: kDiversifyLazyDefault.
+constexpr bool kDiversifyLazyDefault = false;
+bool diversify_lazy() {
+  const char* v = getenv("FRECSYS_DIVERSIFY_VARIANT");
+  if (v && !strcmp(v, "lazy")) return true;
+  if (v && !strcmp(v, "gram")) return false;
+  return kDiversifyLazyDefault;
+}
+
+struct DiversifyStage {
+  const DiversifyRequest& rq;
+  const int64_t n;
+  int64_t gb = 1;
+  DiversifyArgs da{};
+
+  DiversifyStage(const frecsys_ctx* c, const DiversifyRequest& r, int64_t rows, int pool)
+      : rq(r), n(rows) {
+    da.Y = c->emb[1];
+    da.Dp = c->Dp;
+    da.pool = pool;
+    da.k = r.k;
+    da.lam = r.lam;
+    da.raw = (r.flags & FRECSYS_DIV_RAW_SCORES) != 0;
+    da.lazy = diversify_lazy();
+  }
+  static size_t out_bytes(int k) { return (size_t)k * 12; }
+  size_t gram_bytes() const { return da.lazy ? 0 : (size_t)da.pool * da.pool * 4; }
+  // nb rows of a batch, their Gramians in sub-batches within `budget` bytes
+  // (at least one row)
+  void carve_rows(Carver& cv, int64_t nb, size_t budget) {
+    gb = da.lazy ? nb
+                 : std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(budget / gram_bytes())));
+    da.G = cv.take_if<float>(!da.lazy, (size_t)gb * da.pool * da.pool);
+    da.out_items = cv.take<int32_t>((size_t)nb * da.k);
+    da.out_scores = cv.take<float>((size_t)nb * da.k);
+    da.out_mmr = cv.take_if<float>(rq.mmr != nullptr, (size_t)nb * da.k);
+  }
+  // rows [r0, r0 + cnt) of the call, their pools at ids / pool_scores; the
+  // outputs are on their way to the host when it returns (the caller
+  // synchronises)
+  int run(frecsys_ctx* c, const int32_t* ids, const float* pool_scores, int64_t r0, int64_t cnt) {
+    const size_t k = (size_t)da.k, P = (size_t)da.pool;
+    DiversifyArgs sub = da;
+    for (int64_t s0 = 0; s0 < cnt; s0 += gb) {  // two timed launches per sub-batch
+      sub.n = std::min(gb, cnt - s0);
+      sub.ids = ids + (size_t)s0 * P;
+      sub.pool_scores = pool_scores + (size_t)s0 * P;
+      sub.out_items = da.out_items + (size_t)s0 * k;
+      sub.out_scores = da.out_scores + (size_t)s0 * k;
+      sub.out_mmr = da.out_mmr ? da.out_mmr + (size_t)s0 * k : nullptr;
+      if (!da.lazy) {
+        ScopedTimer t(c, "diversify.gram");
+        HIP_TRY(c, launch_diversify_gram(sub, c->stream));
+        t.stop();
+      }
+      {
+        ScopedTimer t(c, "diversify.select");
+        HIP_TRY(c, launch_diversify_select(sub, c->stream));
+        t.stop();
+      }
+    }
+    HIP_TRY(c, to_host(c, rq.items + r0 * k, da.out_items, (size_t)cnt * k));
+    HIP_TRY(c, to_host(c, rq.scores + r0 * k, da.out_scores, (size_t)cnt * k));
+    if (rq.mmr) HIP_TRY(c, to_host(c, rq.mmr + r0 * k, da.out_mmr, (size_t)cnt * k));
+    return FRECSYS_OK;
+  }
+  // flops at the logical dim: the lower triangle of every pool Gramian, then
+  // per step and slot two multiplies and a maximum, a multiply and a
+  // subtraction; bytes: the pool's item rows gathered once, the Gramian
+  // written, k of its rows and the pool read by the selection, the outputs
+  void book(frecsys_ctx* c) const {
+    const double P = da.pool, k = da.k, d = c->dim;
+    if (da.lazy)  // the norms, then per step one row of products: the item rows read k + 1 times
+      add_work(c, "diversify", (double)n * (2.0 * (k + 1.0) * P * d + 5.0 * k * P),
+               (double)n * ((k + 1.0) * P * d * 4.0 + P * 8.0 + k * (rq.mmr ? 12.0 : 8.0)), n);
+    else
+      add_work(c, "diversify", (double)n * (P * (P + 1.0) * d + 5.0 * k * P),
+               (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 +
+                            k * (rq.mmr ? 12.0 : 8.0)),
+               n);
+  }
+};
+
 // The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
-// to the host) and frecsys_rank_metrics (mt given: every batch's lists stay on
-// the device and the metric rows go to the host).  The scan is the same launch
-// with the same workspace layout in both; the ground truth, the tables and the
-// metric outputs lie behind it.
+// to the host), frecsys_rank_metrics (mt given: every batch's lists stay on
+// the device and the metric rows go to the host) and frecsys_recommend_diverse
+// (dv given: k is the pool, every batch's lists and scores stay on the device
+// and the selection goes to the host).  The scan is the same launch with the
+// same workspace layout in all three; the ground truth, the tables and the
+// metric outputs, or the pool Gramians and the selection, lie behind it.
 int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
                    int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
-                   int32_t* items, float* scores, const MetricsRequest* mt) {
+                   int32_t* items, float* scores, const MetricsRequest* mt,
+                   const DiversifyRequest* dv = nullptr) {
   const std::string w = std::string(what) + ": ";
   int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
   if (rc) return rc;
-  if (n_rows < 0 || (n_rows > 0 && (mt ? (!mt->recall || !mt->ndcg) : !items)))
+  if (n_rows < 0 || (n_rows > 0 && (mt   ? (!mt->recall || !mt->ndcg)
+                                    : dv ? (!dv->items || !dv->scores)
+                                         : !items)))
     return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
   const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
   if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, exclude, rows, n_rows))) return rc;
@@ -472,9 +623,14 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
   HIP_TRY(c, hipSetDevice(c->device));
   const MetricsRequest none{};
   MetricsStage ms(mt ? *mt : none, n, k);
-  // per row of a batch beside the scan's own: history bits, the two metric rows
+  const DiversifyRequest no_dv{};
+  DiversifyStage ds(c, dv ? *dv : no_dv, n, k);
+  // per row of a batch beside the scan's own: history bits, the two metric
+  // rows, the pool Gramian and the selection
   const ScanPlan p =
-      scan_plan(c, k, m, n, (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8);
+      scan_plan(c, k, m, n,
+                (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8 +
+                    (dv ? DiversifyStage::out_bytes(dv->k) : 0));
   c->rec_splits = p.splits;
   RecommendArgs a = scan_args(c, side, FRECSYS_SIDE_ITEM, k, p.splits, exclude);
   rc = Carver::run(c, [&](Carver& cv) {
@@ -483,6 +639,9 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
       ms.carve_inputs(cv, (size_t)mt->gt_ptr[n]);  // room for every id; repeats are dropped
       ms.carve_rows(cv, p.nb);
     }
+    // outside the scan's per-row budget: the Gramians of a sub-batch, within a
+    // budget of their own
+    if (dv) ds.carve_rows(cv, p.nb, workspace_budget());
   });
   if (rc) return rc;
   const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
@@ -507,6 +666,9 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     if (mt) {
       if ((rc = ms.run(c, a.out_items, r0, a.n))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (dv) {
+      if ((rc = ds.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else if ((rc = fetch_lists(c, items, scores, k, r0, a.n, a.out_items, a.out_scores))) {
       return rc;
     }
@@ -516,6 +678,7 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
   add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
            ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
   if (mt) ms.book(c);
+  if (dv) ds.book(c);
   return FRECSYS_OK;
 }
 
@@ -786,6 +949,167 @@ int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int6
   const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
   return recommend_impl(c, "rank_metrics", side, rows, n_rows, k, flags, item_mask, nullptr, nullptr,
                         &mt);
+}
+
+int frecsys_recommend_diverse(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                              int32_t k, int32_t pool, float lam, int32_t flags,
+                              const uint8_t* item_mask, int32_t* items, float* scores,
+                              float* mmr) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend_diverse: null context");
+  const int rc = check_diversify(c, "recommend_diverse: ", k, pool, lam, flags,
+                                 FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  const DiversifyRequest dv{k, lam, flags, items, scores, mmr};
+  return recommend_impl(c, "recommend_diverse", side, rows, n_rows, pool,
+                        flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask, nullptr, nullptr, nullptr,
+                        &dv);
+}
+
+int frecsys_diversify(frecsys_ctx* c, const int32_t* lists, const float* list_scores, int64_t n,
+                      int32_t pool, int32_t k, float lam, int32_t flags, int32_t* items,
+                      float* scores, float* mmr) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "diversify: null context");
+  const std::string w = "diversify: ";
+  int rc = check_diversify(c, w, k, pool, lam, flags, FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n == 0) return FRECSYS_OK;
+  if (!lists || !list_scores || !items || !scores)
+    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
+  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
+  const std::string e = pool_error(lists, list_scores, n, pool, c->n[1], raw);
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const DiversifyRequest dv{k, lam, flags, items, scores, mmr};
+  DiversifyStage ds(c, dv, n, pool);
+  // per row of a batch: its pool (ids and scores), its Gramian and its
+  // outputs; at least one row per batch, and one Gramian sub-batch per batch
+  const size_t budget = workspace_budget();
+  const size_t per_row = (size_t)pool * 8 + ds.gram_bytes() + DiversifyStage::out_bytes(k);
+  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(budget / per_row)));
+  int32_t* d_ids = nullptr;
+  float* d_sc = nullptr;
+  rc = Carver::run(c, [&](Carver& cv) {
+    d_ids = cv.take<int32_t>((size_t)nb * pool);
+    d_sc = cv.take<float>((size_t)nb * pool);
+    ds.carve_rows(cv, nb, std::max(budget, (size_t)nb * ds.gram_bytes()));
+  });
+  if (rc) return rc;
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {
+    const int64_t cnt = std::min(nb, n - r0);
+    HIP_TRY(c, to_device(c, d_ids, lists + r0 * pool, (size_t)cnt * pool));
+    HIP_TRY(c, to_device(c, d_sc, list_scores + r0 * pool, (size_t)cnt * pool));
+    if ((rc = ds.run(c, d_ids, d_sc, r0, cnt))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  ds.book(c);
+  return FRECSYS_OK;
+}
+
+int frecsys_mmr_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
+                       int32_t k, float lam, int32_t flags, int32_t* items, float* scores,
+                       float* mmr) {
+#pragma clang fp contract(off)
+  const std::string w = "mmr_select: ";
+  int rc = check_diversify(nullptr, w, k, pool, lam, flags, FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n == 0) return FRECSYS_OK;
+  if (!item_table || n_items < 1 || dim < 1 || ld < dim)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, n_items < 1, ld < dim)");
+  if (!lists || !list_scores || !items || !scores)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "null pointer");
+  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
+  const std::string e = pool_error(lists, list_scores, n, pool, n_items, raw);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  const float oml = 1.0f - lam;
+  auto dot = [&](int32_t x, int32_t y) {
+    const float* px = item_table + (int64_t)x * ld;
+    const float* py = item_table + (int64_t)y * ld;
+    float acc = 0.0f;
+    for (int32_t cc = 0; cc < dim; ++cc) acc = std::fmaf(px[cc], py[cc], acc);
+    return acc;
+  };
+  auto work = [&](int64_t i0, int64_t i1) {
+    std::vector<float> base((size_t)pool), mm((size_t)pool), inv((size_t)pool);
+    std::vector<uint8_t> alive((size_t)pool);
+    for (int64_t i = i0; i < i1; ++i) {
+      const int32_t* ids = lists + i * pool;
+      const float* sc = list_scores + i * pool;
+      float smax = -INFINITY, smin = INFINITY;
+      int32_t p = 0;
+      for (int32_t b = 0; b < pool; ++b) {
+        alive[(size_t)b] = ids[b] >= 0;
+        if (!alive[(size_t)b]) continue;
+        ++p;
+        smax = std::fmax(smax, sc[b]);
+        smin = std::fmin(smin, sc[b]);
+        const float n2 = dot(ids[b], ids[b]);
+        inv[(size_t)b] = n2 > 0.0f ? 1.0f / std::sqrt(n2) : 0.0f;
+      }
+      const float range = smax - smin;
+      for (int32_t b = 0; b < pool; ++b) {
+        if (!alive[(size_t)b]) continue;
+        const float rel = raw ? sc[b] : (range > 0.0f ? (sc[b] - smin) / range : 0.0f);
+        base[(size_t)b] = lam * rel;
+        mm[(size_t)b] = -INFINITY;
+      }
+      const int32_t steps = std::min(p, k);
+      for (int32_t t = 0; t < steps; ++t) {
+        uint64_t best = 0;
+        for (int32_t b = 0; b < pool; ++b) {
+          if (!alive[(size_t)b]) continue;
+          float v;
+          if (t == 0) {
+            v = base[(size_t)b] + 0.0f;
+          } else {
+            const float pen = oml * mm[(size_t)b];
+            v = (base[(size_t)b] - pen) + 0.0f;
+          }
+          uint32_t u;
+          std::memcpy(&u, &v, 4);
+          const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // score_key
+          const uint64_t word = ((uint64_t)key << 32) | (0xFFFFFFFFu - (uint32_t)b);
+          if (word > best) best = word;
+        }
+        const int32_t s = (int32_t)(0xFFFFFFFFu - (uint32_t)best);
+        const uint32_t key = (uint32_t)(best >> 32);
+        const uint32_t u = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;  // score_unkey
+        items[i * k + t] = ids[s];
+        scores[i * k + t] = sc[s];
+        if (mmr) std::memcpy(&mmr[i * k + t], &u, 4);
+        alive[(size_t)s] = 0;
+        if (t + 1 == steps) break;
+        for (int32_t b = 0; b < pool; ++b) {
+          if (!alive[(size_t)b]) continue;
+          const float g = dot(ids[s], ids[b]);
+          const float gs = g * inv[(size_t)s];
+          const float cs = gs * inv[(size_t)b] + 0.0f;
+          mm[(size_t)b] = std::fmax(mm[(size_t)b], cs);
+        }
+      }
+      for (int32_t t = steps; t < k; ++t) {
+        items[i * k + t] = -1;
+        scores[i * k + t] = -FLT_MAX;
+        if (mmr) mmr[i * k + t] = -FLT_MAX;
+      }
+    }
+  };
+  // rows are independent: host threads over row ranges when there is enough work
+  const double cost = (double)n * pool * (double)k * dim;
+  const int nt = cost < 1e8 ? 1
+                            : (int)std::min<int64_t>(
+                                  n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+  if (nt <= 1) {
+    work(0, n);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
+    for (auto& t : th) t.join();
+  }
+  return FRECSYS_OK;
 }
 
 int frecsys_score_pairs(frecsys_ctx* c, int32_t side, const int64_t* rows, const int32_t* items,

@@ -20,6 +20,7 @@ import numpy as np
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
 REC_EXCLUDE_HISTORY = 1
 SIM_COSINE, SIM_KEEP_SELF = 1, 2
+DIV_RAW_SCORES = 2
 # the cut-offs and tail levels run_model evaluates (run_model.cc:97-100)
 EVAL_K_LIST = (5, 10, 20, 50, 100)
 EVAL_ALPHA_LIST = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
@@ -54,7 +55,8 @@ EXPORTS = (
     "frecsys_rank_metrics", "frecsys_score_pairs", "frecsys_rank_candidates",
     "frecsys_similar", "frecsys_sample_negatives", "frecsys_rank_candidates_metrics",
     "frecsys_sampled_metrics", "frecsys_position_metrics", "frecsys_rank_positions",
-    "frecsys_explain", "frecsys_csr_row_lengths",
+    "frecsys_explain", "frecsys_csr_row_lengths", "frecsys_mmr_select", "frecsys_diversify",
+    "frecsys_recommend_diverse",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -72,6 +74,8 @@ MODEL_EXPORTS = (
     "frecsys_model_evaluate_ranks", "frecsys_model_evaluate_ranks_fold_in",
     "frecsys_model_save", "frecsys_model_load", "frecsys_model_file_info",
     "frecsys_model_epochs", "frecsys_model_explain", "frecsys_model_explain_fold_in",
+    "frecsys_model_recommend_diverse", "frecsys_model_recommend_diverse_fold_in",
+    "frecsys_model_diversify",
 )
 
 
@@ -215,6 +219,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_rank_positions": (ctypes.c_int, [P, I32, P, I64, I32, P, P, P, P, P, P, P]),
         "frecsys_explain": (ctypes.c_int, [P, I32, P, P, I64, P, P, I32, P, P, P, P]),
         "frecsys_csr_row_lengths": (ctypes.c_int, [P, I32, P, I64, P]),
+        "frecsys_mmr_select": (ctypes.c_int,
+                               [P, I64, I32, I64, P, P, I64, I32, I32, F, I32, P, P, P]),
+        "frecsys_diversify": (ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, P, P, P]),
+        "frecsys_recommend_diverse": (ctypes.c_int,
+                                      [P, I32, P, I64, I32, I32, F, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -233,7 +242,7 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise FrecsysError(ERR_INVALID, f"{path} missing: run __graft_entry__.build() / make")
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    P, I32, I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    P, I32, I64, F = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     sig = {
         "frecsys_model_config_default": (None, [P]),
         "frecsys_model_create": (ctypes.c_int, [P, P, P, I64, P]),
@@ -277,6 +286,11 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_explain": (ctypes.c_int, [P, P, I64, P, P, I32, P, P, P, P]),
         "frecsys_model_explain_fold_in": (ctypes.c_int,
                                           [P, P, P, I64, P, P, I32, P, P, P, P]),
+        "frecsys_model_recommend_diverse": (ctypes.c_int,
+                                            [P, P, I64, I32, I32, F, I32, I32, P, P, P, P]),
+        "frecsys_model_recommend_diverse_fold_in": (
+            ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, I32, P, P, P, P]),
+        "frecsys_model_diversify": (ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -356,6 +370,48 @@ def list_metrics(lists, gt_ptr, gt_items, k_list) -> Tuple[np.ndarray, np.ndarra
     if rc:
         raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
     return rec, ndcg
+
+
+def default_pool(k: int) -> int:
+    """The pool the diversified calls draw k items from when none is given."""
+    return min(1024, max(k, 4 * k))
+
+
+def _pools(lists, scores):
+    ls = np.ascontiguousarray(lists, dtype=np.int32)
+    sc = np.ascontiguousarray(scores, dtype=np.float32)
+    assert ls.ndim == 2 and ls.shape == sc.shape, (ls.shape, sc.shape)
+    return ls, sc
+
+
+def _diverse_out(n: int, k: int, return_mmr: bool):
+    items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+    scores = np.zeros(items.shape, dtype=np.float32)
+    return items, scores, (np.zeros(items.shape, dtype=np.float32) if return_mmr else None)
+
+
+def mmr_select(item_table, lists, scores, k: int, lam: float = 0.7, raw_scores: bool = False,
+               return_mmr: bool = False):
+    """(items int32 [n, k], scores float32 [n, k][, mmr float32 [n, k]]): greedy
+    maximal-marginal-relevance selection of k slots from each row's pool
+    (lists int32 [n, pool], negative = empty slot; scores float32 [n, pool])
+    against item_table float32 [n_items, dim], on the host
+    (frecsys_mmr_select: the definition Context.diversify and
+    Context.recommend_diverse return bit for bit; no GPU needed)."""
+    lib = load_library()
+    tab = np.asarray(item_table, dtype=np.float32)
+    assert tab.ndim == 2, tab.shape
+    if tab.strides[1] != 4 or tab.strides[0] % 4 or tab.strides[0] < 4 * tab.shape[1]:
+        tab = np.ascontiguousarray(tab)
+    ls, sc = _pools(lists, scores)
+    items, out, mmr = _diverse_out(ls.shape[0], k, return_mmr)
+    rc = lib.frecsys_mmr_select(_ptr(tab), tab.shape[0], tab.shape[1], tab.strides[0] // 4,
+                                _ptr(ls), _ptr(sc), ls.shape[0], ls.shape[1], k, lam,
+                                DIV_RAW_SCORES if raw_scores else 0, _ptr(items), _ptr(out),
+                                _ptr(mmr))
+    if rc:
+        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    return (items, out, mmr) if return_mmr else (items, out)
 
 
 def sample_negatives(n_items: int, gt_ptr, gt_items, n_neg: int, seed: int = 0, rows=None,
@@ -706,6 +762,42 @@ class Context:
                                                REC_EXCLUDE_HISTORY if exclude_history else 0,
                                                _ptr(mk), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def recommend_diverse(self, side: int, k: int, pool: Optional[int] = None, lam: float = 0.7,
+                          rows=None, raw_scores: bool = False, exclude_history: bool = True,
+                          item_mask=None, return_mmr: bool = False):
+        """(items int32 [n, k], scores float32 [n, k][, mmr float32 [n, k]]):
+        mmr_select of recommend(side, pool, ...)'s lists against the item
+        table, bit for bit, with the pools never leaving the GPU
+        (frecsys_recommend_diverse).  pool defaults to default_pool(k); lam = 1
+        returns recommend(side, k, ...)."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        items, scores, mmr = _diverse_out(n, k, return_mmr)
+        flags = (REC_EXCLUDE_HISTORY if exclude_history else 0) | \
+            (DIV_RAW_SCORES if raw_scores else 0)
+        self._check(self.lib.frecsys_recommend_diverse(
+            self.h, side, _ptr(r), n, k, default_pool(k) if pool is None else pool, lam, flags,
+            _ptr(mk), _ptr(items), _ptr(scores), _ptr(mmr)))
+        return (items, scores, mmr) if return_mmr else (items, scores)
+
+    def diversify(self, lists, scores, k: int, lam: float = 0.7, raw_scores: bool = False,
+                  return_mmr: bool = False):
+        """The same selection from caller-supplied pools (lists int32 [n,
+        pool], negative = empty slot; scores float32 [n, pool]) against the
+        context's item table, on the GPU (frecsys_diversify): mmr_select's
+        result bit for bit."""
+        ls, sc = _pools(lists, scores)
+        items, out, mmr = _diverse_out(ls.shape[0], k, return_mmr)
+        self._check(self.lib.frecsys_diversify(self.h, _ptr(ls), _ptr(sc), ls.shape[0],
+                                               ls.shape[1], k, lam,
+                                               DIV_RAW_SCORES if raw_scores else 0, _ptr(items),
+                                               _ptr(out), _ptr(mmr)))
+        return (items, out, mmr) if return_mmr else (items, out)
 
     def rank_metrics(self, side: int, k_list, gt_ptr, gt_items, rows=None,
                      exclude_history: bool = True,
@@ -1190,6 +1282,58 @@ class Model:
         if rc:
             raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
         return items, scores
+
+    def recommend_diverse(self, users, k: int, pool: Optional[int] = None, lam: float = 0.7,
+                          raw_scores: bool = False, exclude_history: bool = True, item_mask=None,
+                          return_mmr: bool = False):
+        """(items int32 [n, k], scores float32 [n, k][, mmr float32 [n, k]]) for
+        trained users (frecsys_model_recommend_diverse): greedy MMR re-ranking
+        of recommend(users, pool)'s lists down to k against the item table --
+        mmr_select's result bit for bit, computed on the GPU.  pool defaults to
+        min(1024, max(k, 4 k)); lam = 1 returns recommend(users, k)."""
+        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+        mk = self._mask(item_mask)
+        items, scores, mmr = _diverse_out(len(u), k, return_mmr)
+        rc = self.lib.frecsys_model_recommend_diverse(
+            self.h, _ptr(u), len(u), k, default_pool(k) if pool is None else pool, lam,
+            int(bool(raw_scores)), int(bool(exclude_history)), _ptr(mk), _ptr(items),
+            _ptr(scores), _ptr(mmr))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return (items, scores, mmr) if return_mmr else (items, scores)
+
+    def recommend_diverse_fold_in(self, hist_ptr, hist_items, k: int, pool: Optional[int] = None,
+                                  lam: float = 0.7, raw_scores: bool = False,
+                                  exclude_history: bool = True, item_mask=None,
+                                  return_mmr: bool = False):
+        """The same for unseen users given by their histories (CSR), as
+        recommend_fold_in (frecsys_model_recommend_diverse_fold_in)."""
+        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
+        n = len(hp) - 1
+        mk = self._mask(item_mask)
+        items, scores, mmr = _diverse_out(n, k, return_mmr)
+        rc = self.lib.frecsys_model_recommend_diverse_fold_in(
+            self.h, _ptr(hp), _ptr(hi), n, k, default_pool(k) if pool is None else pool, lam,
+            int(bool(raw_scores)), int(bool(exclude_history)), _ptr(mk), _ptr(items),
+            _ptr(scores), _ptr(mmr))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return (items, scores, mmr) if return_mmr else (items, scores)
+
+    def diversify(self, lists, scores, k: int, lam: float = 0.7, raw_scores: bool = False,
+                  return_mmr: bool = False):
+        """The same selection from caller-supplied pools (lists int32 [n,
+        pool], negative = empty slot; scores float32 [n, pool]) against the
+        model's item table (frecsys_model_diversify)."""
+        ls, sc = _pools(lists, scores)
+        items, out, mmr = _diverse_out(ls.shape[0], k, return_mmr)
+        rc = self.lib.frecsys_model_diversify(self.h, _ptr(ls), _ptr(sc), ls.shape[0],
+                                              ls.shape[1], k, lam, int(bool(raw_scores)),
+                                              _ptr(items), _ptr(out), _ptr(mmr))
+        if rc:
+            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        return (items, out, mmr) if return_mmr else (items, out)
 
     def _explain_out(self, tp, top):
         pairs = int(tp[-1])

@@ -108,6 +108,25 @@ class DeviceModel : public Recommender {
                            exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
   }
 
+  // Diversified lists (frecsys_recommend_diverse): the greedy MMR selection of
+  // k from the `pool` best items of each row of `side` (USER: trained users;
+  // EVAL: the rows a FoldIn left there), against the model's item table.
+  // flags: FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES; outputs: host
+  // [n * k] (mmr may be nullptr).  The status code, for callers that report
+  // errors.
+  int RecommendDiverse(int side, const int64_t* rows, int64_t n, int k, int pool, float lam,
+                       int flags, const uint8_t* mask, int32_t* items, float* scores, float* mmr) {
+    return frecsys_recommend_diverse(dev_->raw(), side, rows, n, k, pool, lam, flags, mask, items,
+                                     scores, mmr);
+  }
+  // The same selection from caller-supplied pools, lists / list_scores: host
+  // [n * pool] (frecsys_diversify).
+  int Diversify(const int32_t* lists, const float* list_scores, int64_t n, int pool, int k,
+                float lam, int flags, int32_t* items, float* scores, float* mmr) {
+    return frecsys_diversify(dev_->raw(), lists, list_scores, n, pool, k, lam, flags, items, scores,
+                             mmr);
+  }
+
   // The solve parameters of the model's own fold-in projection -- the ones
   // its FoldIn passes, omega = 1 where the fold-in uses it.  iALS++ and
   // SAFER2++ give the parameters of the objective their block steps descend:

@@ -902,6 +902,78 @@ int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                        k_list, nk, alpha_list, na, recall, ndcg, summary);
 }
 
+// The cases the MMR calls reject (frecsys_hip.h), for the fold-in call to
+// report before it projects anything; "" when fine.
+static std::string diverse_args_error(int32_t k, int32_t pool, float lam, int32_t raw_scores,
+                                      int64_t n, const int32_t* items, const float* scores) {
+  if (pool < 1 || pool > 1024) return "pool must be in [1, 1024]";
+  if (k < 1 || k > pool) return "k must be in [1, pool]";
+  if (!(lam >= 0.0f && lam <= 1.0f)) return "lam must be in [0, 1]";
+  if (raw_scores != 0 && raw_scores != 1) return "raw_scores must be 0 or 1";
+  if (n > 0 && (!items || !scores)) return "null outputs";
+  return "";
+}
+
+static int32_t diverse_flags(int32_t exclude_seen, int32_t raw_scores) {
+  return (exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0) |
+         (raw_scores ? FRECSYS_DIV_RAW_SCORES : 0);
+}
+
+int frecsys_model_recommend_diverse(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                    int32_t pool, float lam, int32_t raw_scores,
+                                    int32_t exclude_seen, const uint8_t* item_mask,
+                                    int32_t* items, float* scores, float* mmr) {
+  const std::string w = "frecsys_model_recommend_diverse: ";
+  if (!m || n < 0 || (n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  const std::string e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (exclude_seen)
+    if (int rc = needs_data(m, "frecsys_model_recommend_diverse")) return rc;
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int rc = dm->RecommendDiverse(FRECSYS_SIDE_USER, users, n, k, pool, lam,
+                                      diverse_flags(exclude_seen, raw_scores), item_mask, items,
+                                      scores, mmr);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                            const int32_t* hist_items, int64_t n, int32_t k,
+                                            int32_t pool, float lam, int32_t raw_scores,
+                                            int32_t exclude_seen, const uint8_t* item_mask,
+                                            int32_t* items, float* scores, float* mmr) {
+  const std::string w = "frecsys_model_recommend_diverse_fold_in: ";
+  if (!m) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  // checked here: the C++ layer treats a bad EVAL CSR as fatal
+  std::string e = hist_args_error(n, dm->device().rows(frecsys::DeviceContext::ITEM), hist_ptr,
+                                  hist_items);
+  if (e.empty()) e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (n == 0) return FRECSYS_OK;
+  frecsys::Csr csr;
+  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
+  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
+  dm->FoldIn(csr);
+  const int rc = dm->RecommendDiverse(FRECSYS_SIDE_EVAL, nullptr, n, k, pool, lam,
+                                      diverse_flags(exclude_seen, raw_scores), item_mask, items,
+                                      scores, mmr);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
+int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float* list_scores,
+                            int64_t n, int32_t pool, int32_t k, float lam, int32_t raw_scores,
+                            int32_t* items, float* scores, float* mmr) {
+  const std::string w = "frecsys_model_diversify: ";
+  if (!m || n < 0 || (n > 0 && (!lists || !list_scores)))
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  const std::string e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  const int rc = dm->Diversify(lists, list_scores, n, pool, k, lam, diverse_flags(0, raw_scores),
+                               items, scores, mmr);
+  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+}
+
 void frecsys_model_destroy(frecsys_model* m) { delete m; }
 
 const char* frecsys_model_last_error(void) { return g_model_error.c_str(); }
