@@ -749,6 +749,7 @@ int frecsys_ctx_create(const frecsys_config* cfg, frecsys_ctx** out) {
   c->dual_max_h = Dp <= 256 ? 224 : Dp == 1024 ? 512 : 256;
   if (const char* v = getenv("FRECSYS_DUAL_MAX_H")) c->dual_max_h = atoi(v);
   if (const char* v = getenv("FRECSYS_DUAL_SERIAL")) c->dual_serial = atoi(v);
+  if (const char* v = getenv("FRECSYS_CHOL_SCHED")) c->chol_sched = atoi(v) != 0;
   if (const char* v = getenv("FRECSYS_SPLIT_ROWS")) c->split_rows = atoi(v);
   if (const char* v = getenv("FRECSYS_DEBUG_SKIP")) {
 #ifdef FRECSYS_ABLATION

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "common.h"
+#include "chol_sched.h"
 
 // With 8 waves: the wave that runs the forward substitution (Y, B of the
 // chain's next block).  Waves w and w + 4 share a SIMD, so 4 leaves the
@@ -503,8 +504,14 @@ __device__ __forceinline__ void chol_solve_tiles(float* tiles, float* bvec, floa
 // U tasks of each panel round-robin, next-column tiles first.  Every wave
 // walks its tasks in one global order (panel by panel: chain, S+B, U by
 // column) in which each task's dependencies come earlier, so the waits
-// cannot deadlock.  The backward sweep x = L^-T y runs the same way after
-// one barrier: wave 0 publishes x_q = L_qq^-T (r_q - L_{q+1,q}^T x_{q+1}),
+// cannot deadlock.  Where chol_sched.h has a table for (T, NW), each worker
+// walks a list of its own instead (the model's list schedule, which has the
+// tiles the chain needs next ready sooner; `sched` off: the round-robin
+// dealing as lists): same tasks, waits and arithmetic, and the waits still
+// cannot deadlock because the data edges plus every wave's sequence are
+// acyclic (tests/test_chol_sched_cpu.py).
+// The backward sweep x = L^-T y runs the same way after one barrier:
+// wave 0 publishes x_q = L_qq^-T (r_q - L_{q+1,q}^T x_{q+1}),
 // the workers fold x_q into r_p (p <= q - 2, each r_p owned by one worker,
 // rcnt(p) = x blocks folded in).
 // debug_skip masks (ablation only): 2 diag, 4 TRSM, 8 trailing.
@@ -561,7 +568,7 @@ __device__ __forceinline__ float tile_gemv(const float* M, const float* v, int l
 template <int T, int NW, bool BLK = true>
 __device__ __forceinline__ void chol_solve_df(float* tiles, float* bvec, float* xvec,
                                               float* part, int* flag, int tid, int debug_skip,
-                                              unsigned long long* prof = nullptr) {
+                                              bool sched, unsigned long long* prof = nullptr) {
   static_assert(NW >= 2, "one chain wave and at least one worker");
   constexpr int NT = T * (T + 1) / 2;
   // split-bf16 tile products (common.h mfma_x6, fp32-accurate) where the
@@ -708,8 +715,7 @@ __device__ __forceinline__ void chol_solve_df(float* tiles, float* bvec, float* 
       }
     }
   } else {
-    // ---- workers: the rest of each panel, round-robin ----
-    int k = 0;
+    // ---- workers: the rest of each panel ----
     unsigned long long tww = 0;  // diagnostics (prof): cycles in waits
     auto wwait = [&](const int* f, int v) {
       if (prof) {
@@ -724,28 +730,56 @@ __device__ __forceinline__ void chol_solve_df(float* tiles, float* bvec, float* 
       if (c) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
     };
+    auto strsm = [&](int I, int p) {  // S(I, p), B(I, p)
+      wwait(ver + tidx(p, p), p + 1);
+      wwait(ver + tidx(I, p), p);
+      wprio(I <= p + 1 + kCholWPrio);
+      trsm(I, p);
+      wwait(yver, p + 1);
+      bupd(I, p);
+    };
+    auto supd = [&](int I, int J, int p) {  // U(I, J, p)
+      wwait(ver + tidx(I, p), p + 1);
+      wwait(ver + tidx(J, p), p + 1);
+      wwait(ver + tidx(I, J), p);
+      wprio(I <= p + 1 + kCholWPrio);
+      update(I, J, p);
+    };
+    using Sched = CholSched<T, NW>;
+    if constexpr (Sched::kHas) {
+      // a static schedule (chol_sched.h): the slot walks its own task list,
+      // the model's list schedule or (sched off) the round-robin dealing
+      // below as a list -- one task loop for both
+      static_assert(Sched::kSlots == NWK, "a table of another wave layout");
+      const int slot = YW ? wave - 1 - (wave > YWAVE ? 1 : 0) : wave - 1;
+      const unsigned short* list = sched ? Sched::kTask[slot] : Sched::kRrTask[slot];
+      const int n = sched ? Sched::kLen[slot] : Sched::kRrLen[slot];
+      unsigned nxt = list[0];
 #pragma unroll 1
-    for (int p = 0; p + 1 < T; ++p) {
-#pragma unroll 1
-      for (int I = p + 2; I < T; ++I, ++k) {  // S(I, p), B(I, p)
-        if (wk_wave(k % NWK) != wave) continue;
-        wwait(ver + tidx(p, p), p + 1);
-        wwait(ver + tidx(I, p), p);
-        wprio(I <= p + 1 + kCholWPrio);
-        trsm(I, p);
-        wwait(yver, p + 1);
-        bupd(I, p);
+      for (int i = 0; i < n; ++i) {
+        const unsigned e = nxt;
+        nxt = list[i + 1];  // the next entry's load runs under this task
+        const int I = (e >> 8) & 15, J = (e >> 4) & 15, p = e & 15;
+        if (e >> 12) supd(I, J, p);
+        else strsm(I, p);
       }
+    } else {
+      // round-robin, next-column tiles first
+      int k = 0;
 #pragma unroll 1
-      for (int J = p + 1; J < T; ++J) {  // U(I, J, p), column by column
+      for (int p = 0; p + 1 < T; ++p) {
 #pragma unroll 1
-        for (int I = (J == p + 1 ? p + 2 : J); I < T; ++I, ++k) {
+        for (int I = p + 2; I < T; ++I, ++k) {
           if (wk_wave(k % NWK) != wave) continue;
-          wwait(ver + tidx(I, p), p + 1);
-          wwait(ver + tidx(J, p), p + 1);
-          wwait(ver + tidx(I, J), p);
-          wprio(I <= p + 1 + kCholWPrio);
-          update(I, J, p);
+          strsm(I, p);
+        }
+#pragma unroll 1
+        for (int J = p + 1; J < T; ++J) {  // column by column
+#pragma unroll 1
+          for (int I = (J == p + 1 ? p + 2 : J); I < T; ++I, ++k) {
+            if (wk_wave(k % NWK) != wave) continue;
+            supd(I, J, p);
+          }
         }
       }
     }

@@ -225,6 +225,7 @@ struct frecsys_ctx {
   int dual_max_h_side[3] = {256, 256, 256};  // per solved side (FRECSYS_DUAL_MAX_H_USER / _ITEM)
   int dual_serial = 0;  // FRECSYS_DUAL_SERIAL=1: no stream overlap (profiling)
   int debug_skip = 0;   // FRECSYS_DEBUG_SKIP ablation mask (-DFRECSYS_ABLATION builds only)
+  int chol_sched = 1;   // FRECSYS_CHOL_SCHED=0: the round-robin worker order (profiling)
   // per-kernel event pairs, resolved after the call's final synchronisation
   struct Pending {
     std::string name;

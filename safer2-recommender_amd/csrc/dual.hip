@@ -474,7 +474,7 @@ __global__ void __launch_bounds__((DualCfg<TH, BF>::NTHR))
   // occupancy without spills; TH = 3 at 128 registers spills 8, measured
   // faster all the same)
   chol_solve_df<TH, NW, (TH >= kDualBlkTH)>(tiles, bvec, xvec, part, flag, tid, a.debug_skip,
-                                            a.prof);
+                                            a.chol_sched != 0, a.prof);
   mark(2);
 
   // ---- v = Y^T (c.*z): the rows again, float4 per lane, 8 rows in flight ----

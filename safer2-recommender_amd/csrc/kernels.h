@@ -48,6 +48,7 @@ struct SolveArgs {
   const float* other_weight;   // [rows of other side] nu
   unsigned long long* fail;    // atomicMin(entity + 1) on a non-SPD pivot
   int debug_skip;              // diagnostic ablation mask (0 in production)
+  int chol_sched;              // the dataflow Cholesky's static worker schedule (chol_sched.h): 1 on
   unsigned long long* prof;    // diagnostics: per-phase cycle sums [16] (nullptr = off)
   // long-history split (tiled and wide kernels; nullptr / 0 = none)
   const int2* split;           // [n_split] per queue position: first slab, slab count
@@ -154,6 +155,7 @@ struct DualArgs {
   const float* other_weight;
   unsigned long long* fail;
   int debug_skip;  // ablation only: 1 SYRK, 2/4/8/16 Cholesky parts, 64 Y^T z, 128 recurrence
+  int chol_sched;  // the dataflow Cholesky's static worker schedule (chol_sched.h): 1 on
   unsigned long long* prof;  // diagnostics: per-phase cycle sums [16] (nullptr = off)
 };
 

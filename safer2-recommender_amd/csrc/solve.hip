@@ -721,7 +721,8 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
   }
 
   // ---- blocked right-looking Cholesky with lookahead + back-solve ----
-  chol_solve_df<T, NW>(tiles, bvec, xvec, part, flag, tid, a.debug_skip, a.prof);
+  chol_solve_df<T, NW>(tiles, bvec, xvec, part, flag, tid, a.debug_skip, a.chol_sched != 0,
+                       a.prof);
   mark(3);
   if (tid < Dp) a.out[e * Dp + tid] = xvec[tid];
   if (tid == 0 && flag[0]) atomicMin(a.fail, (unsigned long long)(e + 1));

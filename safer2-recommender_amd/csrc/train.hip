@@ -361,6 +361,7 @@ SolveArgs solve_args(frecsys_ctx* c, int side, const frecsys_solve_params* p) {
   a.other_weight = is_vkind(p->kind) ? c->d_other_weight.dev.get() : nullptr;
   a.fail = c->d_fail;
   a.debug_skip = c->debug_skip;
+  a.chol_sched = c->chol_sched;
   return a;
 }
 
@@ -438,6 +439,7 @@ DualArgs dual_args(const frecsys_ctx* c, int side, const SolveArgs& a, const Sid
   d.other_weight = a.other_weight;
   d.fail = a.fail;
   d.debug_skip = a.debug_skip;
+  d.chol_sched = a.chol_sched;
   return d;
 }
 
@@ -589,6 +591,13 @@ int print_dual_prof(frecsys_ctx* c, int side) {
             (double)hp[16 * t] / n, (double)hp[16 * t + 1] / n, (double)hp[16 * t + 2] / n,
             (double)hp[16 * t + 3] / n, (double)hp[16 * t + 5] / n, (double)hp[16 * t + 6] / n,
             (double)hp[16 * t + 7] / n);
+    // chol_solve_df's own counters (the workgroup buckets; the wave-per-entity
+    // kernel of TH <= 2 has no chain)
+    if (hp[16 * t + 14])
+      fprintf(stderr, "[dual-prof] side %d tiles %d chain: waits %.0f trsm %.0f update %.0f factor %.0f "
+              "| worker waits %.0f\n", side, t, (double)hp[16 * t + 11] / n,
+              (double)hp[16 * t + 12] / n, (double)hp[16 * t + 13] / n, (double)hp[16 * t + 14] / n,
+              (double)hp[16 * t + 15] / n);
   }
   return FRECSYS_OK;
 }
