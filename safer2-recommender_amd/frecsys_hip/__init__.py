@@ -304,6 +304,14 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _check_host(lib, rc: int, model: bool = False):
+    """Raise the error of a call that has no context: the library's message
+    (frecsys_last_error(NULL), or frecsys_model_last_error for the model ABI)."""
+    if rc:
+        msg = lib.frecsys_model_last_error() if model else lib.frecsys_last_error(None)
+        raise FrecsysError(rc, msg.decode())
+
+
 def _explain_full(lengths: np.ndarray, tgt_ptr: np.ndarray):
     """The buffer of explain's `full` and its pair pointer: pair p of row i
     holds lengths[i] contributions."""
@@ -329,8 +337,7 @@ def partition(row_ptr: np.ndarray, nparts: int) -> np.ndarray:
     rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
     out = np.zeros(nparts + 1, dtype=np.int64)
     rc = lib.frecsys_partition(len(rp) - 1, _ptr(rp), nparts, _ptr(out))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return out
 
 
@@ -342,8 +349,7 @@ def gram_plan(dim: int, n_rows: int, world: int = 1, rank: int = 0):
     ng, lo, hi = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     rc = lib.frecsys_gram_plan(dim, n_rows, world, rank, ctypes.byref(rpl), ctypes.byref(nl),
                                ctypes.byref(ng), ctypes.byref(lo), ctypes.byref(hi))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return int(rpl.value), int(nl.value), int(ng.value), int(lo.value), int(hi.value)
 
 
@@ -367,8 +373,7 @@ def list_metrics(lists, gt_ptr, gt_items, k_list) -> Tuple[np.ndarray, np.ndarra
     ndcg = np.zeros_like(rec)
     rc = lib.frecsys_list_metrics(_ptr(ls), ls.shape[0], ls.shape[1], _ptr(gp), _ptr(gi),
                                   _ptr(ks), len(ks), _ptr(rec), _ptr(ndcg))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return rec, ndcg
 
 
@@ -409,8 +414,7 @@ def mmr_select(item_table, lists, scores, k: int, lam: float = 0.7, raw_scores: 
                                 _ptr(ls), _ptr(sc), ls.shape[0], ls.shape[1], k, lam,
                                 DIV_RAW_SCORES if raw_scores else 0, _ptr(items), _ptr(out),
                                 _ptr(mmr))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return (items, out, mmr) if return_mmr else (items, out)
 
 
@@ -443,8 +447,7 @@ def sample_negatives(n_items: int, gt_ptr, gt_items, n_neg: int, seed: int = 0, 
     rc = lib.frecsys_sample_negatives(n_items, _ptr(mk), _ptr(r), n, _ptr(hp), _ptr(hi), _ptr(gp),
                                       _ptr(gi), n_neg, seed & 0xFFFFFFFFFFFFFFFF, _ptr(cnt),
                                       _ptr(neg))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return cnt, neg
 
 
@@ -463,8 +466,7 @@ def position_metrics(rank, gt_ptr, eligible) -> Tuple[np.ndarray, np.ndarray]:
     mrr = np.zeros(n, dtype=np.float32)
     auc = np.zeros(n, dtype=np.float32)
     rc = lib.frecsys_position_metrics(_ptr(rk), _ptr(gp), _ptr(el), n, _ptr(mrr), _ptr(auc))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return mrr, auc
 
 
@@ -477,8 +479,7 @@ def metric_cvar(values, alphas) -> np.ndarray:
     a = np.ascontiguousarray(alphas, dtype=np.float32).reshape(-1)
     out = np.zeros(len(a), dtype=np.float32)
     rc = lib.frecsys_metric_cvar(_ptr(v), len(v), _ptr(a), len(a), _ptr(out))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return out
 
 
@@ -496,8 +497,7 @@ def model_file_info(path: str, verify: bool = True) -> dict:
     lib = load_model_library()
     info = _ModelFileInfo()
     rc = lib.frecsys_model_file_info(os.fsencode(path), int(bool(verify)), ctypes.byref(info))
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_model_last_error().decode())
+    _check_host(lib, rc, model=True)
     return {"model_name": info.model_name.decode(), "n_users": info.n_users,
             "n_items": info.n_items, "n_tuples": info.n_tuples,
             "epochs_trained": info.epochs_trained, "flags": info.flags,
@@ -510,8 +510,7 @@ def unique_id() -> bytes:
     lib = load_library()
     buf = (ctypes.c_uint8 * 128)()
     rc = lib.frecsys_comm_unique_id(buf)
-    if rc:
-        raise FrecsysError(rc, lib.frecsys_last_error(None).decode())
+    _check_host(lib, rc)
     return bytes(buf)
 
 
@@ -530,8 +529,7 @@ class Context:
         cfg = _Config(dim, device, 1 if parity_quirks else 0, 0, n_users, n_items)
         h = ctypes.c_void_p()
         rc = self.lib.frecsys_ctx_create(ctypes.byref(cfg), ctypes.byref(h))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_last_error(None).decode())
+        _check_host(self.lib, rc)
         self.h = h
         self.dim = dim
         self.n = {SIDE_USER: n_users, SIDE_ITEM: n_items, SIDE_EVAL: 0}
@@ -1131,14 +1129,15 @@ class Model:
         it = np.ascontiguousarray(items, dtype=np.int32)
         assert u.shape == it.shape
         h = ctypes.c_void_p()
-        rc = self.lib.frecsys_model_create(ctypes.byref(cfg), _ptr(u), _ptr(it), len(u),
-                                           ctypes.byref(h))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_create(ctypes.byref(cfg), _ptr(u), _ptr(it), len(u),
+                                                  ctypes.byref(h)))
         self.h = h
         self.dim = cfg.dim
         self.n_users = int(u.max()) + 1
         self.n_items = int(it.max()) + 1
+
+    def _check(self, rc: int):
+        _check_host(self.lib, rc, model=True)
 
     def _apply_flags(self, cfg, flags):
         for k, v in flags.items():
@@ -1155,10 +1154,8 @@ class Model:
         """Write the model to `path` (frecsys_model_save): tables, dual state,
         everything an exact resume needs and, with include_data, the training
         tuples.  Atomic: an existing file is replaced only by a complete one."""
-        rc = self.lib.frecsys_model_save(self.h, os.fsencode(path),
-                                         0 if include_data else SAVE_NO_DATA)
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_save(self.h, os.fsencode(path),
+                                                0 if include_data else SAVE_NO_DATA))
 
     @classmethod
     def load(cls, path: str, users=None, items=None, tables_only: bool = False, **flags):
@@ -1172,9 +1169,7 @@ class Model:
         self = cls.__new__(cls)
         self.lib = load_model_library()
         info = _ModelFileInfo()
-        rc = self.lib.frecsys_model_file_info(os.fsencode(path), 0, ctypes.byref(info))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_file_info(os.fsencode(path), 0, ctypes.byref(info)))
         cfg = _ModelConfig()
         ctypes.pointer(cfg)[0] = info.config
         self._name = bytes(info.model_name.decode(), "ascii")
@@ -1193,11 +1188,9 @@ class Model:
             it = np.ascontiguousarray(items, dtype=np.int32)
             assert u.shape == it.shape
         h = ctypes.c_void_p()
-        rc = self.lib.frecsys_model_load(os.fsencode(path), ctypes.byref(cfg), _ptr(u), _ptr(it),
-                                         0 if u is None else len(u),
-                                         LOAD_TABLES_ONLY if tables_only else 0, ctypes.byref(h))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_load(
+            os.fsencode(path), ctypes.byref(cfg), _ptr(u), _ptr(it), 0 if u is None else len(u),
+            LOAD_TABLES_ONLY if tables_only else 0, ctypes.byref(h)))
         self.h = h
         self.dim = cfg.dim
         self.n_users, self.n_items = info.n_users, info.n_items
@@ -1211,14 +1204,10 @@ class Model:
         return int(self.lib.frecsys_model_epochs(self.h))
 
     def initialize(self):
-        rc = self.lib.frecsys_model_initialize(self.h)
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_initialize(self.h))
 
     def train(self, epochs: int = 1):
-        rc = self.lib.frecsys_model_train(self.h, epochs)
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_train(self.h, epochs))
 
     def context(self) -> Context:
         """The model's device context (borrowed: closing it is a no-op)."""
@@ -1234,9 +1223,8 @@ class Model:
         l = np.zeros(self.n_users, dtype=np.float32)
         r = np.zeros(self.n_items, dtype=np.float32)
         xi = ctypes.c_float(0.0)
-        rc = self.lib.frecsys_model_dual_state(self.h, _ptr(w), _ptr(l), _ptr(r), ctypes.byref(xi))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_dual_state(self.h, _ptr(w), _ptr(l), _ptr(r),
+                                                      ctypes.byref(xi)))
         return w, l, r, float(xi.value)
 
     def mean_weight(self) -> float:
@@ -1249,20 +1237,40 @@ class Model:
         assert mk.shape == (self.n_items,), mk.shape
         return mk
 
+    # Every query comes for trained users and, as <name>_fold_in, for unseen
+    # users given by their histories.  The public pairs share one private body
+    # each, which takes the query rows as `head`, the leading arrays of the
+    # C call, and their count n.
+
+    @staticmethod
+    def _head(users=None, hist=None):
+        """(head, n) of trained `users`, or of hist = (hist_ptr, hist_items)."""
+        if hist is None:
+            u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
+            return [u], len(u)
+        hp = np.ascontiguousarray(hist[0], dtype=np.int64).reshape(-1)
+        hi = np.ascontiguousarray(hist[1], dtype=np.int32).reshape(-1)
+        return [hp, hi], len(hp) - 1
+
+    def _call(self, name: str, head, n: int, *tail):
+        """frecsys_model_<name>, or its _fold_in form for a history head."""
+        fn = getattr(self.lib, "frecsys_model_" + name + ("_fold_in" if len(head) == 2 else ""))
+        self._check(fn(self.h, *[_ptr(x) for x in head], n, *tail))
+
+    def _recommend(self, head, n, k, exclude_seen, item_mask):
+        mk = self._mask(item_mask)
+        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        self._call("recommend", head, n, k, int(bool(exclude_seen)), _ptr(mk), _ptr(items),
+                   _ptr(scores))
+        return items, scores
+
     def recommend(self, users, k: int, exclude_seen: bool = True, item_mask=None):
         """(items int32 [n, k], scores float32 [n, k]) for trained users
         (frecsys_model_recommend): best k items by score, ties by item id;
         exclude_seen drops the training history; item -1 / score -FLT_MAX
         beyond the eligible count."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        mk = self._mask(item_mask)
-        items = np.full((len(u), max(k, 0)), -1, dtype=np.int32)
-        scores = np.zeros(items.shape, dtype=np.float32)
-        rc = self.lib.frecsys_model_recommend(self.h, _ptr(u), len(u), k, int(bool(exclude_seen)),
-                                              _ptr(mk), _ptr(items), _ptr(scores))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return items, scores
+        return self._recommend(*self._head(users), k, exclude_seen, item_mask)
 
     def recommend_fold_in(self, hist_ptr, hist_items, k: int, exclude_seen: bool = True,
                           item_mask=None):
@@ -1270,18 +1278,17 @@ class Model:
         int64 [n + 1], hist_items int32): the model's fold-in projection, then
         the ranking (frecsys_model_recommend_fold_in).  The projected rows stay
         in the EVAL side of the model's context."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
+        return self._recommend(*self._head(hist=(hist_ptr, hist_items)), k, exclude_seen,
+                               item_mask)
+
+    def _recommend_diverse(self, head, n, k, pool, lam, raw_scores, exclude_history, item_mask,
+                           return_mmr):
         mk = self._mask(item_mask)
-        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
-        scores = np.zeros(items.shape, dtype=np.float32)
-        rc = self.lib.frecsys_model_recommend_fold_in(self.h, _ptr(hp), _ptr(hi), n, k,
-                                                      int(bool(exclude_seen)), _ptr(mk),
-                                                      _ptr(items), _ptr(scores))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return items, scores
+        items, scores, mmr = _diverse_out(n, k, return_mmr)
+        self._call("recommend_diverse", head, n, k, default_pool(k) if pool is None else pool,
+                   lam, int(bool(raw_scores)), int(bool(exclude_history)), _ptr(mk), _ptr(items),
+                   _ptr(scores), _ptr(mmr))
+        return (items, scores, mmr) if return_mmr else (items, scores)
 
     def recommend_diverse(self, users, k: int, pool: Optional[int] = None, lam: float = 0.7,
                           raw_scores: bool = False, exclude_history: bool = True, item_mask=None,
@@ -1291,16 +1298,8 @@ class Model:
         of recommend(users, pool)'s lists down to k against the item table --
         mmr_select's result bit for bit, computed on the GPU.  pool defaults to
         min(1024, max(k, 4 k)); lam = 1 returns recommend(users, k)."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        mk = self._mask(item_mask)
-        items, scores, mmr = _diverse_out(len(u), k, return_mmr)
-        rc = self.lib.frecsys_model_recommend_diverse(
-            self.h, _ptr(u), len(u), k, default_pool(k) if pool is None else pool, lam,
-            int(bool(raw_scores)), int(bool(exclude_history)), _ptr(mk), _ptr(items),
-            _ptr(scores), _ptr(mmr))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return (items, scores, mmr) if return_mmr else (items, scores)
+        return self._recommend_diverse(*self._head(users), k, pool, lam, raw_scores,
+                                       exclude_history, item_mask, return_mmr)
 
     def recommend_diverse_fold_in(self, hist_ptr, hist_items, k: int, pool: Optional[int] = None,
                                   lam: float = 0.7, raw_scores: bool = False,
@@ -1308,18 +1307,8 @@ class Model:
                                   return_mmr: bool = False):
         """The same for unseen users given by their histories (CSR), as
         recommend_fold_in (frecsys_model_recommend_diverse_fold_in)."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        mk = self._mask(item_mask)
-        items, scores, mmr = _diverse_out(n, k, return_mmr)
-        rc = self.lib.frecsys_model_recommend_diverse_fold_in(
-            self.h, _ptr(hp), _ptr(hi), n, k, default_pool(k) if pool is None else pool, lam,
-            int(bool(raw_scores)), int(bool(exclude_history)), _ptr(mk), _ptr(items),
-            _ptr(scores), _ptr(mmr))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return (items, scores, mmr) if return_mmr else (items, scores)
+        return self._recommend_diverse(*self._head(hist=(hist_ptr, hist_items)), k, pool, lam,
+                                       raw_scores, exclude_history, item_mask, return_mmr)
 
     def diversify(self, lists, scores, k: int, lam: float = 0.7, raw_scores: bool = False,
                   return_mmr: bool = False):
@@ -1328,17 +1317,29 @@ class Model:
         model's item table (frecsys_model_diversify)."""
         ls, sc = _pools(lists, scores)
         items, out, mmr = _diverse_out(ls.shape[0], k, return_mmr)
-        rc = self.lib.frecsys_model_diversify(self.h, _ptr(ls), _ptr(sc), ls.shape[0],
-                                              ls.shape[1], k, lam, int(bool(raw_scores)),
-                                              _ptr(items), _ptr(out), _ptr(mmr))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_diversify(self.h, _ptr(ls), _ptr(sc), ls.shape[0],
+                                                     ls.shape[1], k, lam, int(bool(raw_scores)),
+                                                     _ptr(items), _ptr(out), _ptr(mmr)))
         return (items, out, mmr) if return_mmr else (items, out)
 
-    def _explain_out(self, tp, top):
+    def _explain(self, head, n, tgt_ptr, tgt_items, top, full):
+        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
+        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
+        assert len(tp) == n + 1, (len(tp), n)
         pairs = int(tp[-1])
+        score = np.zeros(pairs, dtype=np.float32)
         items = np.full((pairs, max(top, 0)), -1, dtype=np.int32)
-        return np.zeros(pairs, dtype=np.float32), items, np.zeros(items.shape, dtype=np.float32)
+        contrib = np.zeros(items.shape, dtype=np.float32)
+        fl = fp = None
+        if full and len(head) == 2:  # sized by the histories given
+            fl, fp = _explain_full(np.diff(head[0]), tp)
+        elif full:  # ... or by the training CSR
+            # a call without rows loads the training CSR if Train() has not
+            self._call("explain", [None], 0, None, None, top, None, None, None, None)
+            fl, fp = _explain_full(self.context().csr_row_lengths(SIDE_USER, head[0]), tp)
+        self._call("explain", head, n, _ptr(tp), _ptr(ti), top, _ptr(score), _ptr(items),
+                   _ptr(contrib), _ptr(fl))
+        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
 
     def explain(self, users, tgt_ptr, tgt_items, top: int = 10, full: bool = False):
         """(score, top_items, top_contrib[, full, full_ptr]) for trained users
@@ -1351,24 +1352,7 @@ class Model:
         U[user] . V[item].  For ialspp / safer2pp it is the exact minimiser of
         the objective their block steps descend; their own fold-in stops after
         8 block epochs.  Needs the training tuples (not a serve-only model)."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
-        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
-        assert len(tp) == len(u) + 1, (len(tp), len(u))
-        score, items, contrib = self._explain_out(tp, top)
-        fl = fp = None
-        if full:
-            # a call without rows loads the training CSR if Train() has not
-            rc = self.lib.frecsys_model_explain(self.h, None, 0, None, None, top, None, None, None,
-                                                None)
-            if rc:
-                raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-            fl, fp = _explain_full(self.context().csr_row_lengths(SIDE_USER, u), tp)
-        rc = self.lib.frecsys_model_explain(self.h, _ptr(u), len(u), _ptr(tp), _ptr(ti), top,
-                                            _ptr(score), _ptr(items), _ptr(contrib), _ptr(fl))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
+        return self._explain(*self._head(users), tgt_ptr, tgt_items, top, full)
 
     def explain_fold_in(self, hist_ptr, hist_items, tgt_ptr, tgt_items, top: int = 10,
                         full: bool = False):
@@ -1377,22 +1361,8 @@ class Model:
         frecsys_model_explain_fold_in.  Bit for bit explain()'s result for a
         user with the same history.  The histories are loaded as the EVAL side
         of the model's context."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)
-        ti = np.ascontiguousarray(tgt_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        assert len(tp) == n + 1, (len(tp), n)
-        score, items, contrib = self._explain_out(tp, top)
-        fl = fp = None
-        if full:
-            fl, fp = _explain_full(np.diff(hp), tp)
-        rc = self.lib.frecsys_model_explain_fold_in(self.h, _ptr(hp), _ptr(hi), n, _ptr(tp),
-                                                    _ptr(ti), top, _ptr(score), _ptr(items),
-                                                    _ptr(contrib), _ptr(fl))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return (score, items, contrib, fl, fp) if full else (score, items, contrib)
+        return self._explain(*self._head(hist=(hist_ptr, hist_items)), tgt_ptr, tgt_items, top,
+                             full)
 
     def score(self, users, items) -> np.ndarray:
         """float32 [n]: the model's score of items[i] for trained user
@@ -1401,10 +1371,24 @@ class Model:
         it = np.ascontiguousarray(items, dtype=np.int32).reshape(-1)
         assert u.shape == it.shape, (u.shape, it.shape)
         out = np.zeros(len(u), dtype=np.float32)
-        rc = self.lib.frecsys_model_score(self.h, _ptr(u), _ptr(it), len(u), _ptr(out))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(self.lib.frecsys_model_score(self.h, _ptr(u), _ptr(it), len(u), _ptr(out)))
         return out
+
+    @staticmethod
+    def _candidates(cand_ptr, cand_items, n):
+        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
+        assert len(cp) == n + 1, (len(cp), n)
+        return cp, ci
+
+    def _rank_candidates(self, head, n, cand_ptr, cand_items, k, exclude_seen, item_mask):
+        cp, ci = self._candidates(cand_ptr, cand_items, n)
+        mk = self._mask(item_mask)
+        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        self._call("rank_candidates", head, n, _ptr(cp), _ptr(ci), k, int(bool(exclude_seen)),
+                   _ptr(mk), _ptr(items), _ptr(scores))
+        return items, scores
 
     def rank_candidates(self, users, cand_ptr, cand_items, k: int, exclude_seen: bool = True,
                         item_mask=None):
@@ -1412,19 +1396,8 @@ class Model:
         ids of each trained user's own candidate list (CSR cand_ptr /
         cand_items; list i belongs to users[i]) -- frecsys_model_rank_candidates;
         exclude_seen, item_mask and the fill as in recommend."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
-        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
-        assert len(cp) == len(u) + 1, (len(cp), len(u))
-        mk = self._mask(item_mask)
-        items = np.full((len(u), max(k, 0)), -1, dtype=np.int32)
-        scores = np.zeros(items.shape, dtype=np.float32)
-        rc = self.lib.frecsys_model_rank_candidates(self.h, _ptr(u), len(u), _ptr(cp), _ptr(ci), k,
-                                                    int(bool(exclude_seen)), _ptr(mk),
-                                                    _ptr(items), _ptr(scores))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return items, scores
+        return self._rank_candidates(*self._head(users), cand_ptr, cand_items, k, exclude_seen,
+                                     item_mask)
 
     def _similar(self, fn, n_side: int, rows, k: int, metric: str, include_self: bool, mask):
         if metric not in ("cosine", "dot"):
@@ -1437,9 +1410,7 @@ class Model:
         ids = np.full((len(r), k) if k > 0 else (len(r), 0), -1, dtype=np.int32)
         scores = np.zeros(ids.shape, dtype=np.float32)
         flags = (SIM_COSINE if metric == "cosine" else 0) | (SIM_KEEP_SELF if include_self else 0)
-        rc = fn(self.h, _ptr(r), len(r), k, flags, _ptr(mk), _ptr(ids), _ptr(scores))
-        if rc != OK:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._check(fn(self.h, _ptr(r), len(r), k, flags, _ptr(mk), _ptr(ids), _ptr(scores)))
         return ids, scores
 
     def similar_items(self, items, k: int, metric: str = "cosine", include_self: bool = False,
@@ -1466,25 +1437,33 @@ class Model:
         candidate list i for history row i
         (frecsys_model_rank_candidates_fold_in).  The projected rows stay in
         the EVAL side of the model's context."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
-        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        assert len(cp) == n + 1, (len(cp), n)
-        mk = self._mask(item_mask)
-        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
-        scores = np.zeros(items.shape, dtype=np.float32)
-        rc = self.lib.frecsys_model_rank_candidates_fold_in(
-            self.h, _ptr(hp), _ptr(hi), n, _ptr(cp), _ptr(ci), k, int(bool(exclude_seen)),
-            _ptr(mk), _ptr(items), _ptr(scores))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return items, scores
+        return self._rank_candidates(*self._head(hist=(hist_ptr, hist_items)), cand_ptr,
+                                     cand_items, k, exclude_seen, item_mask)
 
-    @staticmethod
-    def _evaluation(n, ks, al, rec, ndcg, summary):
+    def _eval_metrics(self, name, head, n, cand, gt_ptr, gt_items, sample, k_list, alpha_list,
+                      exclude_seen, item_mask=None, masked: bool = True):
+        """The Recall / NDCG evaluations frecsys_model_<name>: `cand` is the
+        candidate CSR or None, `sample` (n_neg, seed) or None; evaluate itself
+        takes no item mask (masked=False)."""
+        gp, gi = _ground_truth(gt_ptr, gt_items)
+        assert len(gp) == n + 1, (len(gp), n)
+        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
         nk, na = len(ks), len(al)
+        mk = self._mask(item_mask)
+        rec = np.zeros((n, nk), dtype=np.float32)
+        ndcg = np.zeros_like(rec)
+        summary = np.zeros((2 + 2 * na) * nk, dtype=np.float32)
+        args = []
+        if cand is not None:
+            args += [_ptr(x) for x in self._candidates(cand[0], cand[1], n)]
+        args += [_ptr(gp), _ptr(gi)]
+        if sample is not None:
+            args += [sample[0], sample[1] & 0xFFFFFFFFFFFFFFFF]
+        args += [_ptr(ks), nk, _ptr(al), na, int(bool(exclude_seen))]
+        if masked:
+            args += [_ptr(mk)]
+        self._call(name, head, n, *args, _ptr(rec), _ptr(ndcg), _ptr(summary))
         return {"recall": rec, "ndcg": ndcg, "k_list": ks, "alpha_list": al,
                 "mean_recall": summary[:nk].copy(), "mean_ndcg": summary[nk:2 * nk].copy(),
                 "recall_cvar": summary[2 * nk:(2 + na) * nk].reshape(na, nk).copy(),
@@ -1498,21 +1477,8 @@ class Model:
         "ndcg_cvar" [na, nk] (EvaluationResult's means and cvar()).  Row i of
         the CSR ground truth belongs to users[i]; the defaults are run_model's
         (run_model.cc:97-100)."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        gp, gi = _ground_truth(gt_ptr, gt_items)
-        assert len(gp) == len(u) + 1, (len(gp), len(u))
-        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
-        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
-        rec = np.zeros((len(u), len(ks)), dtype=np.float32)
-        ndcg = np.zeros_like(rec)
-        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
-        rc = self.lib.frecsys_model_evaluate(self.h, _ptr(u), len(u), _ptr(gp), _ptr(gi),
-                                             _ptr(ks), len(ks), _ptr(al), len(al),
-                                             int(bool(exclude_seen)), _ptr(rec), _ptr(ndcg),
-                                             _ptr(summary))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return self._evaluation(len(u), ks, al, rec, ndcg, summary)
+        return self._eval_metrics("evaluate", *self._head(users), None, gt_ptr, gt_items, None,
+                                  k_list, alpha_list, exclude_seen, masked=False)
 
     def evaluate_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items, k_list=EVAL_K_LIST,
                          alpha_list=EVAL_ALPHA_LIST, exclude_seen: bool = True):
@@ -1520,25 +1486,11 @@ class Model:
         hist_items): the model's fold-in projection, then the metrics of the
         projected rows (frecsys_model_evaluate_fold_in) -- the reference's
         EvaluateDataset.  The projected rows stay in the EVAL side."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        gp, gi = _ground_truth(gt_ptr, gt_items)
-        assert len(gp) == n + 1, (len(gp), n)
-        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
-        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
-        rec = np.zeros((n, len(ks)), dtype=np.float32)
-        ndcg = np.zeros_like(rec)
-        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
-        rc = self.lib.frecsys_model_evaluate_fold_in(self.h, _ptr(hp), _ptr(hi), n, _ptr(gp),
-                                                     _ptr(gi), _ptr(ks), len(ks), _ptr(al),
-                                                     len(al), int(bool(exclude_seen)), _ptr(rec),
-                                                     _ptr(ndcg), _ptr(summary))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return self._evaluation(n, ks, al, rec, ndcg, summary)
+        return self._eval_metrics("evaluate", *self._head(hist=(hist_ptr, hist_items)), None,
+                                  gt_ptr, gt_items, None, k_list, alpha_list, exclude_seen,
+                                  masked=False)
 
-    def _eval_ranks(self, fn, head, n, gt_ptr, gt_items, alpha_list, exclude_seen, item_mask):
+    def _eval_ranks(self, head, n, gt_ptr, gt_items, alpha_list, exclude_seen, item_mask):
         gp, gi = _ground_truth(gt_ptr, gt_items)
         assert len(gp) == n + 1, (len(gp), n)
         al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
@@ -1549,11 +1501,9 @@ class Model:
         mrr = np.zeros(n, dtype=np.float32)
         auc = np.zeros(n, dtype=np.float32)
         summary = np.zeros(2 + 2 * na, dtype=np.float32)
-        rc = fn(self.h, *[_ptr(x) for x in head], n, _ptr(gp), _ptr(gi), _ptr(al), na,
-                int(bool(exclude_seen)), _ptr(mk), _ptr(rank), _ptr(elig), _ptr(mrr), _ptr(auc),
-                _ptr(summary))
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
+        self._call("evaluate_ranks", head, n, _ptr(gp), _ptr(gi), _ptr(al), na,
+                   int(bool(exclude_seen)), _ptr(mk), _ptr(rank), _ptr(elig), _ptr(mrr), _ptr(auc),
+                   _ptr(summary))
         return {"rank": rank, "eligible": elig, "mrr": mrr, "auc": auc, "alpha_list": al,
                 "mean_mrr": float(summary[0]), "mean_auc": float(summary[1]),
                 "mrr_cvar": summary[2:2 + na].copy(), "auc_cvar": summary[2 + na:].copy()}
@@ -1567,9 +1517,8 @@ class Model:
         "mrr" and "auc" float32 [n], and "mean_mrr", "mean_auc", "mrr_cvar",
         "auc_cvar" [na] by evaluate()'s own mean and cvar().  Unlike Recall@K /
         NDCG@K these tell apart users whose held-out items rank below 1024."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        return self._eval_ranks(self.lib.frecsys_model_evaluate_ranks, [u], len(u), gt_ptr,
-                                gt_items, alpha_list, exclude_seen, item_mask)
+        return self._eval_ranks(*self._head(users), gt_ptr, gt_items, alpha_list, exclude_seen,
+                                item_mask)
 
     def evaluate_ranks_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items,
                                alpha_list=EVAL_ALPHA_LIST, exclude_seen: bool = True,
@@ -1578,36 +1527,8 @@ class Model:
         hist_items): the model's fold-in projection, then the positions of the
         projected rows (frecsys_model_evaluate_ranks_fold_in).  The projected
         rows stay in the EVAL side."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        return self._eval_ranks(self.lib.frecsys_model_evaluate_ranks_fold_in, [hp, hi],
-                                len(hp) - 1, gt_ptr, gt_items, alpha_list, exclude_seen, item_mask)
-
-    def _eval_lists(self, fn, head, n, cand, gt_ptr, gt_items, sample, k_list, alpha_list,
-                    exclude_seen, item_mask):
-        """The four list evaluations: `head` are the leading arguments (users
-        or the history CSR), `cand` the candidate CSR or None, `sample`
-        (n_neg, seed) or None."""
-        gp, gi = _ground_truth(gt_ptr, gt_items)
-        assert len(gp) == n + 1, (len(gp), n)
-        ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
-        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
-        mk = self._mask(item_mask)
-        rec = np.zeros((n, len(ks)), dtype=np.float32)
-        ndcg = np.zeros_like(rec)
-        summary = np.zeros((2 + 2 * len(al)) * len(ks), dtype=np.float32)
-        args = [self.h] + [_ptr(x) for x in head] + [n]
-        if cand is not None:
-            args += [_ptr(cand[0]), _ptr(cand[1])]
-        args += [_ptr(gp), _ptr(gi)]
-        if sample is not None:
-            args += [sample[0], sample[1] & 0xFFFFFFFFFFFFFFFF]
-        args += [_ptr(ks), len(ks), _ptr(al), len(al), int(bool(exclude_seen)), _ptr(mk),
-                 _ptr(rec), _ptr(ndcg), _ptr(summary)]
-        rc = fn(*args)
-        if rc:
-            raise FrecsysError(rc, self.lib.frecsys_model_last_error().decode())
-        return self._evaluation(n, ks, al, rec, ndcg, summary)
+        return self._eval_ranks(*self._head(hist=(hist_ptr, hist_items)), gt_ptr, gt_items,
+                                alpha_list, exclude_seen, item_mask)
 
     def evaluate_candidates(self, users, cand_ptr, cand_items, gt_ptr, gt_items,
                             k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
@@ -1617,13 +1538,9 @@ class Model:
         and ground-truth row i belong to users[i]) --
         frecsys_model_evaluate_candidates: the metrics of rank_candidates'
         lists, computed on the GPU."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
-        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
-        assert len(cp) == len(u) + 1, (len(cp), len(u))
-        return self._eval_lists(self.lib.frecsys_model_evaluate_candidates, [u], len(u), (cp, ci),
-                                gt_ptr, gt_items, None, k_list, alpha_list, exclude_seen,
-                                item_mask)
+        return self._eval_metrics("evaluate_candidates", *self._head(users),
+                                  (cand_ptr, cand_items), gt_ptr, gt_items, None, k_list,
+                                  alpha_list, exclude_seen, item_mask)
 
     def evaluate_candidates_fold_in(self, hist_ptr, hist_items, cand_ptr, cand_items, gt_ptr,
                                     gt_items, k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
@@ -1632,15 +1549,9 @@ class Model:
         projection, then the metrics of candidate list i for history row i
         (frecsys_model_evaluate_candidates_fold_in).  The projected rows stay
         in the EVAL side."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        cp = np.ascontiguousarray(cand_ptr, dtype=np.int64).reshape(-1)
-        ci = np.ascontiguousarray(cand_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        assert len(cp) == n + 1, (len(cp), n)
-        return self._eval_lists(self.lib.frecsys_model_evaluate_candidates_fold_in, [hp, hi], n,
-                                (cp, ci), gt_ptr, gt_items, None, k_list, alpha_list,
-                                exclude_seen, item_mask)
+        return self._eval_metrics("evaluate_candidates", *self._head(hist=(hist_ptr, hist_items)),
+                                  (cand_ptr, cand_items), gt_ptr, gt_items, None, k_list,
+                                  alpha_list, exclude_seen, item_mask)
 
     def evaluate_sampled(self, users, gt_ptr, gt_items, n_neg: int, seed: int = 0,
                          k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
@@ -1650,10 +1561,8 @@ class Model:
         against n_neg negatives drawn on the GPU (Context.sampled_metrics,
         sample_negatives).  Affordable per epoch where evaluate() is not --
         and not an estimate of evaluate()'s full-catalogue values."""
-        u = np.ascontiguousarray(users, dtype=np.int64).reshape(-1)
-        return self._eval_lists(self.lib.frecsys_model_evaluate_sampled, [u], len(u), None, gt_ptr,
-                                gt_items, (n_neg, seed), k_list, alpha_list, exclude_seen,
-                                item_mask)
+        return self._eval_metrics("evaluate_sampled", *self._head(users), None, gt_ptr, gt_items,
+                                  (n_neg, seed), k_list, alpha_list, exclude_seen, item_mask)
 
     def evaluate_sampled_fold_in(self, hist_ptr, hist_items, gt_ptr, gt_items, n_neg: int,
                                  seed: int = 0, k_list=EVAL_K_LIST, alpha_list=EVAL_ALPHA_LIST,
@@ -1661,12 +1570,9 @@ class Model:
         """The same for unseen users given by their histories
         (frecsys_model_evaluate_sampled_fold_in); history row i has side row
         id i in the generator.  The projected rows stay in the EVAL side."""
-        hp = np.ascontiguousarray(hist_ptr, dtype=np.int64).reshape(-1)
-        hi = np.ascontiguousarray(hist_items, dtype=np.int32).reshape(-1)
-        n = len(hp) - 1
-        return self._eval_lists(self.lib.frecsys_model_evaluate_sampled_fold_in, [hp, hi], n, None,
-                                gt_ptr, gt_items, (n_neg, seed), k_list, alpha_list, exclude_seen,
-                                item_mask)
+        return self._eval_metrics("evaluate_sampled", *self._head(hist=(hist_ptr, hist_items)),
+                                  None, gt_ptr, gt_items, (n_neg, seed), k_list, alpha_list,
+                                  exclude_seen, item_mask)
 
     def close(self):
         if getattr(self, "h", None):

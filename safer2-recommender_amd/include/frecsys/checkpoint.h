@@ -88,6 +88,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -210,31 +211,47 @@ using KeyValues = std::map<std::string, std::string>;
 
 namespace detail {
 
+// The one list of the stored numeric fields, in file order.  Config,
+// frecsys_model_config and ModelParams name them alike, so the list walks two
+// objects at once: f(name, a.field, b.field).  seed and parity_quirks are
+// options of the device context and not in ModelParams: they are visited when
+// both objects have them.
+template <class T, class = void>
+struct HasSeed : std::false_type {};
+template <class T>
+struct HasSeed<T, std::void_t<decltype(std::declval<T&>().seed)>> : std::true_type {};
+
+template <class A, class B, class F>
+void ForEachConfigField(A& a, B& b, F&& f) {
+  f("dim", a.dim, b.dim);
+  f("l2_reg", a.l2_reg, b.l2_reg);
+  f("l2_reg_exp", a.l2_reg_exp, b.l2_reg_exp);
+  f("uobs_weight", a.uobs_weight, b.uobs_weight);
+  f("stdev", a.stdev, b.stdev);
+  f("alpha", a.alpha, b.alpha);
+  f("bandwidth", a.bandwidth, b.bandwidth);
+  f("stepsize", a.stepsize, b.stepsize);
+  f("sampling_ratio", a.sampling_ratio, b.sampling_ratio);
+  f("block_size", a.block_size, b.block_size);
+  f("xi_iterations", a.xi_iterations, b.xi_iterations);
+  f("pd_iterations", a.pd_iterations, b.pd_iterations);
+  f("use_epanechnikov", a.use_epanechnikov, b.use_epanechnikov);
+  f("use_snr", a.use_snr, b.use_snr);
+  f("print_train_stats", a.print_train_stats, b.print_train_stats);
+  f("print_residual_stats", a.print_residual_stats, b.print_residual_stats);
+  f("print_var_stats", a.print_var_stats, b.print_var_stats);
+  if constexpr (HasSeed<A>::value && HasSeed<B>::value) {
+    f("seed", a.seed, b.seed);
+    f("parity_quirks", a.parity_quirks, b.parity_quirks);
+  }
+  f("use_cg", a.use_cg, b.use_cg);
+  f("cg_error_tolerance", a.cg_error_tolerance, b.cg_error_tolerance);
+  f("cg_max_iterations", a.cg_max_iterations, b.cg_max_iterations);
+}
 // f(name, field) for every numeric CONFIG field, in file order.
 template <class C, class F>
 void ForEachConfigField(C& c, F&& f) {
-  f("dim", c.dim);
-  f("l2_reg", c.l2_reg);
-  f("l2_reg_exp", c.l2_reg_exp);
-  f("uobs_weight", c.uobs_weight);
-  f("stdev", c.stdev);
-  f("alpha", c.alpha);
-  f("bandwidth", c.bandwidth);
-  f("stepsize", c.stepsize);
-  f("sampling_ratio", c.sampling_ratio);
-  f("block_size", c.block_size);
-  f("xi_iterations", c.xi_iterations);
-  f("pd_iterations", c.pd_iterations);
-  f("use_epanechnikov", c.use_epanechnikov);
-  f("use_snr", c.use_snr);
-  f("print_train_stats", c.print_train_stats);
-  f("print_residual_stats", c.print_residual_stats);
-  f("print_var_stats", c.print_var_stats);
-  f("seed", c.seed);
-  f("parity_quirks", c.parity_quirks);
-  f("use_cg", c.use_cg);
-  f("cg_error_tolerance", c.cg_error_tolerance);
-  f("cg_max_iterations", c.cg_max_iterations);
+  ForEachConfigField(c, c, [&f](const char* n, auto& x, auto&) { f(n, x); });
 }
 
 struct FieldWriter {
@@ -309,6 +326,15 @@ inline std::string tag_string(const char* tag8) {
 }
 
 }  // namespace detail
+
+// to->field = from.field for every field of the list that both have, converted
+// to the field's type: a flag kept as an int becomes a bool by != 0, a bool 0 / 1.
+template <class From, class To>
+void CopyConfigFields(const From& from, To* to) {
+  detail::ForEachConfigField(from, *to, [](const char*, const auto& s, auto& d) {
+    d = static_cast<std::decay_t<decltype(d)>>(s);
+  });
+}
 
 // `name=value` lines <-> a map.  A line without '=' or an empty name is an
 // error; a repeated name keeps its last value.
@@ -829,54 +855,16 @@ static_assert(kInvalid == FRECSYS_ERR_INVALID && kIo == FRECSYS_ERR_IO && kOk ==
 
 inline ModelParams ToParams(const Config& c) {
   ModelParams p;
-  p.dim = c.dim;
-  p.l2_reg = c.l2_reg;
-  p.l2_reg_exp = c.l2_reg_exp;
-  p.uobs_weight = c.uobs_weight;
-  p.stdev = c.stdev;
-  p.alpha = c.alpha;
-  p.bandwidth = c.bandwidth;
-  p.stepsize = c.stepsize;
-  p.sampling_ratio = c.sampling_ratio;
-  p.block_size = c.block_size;
-  p.xi_iterations = c.xi_iterations;
-  p.pd_iterations = c.pd_iterations;
-  p.use_epanechnikov = c.use_epanechnikov != 0;
-  p.use_snr = c.use_snr != 0;
-  p.print_train_stats = c.print_train_stats != 0;
-  p.print_residual_stats = c.print_residual_stats != 0;
-  p.print_var_stats = c.print_var_stats != 0;
-  p.use_cg = c.use_cg != 0;
-  p.cg_error_tolerance = c.cg_error_tolerance;
-  p.cg_max_iterations = c.cg_max_iterations;
+  CopyConfigFields(c, &p);
   return p;
 }
 inline Config FromParams(const std::string& model_name, const ModelParams& p, int64_t seed,
                          bool parity_quirks) {
   Config c;
   c.model_name = model_name;
-  c.dim = p.dim;
-  c.l2_reg = p.l2_reg;
-  c.l2_reg_exp = p.l2_reg_exp;
-  c.uobs_weight = p.uobs_weight;
-  c.stdev = p.stdev;
-  c.alpha = p.alpha;
-  c.bandwidth = p.bandwidth;
-  c.stepsize = p.stepsize;
-  c.sampling_ratio = p.sampling_ratio;
-  c.block_size = p.block_size;
-  c.xi_iterations = p.xi_iterations;
-  c.pd_iterations = p.pd_iterations;
-  c.use_epanechnikov = p.use_epanechnikov;
-  c.use_snr = p.use_snr;
-  c.print_train_stats = p.print_train_stats;
-  c.print_residual_stats = p.print_residual_stats;
-  c.print_var_stats = p.print_var_stats;
+  CopyConfigFields(p, &c);
   c.seed = seed;
   c.parity_quirks = parity_quirks;
-  c.use_cg = p.use_cg;
-  c.cg_error_tolerance = p.cg_error_tolerance;
-  c.cg_max_iterations = p.cg_max_iterations;
   return c;
 }
 

@@ -2,6 +2,13 @@
 // over the C++ model classes (include/frecsys/*.h).  A thin owner of one
 // Dataset + one Recommender built by the run_model factory
 // (frecsys/factory.h); every compute call lands in libfrecsys_hip.so.
+//
+// The query entry points (recommend, rank_candidates, the evaluations, explain,
+// recommend_diverse) come as a trained-users form and a _fold_in form.  Each
+// pair is one function over a Query -- trained user ids or a history CSR --
+// that open_query() checks and, for histories, projects; the extern "C"
+// functions only name the call and build the Query.  The stored model flags
+// are listed once, in checkpoint.h (ForEachConfigField).
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -26,6 +33,8 @@ struct frecsys_model {
 };
 
 namespace {
+namespace ck = frecsys::checkpoint;
+
 std::string g_model_error;
 int model_fail(int code, const std::string& msg) {
   g_model_error = msg;
@@ -37,95 +46,29 @@ extern "C" {
 
 void frecsys_model_config_default(frecsys_model_config* c) {
   if (!c) return;
-  std::memset(c, 0, sizeof(*c));
-  const frecsys::ModelParams p;  // run_model.cc:129-230 defaults
-  c->dim = p.dim;
-  c->l2_reg = p.l2_reg;
-  c->l2_reg_exp = p.l2_reg_exp;
-  c->uobs_weight = p.uobs_weight;
-  c->stdev = p.stdev;
-  c->alpha = p.alpha;
-  c->bandwidth = p.bandwidth;
-  c->stepsize = p.stepsize;
-  c->sampling_ratio = p.sampling_ratio;
-  c->block_size = p.block_size;
-  c->xi_iterations = p.xi_iterations;
-  c->pd_iterations = p.pd_iterations;
-  c->use_epanechnikov = p.use_epanechnikov;
-  c->use_snr = p.use_snr;
-  c->print_train_stats = p.print_train_stats;
-  c->print_residual_stats = p.print_residual_stats;
-  c->print_var_stats = p.print_var_stats;
+  std::memset(c, 0, sizeof(*c));  // world 0, comm_id and model_name null
+  ck::CopyConfigFields(frecsys::ModelParams(), c);  // run_model.cc:129-230 defaults
   c->seed = -1;
   c->device = -1;
   c->parity_quirks = 1;
-  c->world = 0;
   c->rank = -1;
-  c->comm_id = nullptr;
-  c->use_cg = p.use_cg;
-  c->cg_error_tolerance = p.cg_error_tolerance;
-  c->cg_max_iterations = p.cg_max_iterations;
 }
 
 }  // extern "C"
 
 namespace {
 
-namespace ck = frecsys::checkpoint;
-
-// The stored fields of a C config (device / world / rank / comm_id stay out).
+// The stored fields of a C config (device / world / rank / comm_id stay out),
+// the flags among them as 0 / 1: through ModelParams, where they are bools.
 ck::Config stored_config(const frecsys_model_config& c, const std::string& name) {
-  ck::Config k;
-  k.model_name = name;
-  k.dim = c.dim;
-  k.l2_reg = c.l2_reg;
-  k.l2_reg_exp = c.l2_reg_exp;
-  k.uobs_weight = c.uobs_weight;
-  k.stdev = c.stdev;
-  k.alpha = c.alpha;
-  k.bandwidth = c.bandwidth;
-  k.stepsize = c.stepsize;
-  k.sampling_ratio = c.sampling_ratio;
-  k.block_size = c.block_size;
-  k.xi_iterations = c.xi_iterations;
-  k.pd_iterations = c.pd_iterations;
-  k.use_epanechnikov = c.use_epanechnikov != 0;
-  k.use_snr = c.use_snr != 0;
-  k.print_train_stats = c.print_train_stats != 0;
-  k.print_residual_stats = c.print_residual_stats != 0;
-  k.print_var_stats = c.print_var_stats != 0;
-  k.seed = c.seed;
-  k.parity_quirks = c.parity_quirks != 0;
-  k.use_cg = c.use_cg != 0;
-  k.cg_error_tolerance = c.cg_error_tolerance;
-  k.cg_max_iterations = c.cg_max_iterations;
-  return k;
+  frecsys::ModelParams p;
+  ck::CopyConfigFields(c, &p);
+  return ck::FromParams(name, p, c.seed, c.parity_quirks != 0);
 }
 // ... and back, on top of the defaults; model_name is left to the caller.
 void c_config(const ck::Config& k, frecsys_model_config* c) {
   frecsys_model_config_default(c);
-  c->dim = k.dim;
-  c->l2_reg = k.l2_reg;
-  c->l2_reg_exp = k.l2_reg_exp;
-  c->uobs_weight = k.uobs_weight;
-  c->stdev = k.stdev;
-  c->alpha = k.alpha;
-  c->bandwidth = k.bandwidth;
-  c->stepsize = k.stepsize;
-  c->sampling_ratio = k.sampling_ratio;
-  c->block_size = k.block_size;
-  c->xi_iterations = k.xi_iterations;
-  c->pd_iterations = k.pd_iterations;
-  c->use_epanechnikov = k.use_epanechnikov;
-  c->use_snr = k.use_snr;
-  c->print_train_stats = k.print_train_stats;
-  c->print_residual_stats = k.print_residual_stats;
-  c->print_var_stats = k.print_var_stats;
-  c->seed = k.seed;
-  c->parity_quirks = k.parity_quirks;
-  c->use_cg = k.use_cg;
-  c->cg_error_tolerance = k.cg_error_tolerance;
-  c->cg_max_iterations = k.cg_max_iterations;
+  ck::CopyConfigFields(k, c);
 }
 
 // The use_cg and block_size rules of a configuration, which need no device
@@ -409,187 +352,53 @@ int frecsys_model_dual_state(const frecsys_model* m, float* weights, float* loss
   return FRECSYS_OK;
 }
 
-int frecsys_model_recommend(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
-                            int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
-                            float* scores) {
-  if (!m || n < 0 || (n > 0 && !users))
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend: bad arguments");
-  if (exclude_seen)
-    if (int rc = needs_data(m, "frecsys_model_recommend")) return rc;
-  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
-  const int rc = dev.TryRecommend(FRECSYS_SIDE_USER, users, n, k,
-                                  exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
-                                  items, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
-                                    const int32_t* hist_items, int64_t n, int32_t k,
-                                    int32_t exclude_seen, const uint8_t* item_mask,
-                                    int32_t* items, float* scores) {
-  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0)
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: bad arguments");
-  // checked here: the C++ layer treats a bad EVAL CSR as fatal
-  if (k < 1 || k > 1024 || (n > 0 && !items))
-    return model_fail(FRECSYS_ERR_INVALID,
-                      "frecsys_model_recommend_fold_in: k must be in [1, 1024], items non-null");
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
-  for (int64_t i = 0; i < n; ++i)
-    if (hist_ptr[i + 1] < hist_ptr[i])
-      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: hist_ptr not monotone");
-  if (hist_ptr[n] > 0 && !hist_items)
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: null hist_items");
-  for (int64_t p = 0; p < hist_ptr[n]; ++p)
-    if (hist_items[p] < 0 || hist_items[p] >= n_items)
-      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_recommend_fold_in: item id " +
-                                                 std::to_string(hist_items[p]) + " out of range");
-  if (n == 0) return FRECSYS_OK;
-  frecsys::Csr csr;
-  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-  dm->FoldIn(csr);
-  const int rc = dm->device().TryRecommend(FRECSYS_SIDE_EVAL, nullptr, n, k,
-                                           exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
-                                           item_mask, items, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
-                        float* scores) {
-  if (!m || n < 0 || (n > 0 && (!users || !items || !scores)))
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_score: bad arguments");
-  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
-  const int rc = dev.TryScorePairs(FRECSYS_SIDE_USER, users, items, n, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_explain(frecsys_model* m, const int64_t* users, int64_t n,
-                          const int64_t* tgt_ptr, const int32_t* tgt_items, int32_t top,
-                          float* score, int32_t* top_items, float* top_contrib, float* full) {
-  if (!m || n < 0 || (n > 0 && (!users || !tgt_ptr)))
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_explain: bad arguments");
-  if (int rc = needs_data(m, "frecsys_model_explain")) return rc;
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  dm->device().LoadTraining(*m->train);  // once per dataset; Train() has usually done it
-  const int rc = dm->Explain(users, n, tgt_ptr, tgt_items, top, score, top_items, top_contrib, full);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_explain_fold_in(frecsys_model* m, const int64_t* hist_ptr,
-                                  const int32_t* hist_items, int64_t n, const int64_t* tgt_ptr,
-                                  const int32_t* tgt_items, int32_t top, float* score,
-                                  int32_t* top_items, float* top_contrib, float* full) {
-  const std::string w = "frecsys_model_explain_fold_in: ";
-  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0 || !tgt_ptr)
-    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  // checked here: the C++ layer treats a bad EVAL CSR as fatal
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
-  for (int64_t i = 0; i < n; ++i)
-    if (hist_ptr[i + 1] < hist_ptr[i])
-      return model_fail(FRECSYS_ERR_INVALID, w + "hist_ptr not monotone");
-  if (hist_ptr[n] > 0 && !hist_items) return model_fail(FRECSYS_ERR_INVALID, w + "null hist_items");
-  for (int64_t p = 0; p < hist_ptr[n]; ++p)
-    if (hist_items[p] < 0 || hist_items[p] >= n_items)
-      return model_fail(FRECSYS_ERR_INVALID,
-                        w + "item id " + std::to_string(hist_items[p]) + " out of range");
-  if (n == 0) return FRECSYS_OK;
-  frecsys::Csr csr;
-  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-  const int rc =
-      dm->ExplainFoldIn(csr, tgt_ptr, tgt_items, top, score, top_items, top_contrib, full);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_t n,
-                                  const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
-                                  int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
-                                  float* scores) {
-  if (!m || n < 0 || (n > 0 && !users))
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_rank_candidates: bad arguments");
-  if (exclude_seen)
-    if (int rc = needs_data(m, "frecsys_model_rank_candidates")) return rc;
-  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
-  const int rc = dev.TryRankCandidates(FRECSYS_SIDE_USER, users, n, cand_ptr, cand_items, k,
-                                       exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask,
-                                       items, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
-}
-
-static int model_similar(frecsys_model* m, const char* what, int side, const int64_t* rows,
-                         int64_t n, int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids,
-                         float* scores) {
-  if (!m || n < 0 || (n > 0 && !ids))
-    return model_fail(FRECSYS_ERR_INVALID, std::string(what) + ": bad arguments");
-  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
-  const int rc = dev.TrySimilar(side, rows, n, k, flags, mask, ids, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
-}
-
-int frecsys_model_similar_items(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
-                                int32_t flags, const uint8_t* item_mask, int32_t* ids,
-                                float* scores) {
-  return model_similar(m, "frecsys_model_similar_items", FRECSYS_SIDE_ITEM, items, n, k, flags,
-                       item_mask, ids, scores);
-}
-
-int frecsys_model_similar_users(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
-                                int32_t flags, const uint8_t* user_mask, int32_t* ids,
-                                float* scores) {
-  return model_similar(m, "frecsys_model_similar_users", FRECSYS_SIDE_USER, users, n, k, flags,
-                       user_mask, ids, scores);
-}
-
-int frecsys_model_rank_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
-                                          const int32_t* hist_items, int64_t n,
-                                          const int64_t* cand_ptr, const int32_t* cand_items,
-                                          int32_t k, int32_t exclude_seen,
-                                          const uint8_t* item_mask, int32_t* items,
-                                          float* scores) {
-  const std::string w = "frecsys_model_rank_candidates_fold_in: ";
-  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0 || !cand_ptr || cand_ptr[0] != 0)
-    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  // checked here: the C++ layer treats a bad EVAL CSR as fatal, and the
-  // candidate lists are checked before the projection runs
-  if (k < 1 || k > 1024 || (n > 0 && !items))
-    return model_fail(FRECSYS_ERR_INVALID, w + "k must be in [1, 1024], items non-null");
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
-  for (int64_t i = 0; i < n; ++i)
-    if (hist_ptr[i + 1] < hist_ptr[i] || cand_ptr[i + 1] < cand_ptr[i])
-      return model_fail(FRECSYS_ERR_INVALID, w + "hist_ptr / cand_ptr not monotone");
-  if ((hist_ptr[n] > 0 && !hist_items) || (cand_ptr[n] > 0 && !cand_items))
-    return model_fail(FRECSYS_ERR_INVALID, w + "null hist_items / cand_items");
-  for (int64_t p = 0; p < hist_ptr[n]; ++p)
-    if (hist_items[p] < 0 || hist_items[p] >= n_items)
-      return model_fail(FRECSYS_ERR_INVALID,
-                        w + "item id " + std::to_string(hist_items[p]) + " out of range");
-  for (int64_t p = 0; p < cand_ptr[n]; ++p)
-    if (cand_items[p] < 0 || cand_items[p] >= n_items)
-      return model_fail(FRECSYS_ERR_INVALID,
-                        w + "candidate id " + std::to_string(cand_items[p]) + " out of range");
-  if (n == 0) return FRECSYS_OK;
-  frecsys::Csr csr;
-  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-  dm->FoldIn(csr);
-  const int rc = dm->device().TryRankCandidates(
-      FRECSYS_SIDE_EVAL, nullptr, n, cand_ptr, cand_items, k,
-      exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, item_mask, items, scores);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
-}
-
 }  // extern "C"
 
 namespace {
 
-// The argument checks of the two evaluate entry points, before any device
-// call (the C++ layer treats a failed device call as fatal); "" when fine.
-// Its pieces, shared with the rank evaluation: the row count and the head of
-// the ground-truth CSR, the alphas, and the CSR's rows and ids (gt_items not
-// null when there are rows: the caller's check).
+using frecsys::DeviceContext;
+
+// The status of a context call: the context's message goes with its code.
+int context_status(DeviceContext& dev, int rc) {
+  return rc ? model_fail(rc, frecsys_last_error(dev.raw())) : FRECSYS_OK;
+}
+
+int exclude_flag(int32_t exclude_seen) { return exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0; }
+
+// ---- argument checks, before any device call (the C++ layer treats a failed
+// device call and a bad EVAL CSR as fatal); "" when fine ----
+
+std::string hist_args_error(int64_t n, int64_t n_items, const int64_t* hist_ptr,
+                            const int32_t* hist_items) {
+  if (n < 0 || !hist_ptr || hist_ptr[0] != 0) return "bad arguments";
+  for (int64_t i = 0; i < n; ++i)
+    if (hist_ptr[i + 1] < hist_ptr[i]) return "hist_ptr not monotone";
+  if (hist_ptr[n] > 0 && !hist_items) return "null hist_items";
+  for (int64_t p = 0; p < hist_ptr[n]; ++p)
+    if (hist_items[p] < 0 || hist_items[p] >= n_items)
+      return "item id " + std::to_string(hist_items[p]) + " out of range";
+  return "";
+}
+
+std::string cand_args_error(int64_t n, int64_t n_items, const int64_t* cand_ptr,
+                            const int32_t* cand_items) {
+  if (!cand_ptr || cand_ptr[0] != 0) return "bad cand_ptr";
+  for (int64_t i = 0; i < n; ++i)
+    if (cand_ptr[i + 1] < cand_ptr[i]) return "cand_ptr not monotone";
+  if (cand_ptr[n] > 0 && !cand_items) return "null cand_items";
+  for (int64_t p = 0; p < cand_ptr[n]; ++p)
+    if (cand_items[p] < 0 || cand_items[p] >= n_items)
+      return "candidate id " + std::to_string(cand_items[p]) + " out of range";
+  return "";
+}
+
+std::string k_items_error(int32_t k, int64_t n, const int32_t* items) {
+  return k < 1 || k > 1024 || (n > 0 && !items) ? "k must be in [1, 1024], items non-null" : "";
+}
+
+// The pieces of the evaluations' checks: the row count and the head of the
+// ground-truth CSR, the alphas, and the CSR's rows and ids (gt_items not null
+// when there are rows: the caller's check).
 std::string truth_head_error(int64_t n, const int64_t* gt_ptr) {
   return n < 0 || !gt_ptr || gt_ptr[0] != 0 ? "bad arguments (n < 0, gt_ptr)" : "";
 }
@@ -606,37 +415,181 @@ std::string truth_rows_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
       return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
   return "";
 }
-std::string evaluate_args_error(int64_t n, int64_t n_items, const int64_t* gt_ptr,
-                                const int32_t* gt_items, const int32_t* k_list, int32_t nk,
-                                const float* alpha_list, int32_t na, const float* recall,
-                                const float* ndcg) {
-  std::string e = truth_head_error(n, gt_ptr);
+
+// The arguments every Recall / NDCG evaluation shares.
+struct Metrics {
+  const int64_t* gt_ptr;
+  const int32_t* gt_items;
+  const int32_t* k_list;
+  int32_t nk;
+  const float* alpha_list;
+  int32_t na;
+  float* recall;
+  float* ndcg;
+  float* summary;
+};
+
+std::string metrics_args_error(int64_t n, int64_t n_items, const Metrics& mt) {
+  std::string e = truth_head_error(n, mt.gt_ptr);
   if (!e.empty()) return e;
-  if (!k_list || nk < 1 || nk > 32) return "k_list must hold 1 to 32 cut-offs";
-  for (int32_t q = 0; q < nk; ++q)
-    if (k_list[q] < 1 || k_list[q] > 1024) return "cut-offs must be in [1, 1024]";
-  if (!(e = alpha_error(alpha_list, na)).empty()) return e;
-  if (n > 0 && (!recall || !ndcg || !gt_items)) return "null gt_items / recall / ndcg";
-  return truth_rows_error(n, n_items, gt_ptr, gt_items);
+  if (!mt.k_list || mt.nk < 1 || mt.nk > 32) return "k_list must hold 1 to 32 cut-offs";
+  for (int32_t q = 0; q < mt.nk; ++q)
+    if (mt.k_list[q] < 1 || mt.k_list[q] > 1024) return "cut-offs must be in [1, 1024]";
+  if (!(e = alpha_error(mt.alpha_list, mt.na)).empty()) return e;
+  if (n > 0 && (!mt.recall || !mt.ndcg || !mt.gt_items)) return "null gt_items / recall / ndcg";
+  return truth_rows_error(n, n_items, mt.gt_ptr, mt.gt_items);
 }
 
-// Metrics of `n` query rows of `side` into recall / ndcg, then the summary
-// [(2 + 2 na) nk]: mean recall, mean ndcg, recall CVaR [na][nk], ndcg CVaR
-// [na][nk] -- EvaluationResult's own colwise().mean() and cvar().
-int summarize(int64_t n, const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
-              const float* recall, const float* ndcg, float* summary);
-
-int evaluate_rows(frecsys::DeviceContext& dev, int side, const int64_t* rows, int64_t n,
-                  int32_t exclude_seen, const int64_t* gt_ptr, const int32_t* gt_items,
-                  const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
-                  float* recall, float* ndcg, float* summary) {
-  const int rc = dev.TryRankMetrics(side, rows, n, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
-                                    nullptr, gt_ptr, gt_items, k_list, nk, recall, ndcg);
-  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
-  return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
+// The cases the MMR calls reject (frecsys_hip.h).
+std::string diverse_args_error(int32_t k, int32_t pool, float lam, int32_t raw_scores, int64_t n,
+                               const int32_t* items, const float* scores) {
+  if (pool < 1 || pool > 1024) return "pool must be in [1, 1024]";
+  if (k < 1 || k > pool) return "k must be in [1, pool]";
+  if (!(lam >= 0.0f && lam <= 1.0f)) return "lam must be in [0, 1]";
+  if (raw_scores != 0 && raw_scores != 1) return "raw_scores must be 0 or 1";
+  if (n > 0 && (!items || !scores)) return "null outputs";
+  return "";
 }
 
-// The summary of per-row metric values: the same for every evaluation.
+int32_t diverse_flags(int32_t exclude_seen, int32_t raw_scores) {
+  return exclude_flag(exclude_seen) | (raw_scores ? FRECSYS_DIV_RAW_SCORES : 0);
+}
+
+// ---- the query rows of a model call ----
+
+// n trained users (rows of U), or the histories of n unseen users as a CSR,
+// which the model projects into the EVAL side of its context.
+struct Query {
+  const int64_t* users;
+  const int64_t* hist_ptr;
+  const int32_t* hist_items;
+  int64_t n;
+  bool fold_in;
+};
+Query trained(const int64_t* users, int64_t n) { return {users, nullptr, nullptr, n, false}; }
+Query unseen(const int64_t* hist_ptr, const int32_t* hist_items, int64_t n) {
+  return {nullptr, hist_ptr, hist_items, n, true};
+}
+
+// Where an opened query's rows are: the side and the row ids to hand to the
+// context (nullptr: rows 0 .. n-1, the projected ones).
+struct Rows {
+  frecsys::detail::DeviceModel* dm = nullptr;
+  int side = FRECSYS_SIDE_USER;
+  const int64_t* ids = nullptr;
+  DeviceContext& dev() const { return dm->device(); }
+};
+
+// open_query's answer for zero histories: nothing to project, nothing to run.
+// Not a status code; the entry point answers (answered() for most).  Zero
+// trained users go on to the context, which answers for them.
+constexpr int kNoRows = -1;
+int answered(int rc) { return rc == kNoRows ? FRECSYS_OK : rc; }
+
+// What every query entry point does first, in this order: the model; the
+// training tuples where the call reads them (exclude_seen on trained users);
+// the history CSR; the entry point's own checks, own_error(n_items); the
+// trained rows (last: the evaluations word a negative n themselves); then,
+// with every check done, the projection of the histories -- the model's
+// FoldIn, or for explain the bare LoadEval.  `w` is the prefix of every
+// message, "<entry point>: ".
+enum Projection { kFoldIn, kLoadOnly };
+template <class OwnError>
+int open_query(frecsys_model* m, const std::string& w, const Query& q, int32_t reads_training,
+               OwnError own_error, Rows* r, Projection projection = kFoldIn) {
+  if (!m) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  if (reads_training && !q.fold_in)
+    if (int rc = needs_data(m, w.substr(0, w.size() - 2).c_str())) return rc;
+  r->dm = frecsys::AsDeviceModel(m->rec.get());
+  const int64_t n_items = r->dev().rows(DeviceContext::ITEM);
+  std::string e = q.fold_in ? hist_args_error(q.n, n_items, q.hist_ptr, q.hist_items) : "";
+  if (e.empty()) e = own_error(n_items);
+  if (e.empty() && !q.fold_in && (q.n < 0 || (q.n > 0 && !q.users))) e = "bad arguments";
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (!q.fold_in) {
+    r->ids = q.users;
+    return FRECSYS_OK;
+  }
+  if (q.n == 0) return kNoRows;
+  frecsys::Csr csr;
+  csr.ptr.assign(q.hist_ptr, q.hist_ptr + q.n + 1);
+  csr.col.assign(q.hist_items, q.hist_items + q.hist_ptr[q.n]);
+  if (projection == kFoldIn) {
+    r->dm->FoldIn(csr);
+  } else {
+    r->dev().LoadEval(csr);
+  }
+  r->side = FRECSYS_SIDE_EVAL;
+  return FRECSYS_OK;
+}
+
+// ---- the query entry points, one body per trained / fold-in pair ----
+
+// The trained form leaves k, the outputs and the candidate CSR to the context,
+// in whose words they are reported; the fold-in form checks them here, before
+// the projection.
+int recommend(frecsys_model* m, const std::string& w, const Query& q, int32_t k,
+              int32_t exclude_seen, const uint8_t* item_mask, int32_t* items, float* scores) {
+  Rows r;
+  const auto own = [&](int64_t) { return q.fold_in ? k_items_error(k, q.n, items) : ""; };
+  if (int rc = open_query(m, w, q, exclude_seen, own, &r)) return answered(rc);
+  return context_status(r.dev(), r.dev().TryRecommend(r.side, r.ids, q.n, k,
+                                                      exclude_flag(exclude_seen), item_mask,
+                                                      items, scores));
+}
+
+int rank_candidates(frecsys_model* m, const std::string& w, const Query& q,
+                    const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                    int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                    float* scores) {
+  Rows r;
+  const auto own = [&](int64_t n_items) -> std::string {
+    if (!q.fold_in) return "";
+    if (!cand_ptr || cand_ptr[0] != 0) return "bad arguments";
+    const std::string e = k_items_error(k, q.n, items);
+    return e.empty() ? cand_args_error(q.n, n_items, cand_ptr, cand_items) : e;
+  };
+  if (int rc = open_query(m, w, q, exclude_seen, own, &r)) return answered(rc);
+  return context_status(
+      r.dev(), r.dev().TryRankCandidates(r.side, r.ids, q.n, cand_ptr, cand_items, k,
+                                         exclude_flag(exclude_seen), item_mask, items, scores));
+}
+
+int recommend_diverse(frecsys_model* m, const std::string& w, const Query& q, int32_t k,
+                      int32_t pool, float lam, int32_t raw_scores, int32_t exclude_seen,
+                      const uint8_t* item_mask, int32_t* items, float* scores, float* mmr) {
+  Rows r;
+  const auto own = [&](int64_t) {
+    return diverse_args_error(k, pool, lam, raw_scores, q.n, items, scores);
+  };
+  if (int rc = open_query(m, w, q, exclude_seen, own, &r)) return answered(rc);
+  return context_status(r.dev(), r.dm->RecommendDiverse(r.side, r.ids, q.n, k, pool, lam,
+                                                        diverse_flags(exclude_seen, raw_scores),
+                                                        item_mask, items, scores, mmr));
+}
+
+// DeviceModel::Explain / ExplainFoldIn on the opened rows: trained users are
+// explained over the training CSR (loaded here if Train() has not: also by a
+// call without rows), histories over the EVAL CSR open_query loaded.
+int explain(frecsys_model* m, const std::string& w, const Query& q, const int64_t* tgt_ptr,
+            const int32_t* tgt_items, int32_t top, float* score, int32_t* top_items,
+            float* top_contrib, float* full) {
+  Rows r;
+  const auto own = [&](int64_t) {
+    return (q.fold_in || q.n > 0) && !tgt_ptr ? "bad arguments" : "";
+  };
+  if (int rc = open_query(m, w, q, /*reads_training=*/1, own, &r, kLoadOnly)) return answered(rc);
+  if (!q.fold_in) r.dev().LoadTraining(*m->train);
+  r.dev().Gramian(DeviceContext::ITEM);
+  const frecsys_solve_params p = r.dm->ExplainParams();
+  return context_status(r.dev(), frecsys_explain(r.dev().raw(), r.side, &p, r.ids, q.n, tgt_ptr,
+                                                 tgt_items, top, score, top_items, top_contrib,
+                                                 full));
+}
+
+// The summary of per-row metric values [(2 + 2 na) nk]: mean recall, mean
+// ndcg, recall CVaR [na][nk], ndcg CVaR [na][nk] -- EvaluationResult's own
+// colwise().mean() and cvar().  The same for every evaluation.
 int summarize(int64_t n, const int32_t* k_list, int32_t nk, const float* alpha_list, int32_t na,
               const float* recall, const float* ndcg, float* summary) {
   if (!summary) return FRECSYS_OK;
@@ -664,6 +617,23 @@ int summarize(int64_t n, const int32_t* k_list, int32_t nk, const float* alpha_l
   }
   return FRECSYS_OK;
 }
+int summarize(int64_t n, const Metrics& mt) {
+  return summarize(n, mt.k_list, mt.nk, mt.alpha_list, mt.na, mt.recall, mt.ndcg, mt.summary);
+}
+
+int evaluate(frecsys_model* m, const std::string& w, const Query& q, const Metrics& mt,
+             int32_t exclude_seen) {
+  Rows r;
+  const auto own = [&](int64_t n_items) { return metrics_args_error(q.n, n_items, mt); };
+  const int rc = open_query(m, w, q, exclude_seen, own, &r);
+  if (rc == kNoRows) return summarize(q.n, mt);
+  if (rc) return rc;
+  if (int e = r.dev().TryRankMetrics(r.side, r.ids, q.n, exclude_flag(exclude_seen), nullptr,
+                                     mt.gt_ptr, mt.gt_items, mt.k_list, mt.nk, mt.recall,
+                                     mt.ndcg))
+    return context_status(r.dev(), e);
+  return summarize(q.n, mt);
+}
 
 // The list evaluations: caller lists (cand_ptr given) or sampled ones.
 struct ListEval {
@@ -673,124 +643,174 @@ struct ListEval {
   uint64_t seed;
 };
 
-// Their argument checks on top of evaluate_args_error, before any device
-// call (the fold-in projection is one); "" when fine.
-std::string list_args_error(int64_t n, int64_t n_items, const ListEval& le, bool sampled) {
-  if (sampled) {
-    if (le.n_neg < 0) return "n_neg must not be negative";
-    if (le.n_neg > 0 && n > INT64_MAX / le.n_neg) return "n * n_neg overflows";
-    return "";
-  }
-  if (!le.cand_ptr || le.cand_ptr[0] != 0) return "bad cand_ptr";
-  for (int64_t i = 0; i < n; ++i)
-    if (le.cand_ptr[i + 1] < le.cand_ptr[i]) return "cand_ptr not monotone";
-  if (le.cand_ptr[n] > 0 && !le.cand_items) return "null cand_items";
-  for (int64_t p = 0; p < le.cand_ptr[n]; ++p)
-    if (le.cand_items[p] < 0 || le.cand_items[p] >= n_items)
-      return "candidate id " + std::to_string(le.cand_items[p]) + " out of range";
-  return "";
-}
-
-std::string hist_args_error(int64_t n, int64_t n_items, const int64_t* hist_ptr,
-                            const int32_t* hist_items) {
-  if (n < 0 || !hist_ptr || hist_ptr[0] != 0) return "bad arguments";
-  for (int64_t i = 0; i < n; ++i)
-    if (hist_ptr[i + 1] < hist_ptr[i]) return "hist_ptr not monotone";
-  if (hist_ptr[n] > 0 && !hist_items) return "null hist_items";
-  for (int64_t p = 0; p < hist_ptr[n]; ++p)
-    if (hist_items[p] < 0 || hist_items[p] >= n_items)
-      return "item id " + std::to_string(hist_items[p]) + " out of range";
-  return "";
-}
-
-// users != nullptr: trained users (USER side); else the n histories are
-// projected into the EVAL side first.
-int evaluate_lists(frecsys_model* m, const std::string& w, const int64_t* users,
-                   const int64_t* hist_ptr, const int32_t* hist_items, bool fold_in, int64_t n,
-                   const ListEval& le, bool sampled, const int64_t* gt_ptr,
-                   const int32_t* gt_items, const int32_t* k_list, int32_t nk,
-                   const float* alpha_list, int32_t na, int32_t exclude_seen,
-                   const uint8_t* item_mask, float* recall, float* ndcg, float* summary) {
-  if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  if (exclude_seen && !fold_in)
+int evaluate_lists(frecsys_model* m, const std::string& w, const Query& q, const ListEval& le,
+                   bool sampled, const Metrics& mt, int32_t exclude_seen,
+                   const uint8_t* item_mask) {
+  // the two list evaluations name themselves together where they need the
+  // tuples: checked here, not by open_query under the name in `w`
+  if (m && exclude_seen && !q.fold_in)
     if (int rc = needs_data(m, "frecsys_model_evaluate_candidates / _sampled")) return rc;
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  frecsys::DeviceContext& dev = dm->device();
-  const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
-  std::string e = fold_in ? hist_args_error(n, n_items, hist_ptr, hist_items) : "";
-  if (e.empty())
-    e = evaluate_args_error(n, n_items, gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg);
-  if (e.empty()) e = list_args_error(n, n_items, le, sampled);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
-  if (n == 0) return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
-  int side = FRECSYS_SIDE_USER;
-  if (fold_in) {
-    frecsys::Csr csr;
-    csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-    csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-    dm->FoldIn(csr);
-    side = FRECSYS_SIDE_EVAL;
-  }
-  const int flags = exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0;
-  const int rc =
-      sampled ? dev.TrySampledMetrics(side, users, n, flags, item_mask, gt_ptr, gt_items, le.n_neg,
-                                      le.seed, k_list, nk, recall, ndcg)
-              : dev.TryRankCandidatesMetrics(side, users, n, le.cand_ptr, le.cand_items, flags,
-                                             item_mask, gt_ptr, gt_items, k_list, nk, recall, ndcg);
-  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
-  return summarize(n, k_list, nk, alpha_list, na, recall, ndcg, summary);
+  Rows r;
+  const auto own = [&](int64_t n_items) -> std::string {
+    const std::string e = metrics_args_error(q.n, n_items, mt);
+    if (!e.empty()) return e;
+    if (!sampled) return cand_args_error(q.n, n_items, le.cand_ptr, le.cand_items);
+    if (le.n_neg < 0) return "n_neg must not be negative";
+    if (le.n_neg > 0 && q.n > INT64_MAX / le.n_neg) return "n * n_neg overflows";
+    return "";
+  };
+  const int rc = open_query(m, w, q, /*reads_training=*/0, own, &r);
+  if (rc == kNoRows || (rc == FRECSYS_OK && q.n == 0)) return summarize(q.n, mt);
+  if (rc) return rc;
+  const int flags = exclude_flag(exclude_seen);
+  const int e =
+      sampled ? r.dev().TrySampledMetrics(r.side, r.ids, q.n, flags, item_mask, mt.gt_ptr,
+                                          mt.gt_items, le.n_neg, le.seed, mt.k_list, mt.nk,
+                                          mt.recall, mt.ndcg)
+              : r.dev().TryRankCandidatesMetrics(r.side, r.ids, q.n, le.cand_ptr, le.cand_items,
+                                                 flags, item_mask, mt.gt_ptr, mt.gt_items,
+                                                 mt.k_list, mt.nk, mt.recall, mt.ndcg);
+  if (e) return context_status(r.dev(), e);
+  return summarize(q.n, mt);
 }
 
-// frecsys_model_evaluate_ranks and its fold-in form (users != nullptr: trained
-// users).  The summary is summarize()'s with one column: mrr in recall's
-// place, auc in ndcg's.
-int evaluate_ranks(frecsys_model* m, const std::string& w, const int64_t* users,
-                   const int64_t* hist_ptr, const int32_t* hist_items, bool fold_in, int64_t n,
-                   const int64_t* gt_ptr, const int32_t* gt_items, const float* alpha_list,
-                   int32_t na, int32_t exclude_seen, const uint8_t* item_mask, int32_t* rank,
+// The summary is summarize()'s with one column: mrr in recall's place, auc in
+// ndcg's.
+int evaluate_ranks(frecsys_model* m, const std::string& w, const Query& q, const int64_t* gt_ptr,
+                   const int32_t* gt_items, const float* alpha_list, int32_t na,
+                   int32_t exclude_seen, const uint8_t* item_mask, int32_t* rank,
                    int32_t* eligible, float* mrr, float* auc, float* summary) {
-  if (!m || (!fold_in && n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  if (exclude_seen && !fold_in)
-    if (int rc = needs_data(m, "frecsys_model_evaluate_ranks")) return rc;
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  frecsys::DeviceContext& dev = dm->device();
-  const int64_t n_items = dev.rows(frecsys::DeviceContext::ITEM);
   const int32_t one = 1;  // summarize()'s one column
-  std::string e = fold_in ? hist_args_error(n, n_items, hist_ptr, hist_items) : "";
-  if (e.empty()) e = truth_head_error(n, gt_ptr);
-  if (e.empty()) e = alpha_error(alpha_list, na);
-  if (e.empty() && n > 0 && !gt_items) e = "null gt_items";
-  if (e.empty() && n > 0 && !rank && !eligible && !mrr && !auc) e = "null outputs";
-  if (e.empty() && summary && n > 0 && (!mrr || !auc)) e = "summary needs mrr and auc";
-  if (e.empty()) e = truth_rows_error(n, n_items, gt_ptr, gt_items);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
-  if (n == 0) return summarize(n, &one, 1, alpha_list, na, mrr, auc, summary);
-  int side = FRECSYS_SIDE_USER;
-  if (fold_in) {
-    frecsys::Csr csr;
-    csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-    csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-    dm->FoldIn(csr);
-    side = FRECSYS_SIDE_EVAL;
-  }
-  const int rc = dev.TryRankPositions(side, users, n, exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0,
-                                      item_mask, gt_ptr, gt_items, rank, eligible, mrr, auc);
-  if (rc) return model_fail(rc, frecsys_last_error(dev.raw()));
-  return summarize(n, &one, 1, alpha_list, na, mrr, auc, summary);
+  Rows r;
+  const auto own = [&](int64_t n_items) -> std::string {
+    std::string e = truth_head_error(q.n, gt_ptr);
+    if (e.empty()) e = alpha_error(alpha_list, na);
+    if (!e.empty()) return e;
+    if (q.n > 0 && !gt_items) return "null gt_items";
+    if (q.n > 0 && !rank && !eligible && !mrr && !auc) return "null outputs";
+    if (summary && q.n > 0 && (!mrr || !auc)) return "summary needs mrr and auc";
+    return truth_rows_error(q.n, n_items, gt_ptr, gt_items);
+  };
+  const int rc = open_query(m, w, q, exclude_seen, own, &r);
+  if (rc == kNoRows || (rc == FRECSYS_OK && q.n == 0))
+    return summarize(q.n, &one, 1, alpha_list, na, mrr, auc, summary);
+  if (rc) return rc;
+  if (int e = r.dev().TryRankPositions(r.side, r.ids, q.n, exclude_flag(exclude_seen), item_mask,
+                                       gt_ptr, gt_items, rank, eligible, mrr, auc))
+    return context_status(r.dev(), e);
+  return summarize(q.n, &one, 1, alpha_list, na, mrr, auc, summary);
+}
+
+int model_similar(frecsys_model* m, const char* what, int side, const int64_t* rows, int64_t n,
+                  int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
+  if (!m || n < 0 || (n > 0 && !ids))
+    return model_fail(FRECSYS_ERR_INVALID, std::string(what) + ": bad arguments");
+  DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  return context_status(dev, dev.TrySimilar(side, rows, n, k, flags, mask, ids, scores));
 }
 
 }  // namespace
 
 extern "C" {
 
+int frecsys_model_recommend(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                            int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                            float* scores) {
+  return recommend(m, "frecsys_model_recommend: ", trained(users, n), k, exclude_seen, item_mask,
+                   items, scores);
+}
+
+int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                    const int32_t* hist_items, int64_t n, int32_t k,
+                                    int32_t exclude_seen, const uint8_t* item_mask,
+                                    int32_t* items, float* scores) {
+  return recommend(m, "frecsys_model_recommend_fold_in: ", unseen(hist_ptr, hist_items, n), k,
+                   exclude_seen, item_mask, items, scores);
+}
+
+int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
+                        float* scores) {
+  if (!m || n < 0 || (n > 0 && (!users || !items || !scores)))
+    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_score: bad arguments");
+  DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  return context_status(dev, dev.TryScorePairs(FRECSYS_SIDE_USER, users, items, n, scores));
+}
+
+int frecsys_model_explain(frecsys_model* m, const int64_t* users, int64_t n,
+                          const int64_t* tgt_ptr, const int32_t* tgt_items, int32_t top,
+                          float* score, int32_t* top_items, float* top_contrib, float* full) {
+  return explain(m, "frecsys_model_explain: ", trained(users, n), tgt_ptr, tgt_items, top, score,
+                 top_items, top_contrib, full);
+}
+
+int frecsys_model_explain_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                  const int32_t* hist_items, int64_t n, const int64_t* tgt_ptr,
+                                  const int32_t* tgt_items, int32_t top, float* score,
+                                  int32_t* top_items, float* top_contrib, float* full) {
+  return explain(m, "frecsys_model_explain_fold_in: ", unseen(hist_ptr, hist_items, n), tgt_ptr,
+                 tgt_items, top, score, top_items, top_contrib, full);
+}
+
+int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_t n,
+                                  const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
+                                  int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                                  float* scores) {
+  return rank_candidates(m, "frecsys_model_rank_candidates: ", trained(users, n), cand_ptr,
+                         cand_items, k, exclude_seen, item_mask, items, scores);
+}
+
+int frecsys_model_rank_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                          const int32_t* hist_items, int64_t n,
+                                          const int64_t* cand_ptr, const int32_t* cand_items,
+                                          int32_t k, int32_t exclude_seen,
+                                          const uint8_t* item_mask, int32_t* items,
+                                          float* scores) {
+  return rank_candidates(m, "frecsys_model_rank_candidates_fold_in: ",
+                         unseen(hist_ptr, hist_items, n), cand_ptr, cand_items, k, exclude_seen,
+                         item_mask, items, scores);
+}
+
+int frecsys_model_similar_items(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* item_mask, int32_t* ids,
+                                float* scores) {
+  return model_similar(m, "frecsys_model_similar_items", FRECSYS_SIDE_ITEM, items, n, k, flags,
+                       item_mask, ids, scores);
+}
+
+int frecsys_model_similar_users(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                int32_t flags, const uint8_t* user_mask, int32_t* ids,
+                                float* scores) {
+  return model_similar(m, "frecsys_model_similar_users", FRECSYS_SIDE_USER, users, n, k, flags,
+                       user_mask, ids, scores);
+}
+
+int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
+                           const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list,
+                           int32_t nk, const float* alpha_list, int32_t na, int32_t exclude_seen,
+                           float* recall, float* ndcg, float* summary) {
+  return evaluate(m, "frecsys_model_evaluate: ", trained(users, n),
+                  Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg, summary},
+                  exclude_seen);
+}
+
+int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                   const int32_t* hist_items, int64_t n, const int64_t* gt_ptr,
+                                   const int32_t* gt_items, const int32_t* k_list, int32_t nk,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   float* recall, float* ndcg, float* summary) {
+  return evaluate(m, "frecsys_model_evaluate_fold_in: ", unseen(hist_ptr, hist_items, n),
+                  Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg, summary},
+                  exclude_seen);
+}
+
 int frecsys_model_evaluate_ranks(frecsys_model* m, const int64_t* users, int64_t n,
                                  const int64_t* gt_ptr, const int32_t* gt_items,
                                  const float* alpha_list, int32_t na, int32_t exclude_seen,
                                  const uint8_t* item_mask, int32_t* rank, int32_t* eligible,
                                  float* mrr, float* auc, float* summary) {
-  return evaluate_ranks(m, "frecsys_model_evaluate_ranks: ", users, nullptr, nullptr, false, n,
-                        gt_ptr, gt_items, alpha_list, na, exclude_seen, item_mask, rank, eligible,
-                        mrr, auc, summary);
+  return evaluate_ranks(m, "frecsys_model_evaluate_ranks: ", trained(users, n), gt_ptr, gt_items,
+                        alpha_list, na, exclude_seen, item_mask, rank, eligible, mrr, auc,
+                        summary);
 }
 
 int frecsys_model_evaluate_ranks_fold_in(frecsys_model* m, const int64_t* hist_ptr,
@@ -800,9 +820,9 @@ int frecsys_model_evaluate_ranks_fold_in(frecsys_model* m, const int64_t* hist_p
                                          int32_t exclude_seen, const uint8_t* item_mask,
                                          int32_t* rank, int32_t* eligible, float* mrr,
                                          float* auc, float* summary) {
-  return evaluate_ranks(m, "frecsys_model_evaluate_ranks_fold_in: ", nullptr, hist_ptr, hist_items,
-                        true, n, gt_ptr, gt_items, alpha_list, na, exclude_seen, item_mask, rank,
-                        eligible, mrr, auc, summary);
+  return evaluate_ranks(m, "frecsys_model_evaluate_ranks_fold_in: ",
+                        unseen(hist_ptr, hist_items, n), gt_ptr, gt_items, alpha_list, na,
+                        exclude_seen, item_mask, rank, eligible, mrr, auc, summary);
 }
 
 int frecsys_model_evaluate_candidates(frecsys_model* m, const int64_t* users, int64_t n,
@@ -811,9 +831,11 @@ int frecsys_model_evaluate_candidates(frecsys_model* m, const int64_t* users, in
                                       const int32_t* k_list, int32_t nk, const float* alpha_list,
                                       int32_t na, int32_t exclude_seen, const uint8_t* item_mask,
                                       float* recall, float* ndcg, float* summary) {
-  return evaluate_lists(m, "frecsys_model_evaluate_candidates: ", users, nullptr, nullptr, false, n,
-                        ListEval{cand_ptr, cand_items, 0, 0}, false, gt_ptr, gt_items, k_list, nk,
-                        alpha_list, na, exclude_seen, item_mask, recall, ndcg, summary);
+  return evaluate_lists(m, "frecsys_model_evaluate_candidates: ", trained(users, n),
+                        ListEval{cand_ptr, cand_items, 0, 0}, false,
+                        Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg,
+                                summary},
+                        exclude_seen, item_mask);
 }
 
 int frecsys_model_evaluate_candidates_fold_in(frecsys_model* m, const int64_t* hist_ptr,
@@ -824,10 +846,12 @@ int frecsys_model_evaluate_candidates_fold_in(frecsys_model* m, const int64_t* h
                                               const float* alpha_list, int32_t na,
                                               int32_t exclude_seen, const uint8_t* item_mask,
                                               float* recall, float* ndcg, float* summary) {
-  return evaluate_lists(m, "frecsys_model_evaluate_candidates_fold_in: ", nullptr, hist_ptr,
-                        hist_items, true, n, ListEval{cand_ptr, cand_items, 0, 0}, false, gt_ptr,
-                        gt_items, k_list, nk, alpha_list, na, exclude_seen, item_mask, recall, ndcg,
-                        summary);
+  return evaluate_lists(m, "frecsys_model_evaluate_candidates_fold_in: ",
+                        unseen(hist_ptr, hist_items, n), ListEval{cand_ptr, cand_items, 0, 0},
+                        false,
+                        Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg,
+                                summary},
+                        exclude_seen, item_mask);
 }
 
 int frecsys_model_evaluate_sampled(frecsys_model* m, const int64_t* users, int64_t n,
@@ -836,9 +860,11 @@ int frecsys_model_evaluate_sampled(frecsys_model* m, const int64_t* users, int64
                                    const float* alpha_list, int32_t na, int32_t exclude_seen,
                                    const uint8_t* item_mask, float* recall, float* ndcg,
                                    float* summary) {
-  return evaluate_lists(m, "frecsys_model_evaluate_sampled: ", users, nullptr, nullptr, false, n,
-                        ListEval{nullptr, nullptr, n_neg, seed}, true, gt_ptr, gt_items, k_list, nk,
-                        alpha_list, na, exclude_seen, item_mask, recall, ndcg, summary);
+  return evaluate_lists(m, "frecsys_model_evaluate_sampled: ", trained(users, n),
+                        ListEval{nullptr, nullptr, n_neg, seed}, true,
+                        Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg,
+                                summary},
+                        exclude_seen, item_mask);
 }
 
 int frecsys_model_evaluate_sampled_fold_in(frecsys_model* m, const int64_t* hist_ptr,
@@ -848,92 +874,20 @@ int frecsys_model_evaluate_sampled_fold_in(frecsys_model* m, const int64_t* hist
                                            int32_t nk, const float* alpha_list, int32_t na,
                                            int32_t exclude_seen, const uint8_t* item_mask,
                                            float* recall, float* ndcg, float* summary) {
-  return evaluate_lists(m, "frecsys_model_evaluate_sampled_fold_in: ", nullptr, hist_ptr,
-                        hist_items, true, n, ListEval{nullptr, nullptr, n_neg, seed}, true, gt_ptr,
-                        gt_items, k_list, nk, alpha_list, na, exclude_seen, item_mask, recall, ndcg,
-                        summary);
-}
-
-int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
-                           const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list,
-                           int32_t nk, const float* alpha_list, int32_t na, int32_t exclude_seen,
-                           float* recall, float* ndcg, float* summary) {
-  if (!m || (n > 0 && !users))
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate: bad arguments");
-  if (exclude_seen)
-    if (int rc = needs_data(m, "frecsys_model_evaluate")) return rc;
-  frecsys::DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
-  const std::string e =
-      evaluate_args_error(n, dev.rows(frecsys::DeviceContext::ITEM), gt_ptr, gt_items, k_list, nk,
-                          alpha_list, na, recall, ndcg);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate: " + e);
-  return evaluate_rows(dev, FRECSYS_SIDE_USER, users, n, exclude_seen, gt_ptr, gt_items, k_list,
-                       nk, alpha_list, na, recall, ndcg, summary);
-}
-
-int frecsys_model_evaluate_fold_in(frecsys_model* m, const int64_t* hist_ptr,
-                                   const int32_t* hist_items, int64_t n, const int64_t* gt_ptr,
-                                   const int32_t* gt_items, const int32_t* k_list, int32_t nk,
-                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
-                                   float* recall, float* ndcg, float* summary) {
-  if (!m || n < 0 || !hist_ptr || hist_ptr[0] != 0)
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: bad arguments");
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int64_t n_items = dm->device().rows(frecsys::DeviceContext::ITEM);
-  // checked here: the C++ layer treats a bad EVAL CSR as fatal
-  for (int64_t i = 0; i < n; ++i)
-    if (hist_ptr[i + 1] < hist_ptr[i])
-      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: hist_ptr not monotone");
-  if (hist_ptr[n] > 0 && !hist_items)
-    return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: null hist_items");
-  for (int64_t p = 0; p < hist_ptr[n]; ++p)
-    if (hist_items[p] < 0 || hist_items[p] >= n_items)
-      return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: item id " +
-                                                 std::to_string(hist_items[p]) + " out of range");
-  const std::string e = evaluate_args_error(n, n_items, gt_ptr, gt_items, k_list, nk, alpha_list,
-                                            na, recall, ndcg);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, "frecsys_model_evaluate_fold_in: " + e);
-  if (n == 0) return FRECSYS_OK;
-  frecsys::Csr csr;
-  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-  dm->FoldIn(csr);
-  return evaluate_rows(dm->device(), FRECSYS_SIDE_EVAL, nullptr, n, exclude_seen, gt_ptr, gt_items,
-                       k_list, nk, alpha_list, na, recall, ndcg, summary);
-}
-
-// The cases the MMR calls reject (frecsys_hip.h), for the fold-in call to
-// report before it projects anything; "" when fine.
-static std::string diverse_args_error(int32_t k, int32_t pool, float lam, int32_t raw_scores,
-                                      int64_t n, const int32_t* items, const float* scores) {
-  if (pool < 1 || pool > 1024) return "pool must be in [1, 1024]";
-  if (k < 1 || k > pool) return "k must be in [1, pool]";
-  if (!(lam >= 0.0f && lam <= 1.0f)) return "lam must be in [0, 1]";
-  if (raw_scores != 0 && raw_scores != 1) return "raw_scores must be 0 or 1";
-  if (n > 0 && (!items || !scores)) return "null outputs";
-  return "";
-}
-
-static int32_t diverse_flags(int32_t exclude_seen, int32_t raw_scores) {
-  return (exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0) |
-         (raw_scores ? FRECSYS_DIV_RAW_SCORES : 0);
+  return evaluate_lists(m, "frecsys_model_evaluate_sampled_fold_in: ",
+                        unseen(hist_ptr, hist_items, n), ListEval{nullptr, nullptr, n_neg, seed},
+                        true,
+                        Metrics{gt_ptr, gt_items, k_list, nk, alpha_list, na, recall, ndcg,
+                                summary},
+                        exclude_seen, item_mask);
 }
 
 int frecsys_model_recommend_diverse(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
                                     int32_t pool, float lam, int32_t raw_scores,
                                     int32_t exclude_seen, const uint8_t* item_mask,
                                     int32_t* items, float* scores, float* mmr) {
-  const std::string w = "frecsys_model_recommend_diverse: ";
-  if (!m || n < 0 || (n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  const std::string e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
-  if (exclude_seen)
-    if (int rc = needs_data(m, "frecsys_model_recommend_diverse")) return rc;
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int rc = dm->RecommendDiverse(FRECSYS_SIDE_USER, users, n, k, pool, lam,
-                                      diverse_flags(exclude_seen, raw_scores), item_mask, items,
-                                      scores, mmr);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+  return recommend_diverse(m, "frecsys_model_recommend_diverse: ", trained(users, n), k, pool, lam,
+                           raw_scores, exclude_seen, item_mask, items, scores, mmr);
 }
 
 int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* hist_ptr,
@@ -941,23 +895,9 @@ int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* his
                                             int32_t pool, float lam, int32_t raw_scores,
                                             int32_t exclude_seen, const uint8_t* item_mask,
                                             int32_t* items, float* scores, float* mmr) {
-  const std::string w = "frecsys_model_recommend_diverse_fold_in: ";
-  if (!m) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
-  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  // checked here: the C++ layer treats a bad EVAL CSR as fatal
-  std::string e = hist_args_error(n, dm->device().rows(frecsys::DeviceContext::ITEM), hist_ptr,
-                                  hist_items);
-  if (e.empty()) e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
-  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
-  if (n == 0) return FRECSYS_OK;
-  frecsys::Csr csr;
-  csr.ptr.assign(hist_ptr, hist_ptr + n + 1);
-  csr.col.assign(hist_items, hist_items + hist_ptr[n]);
-  dm->FoldIn(csr);
-  const int rc = dm->RecommendDiverse(FRECSYS_SIDE_EVAL, nullptr, n, k, pool, lam,
-                                      diverse_flags(exclude_seen, raw_scores), item_mask, items,
-                                      scores, mmr);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+  return recommend_diverse(m, "frecsys_model_recommend_diverse_fold_in: ",
+                           unseen(hist_ptr, hist_items, n), k, pool, lam, raw_scores, exclude_seen,
+                           item_mask, items, scores, mmr);
 }
 
 int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float* list_scores,
@@ -969,9 +909,9 @@ int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float*
   const std::string e = diverse_args_error(k, pool, lam, raw_scores, n, items, scores);
   if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
   frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
-  const int rc = dm->Diversify(lists, list_scores, n, pool, k, lam, diverse_flags(0, raw_scores),
-                               items, scores, mmr);
-  return rc ? model_fail(rc, frecsys_last_error(dm->device().raw())) : FRECSYS_OK;
+  return context_status(dm->device(), dm->Diversify(lists, list_scores, n, pool, k, lam,
+                                                    diverse_flags(0, raw_scores), items, scores,
+                                                    mmr));
 }
 
 void frecsys_model_destroy(frecsys_model* m) { delete m; }
