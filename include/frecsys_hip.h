@@ -812,6 +812,112 @@ int frecsys_diversify(frecsys_ctx* ctx, const int32_t* lists, const float* list_
 int frecsys_recommend_diverse(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                               int32_t k, int32_t pool, float lam, int32_t flags,
                               const uint8_t* item_mask, int32_t* items, float* scores, float* mmr);
+/* ---- list quality: intra-list diversity, novelty, item exposure ----
+ * What a serving configuration buys beside Recall / NDCG (no reference
+ * counterpart): how varied each list is, how far down the popularity tail it
+ * reaches, and how evenly the catalogue is exposed.  Four calls share the
+ * definitions, which are stated here in full.
+ *   Lists.  A row has list_k slots of item ids.  A negative id is an empty slot;
+ * a repeated id is a slot of its own.  Cut-offs are k_list[q], 1 <= nk <= 32,
+ * 1 <= k_list[q] <= min(1024, list_k), any order, repeats allowed.  For cut-off
+ * K the filled slots are the non-negative ids among positions j < K: n of them,
+ * in list order b = 0 .. n-1.
+ *   ILD@K = 1 - the mean pairwise cosine of the filled slots by item factors,
+ * all in float64: n2_b = sum_c y_bc^2 over the item row converted to double;
+ * inv_b = n2_b > 0 ? 1 / sqrt(n2_b) : 0 (a zero row has cosine 0 with
+ * everything, as for the MMR calls); yh_b = inv_b y_b; s_b = sum_{a<b} yh_a;
+ * T_b = yh_b . s_b; C(K) = sum_{b<n} T_b; ild = n >= 2 ? (float)(1 - C /
+ * (n (n - 1) / 2)) : 0.0f.  The running sum makes every cut-off one O(K d)
+ * sweep; no K x K Gramian is formed.  The result is not clamped: a list of one
+ * item repeated gives about +-1e-16, not exactly 0.
+ *   Novelty@K = n >= 1 ? (float)(sum_{b<n} (double)item_weight[id_b] / n) :
+ * 0.0f, with item_weight a host fp32 [n_items] array of the caller's (self
+ * information -log2 of the item's popularity is the usual choice; the library
+ * sums weights and takes no logarithm).  item_weight NULL: no novelty, and the
+ * novelty output must be NULL too.
+ *   Exposure.  exposure[q * n_items + i], int64: the filled slots with id i
+ * among positions < k_list[q], summed over the rows of the call.  Integers, so
+ * exact and independent of any order.
+ *   Outputs.  ild, novelty: host [n * nk]; exposure: host [nk * n_items]; each
+ * may be NULL, not all.
+ *   What is bit-stable.  Exposure is exact integers, and the summary below is
+ * one host function of them for every caller: device and host agree bit for
+ * bit.  The device fixes the reduction order of ILD and
+ * novelty by the padded dim and the list alone: a row's output bytes do not
+ * depend on the batch, the item splits, the sub-batch, FRECSYS_RECOMMEND_WS_MB,
+ * FRECSYS_RECOMMEND_SPLITS, the other rows or the order of the rows.  Device
+ * against host ILD and novelty satisfy |a - b| <= 2^-23 max(1, |b|): every sum
+ * is float64, reordering moves it by about (K + Dp) 2^-52, and what remains is
+ * the final rounding to fp32 on each side, half an ulp each.
+ *   FRECSYS_ERR_INVALID, before any device call and any write: k_list null or
+ * nk outside [1, 32], a cut-off out of range, every output null, novelty
+ * without item_weight or item_weight without novelty, a non-finite weight, a
+ * negative row count, n * list_k beyond int64, an id >= n_items in any slot of
+ * caller lists (the slots past the largest cut-off included).  Zero rows return
+ * FRECSYS_OK and touch nothing but a given exposure array, which is zeroed.
+ *
+ * frecsys_list_quality: the definition in scalar C++ on the host -- no context,
+ * no HIP call.  item_table is row-major [n_items][ld] with ld >= dim >= 1 (it
+ * may be NULL when ild is); lists is [n][list_k]. */
+int frecsys_list_quality(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                         const int32_t* lists, int64_t n, int32_t list_k, const int32_t* k_list,
+                         int32_t nk, const float* item_weight, float* ild, float* novelty,
+                         int64_t* exposure);
+/* The summary of one exposure row c[0 .. n_items) on the host.  M = the
+ * eligible items (item_mask byte non-zero; NULL: all), S = sum of c_i over
+ * them.  *coverage = (eligible i with c_i > 0) / M; *gini = sum_{i=1..M}
+ * (2 i - M - 1) c_(i) / (M S) with c_(i) the eligible counts sorted ascending,
+ * the numerator and M S accumulated exactly in 128-bit integers, each converted
+ * to double (exact below 2^53; beyond it a rounding each, so the quotient is
+ * then within 3 * 2^-53 relative of the exact ratio, not its rounding), then one
+ * double division; both 0 when M == 0 or S == 0.  *total = S, *covered = the
+ * count of covered items.  Every output may be NULL.  FRECSYS_ERR_INVALID: a
+ * null array, n_items < 1, a negative count, a sum beyond int64. */
+int frecsys_exposure_summary(const int64_t* exposure, int64_t n_items, const uint8_t* item_mask,
+                             double* coverage, double* gini, int64_t* total, int64_t* covered);
+/* frecsys_list_quality (above) of the lists a serving configuration produces,
+ * without the lists leaving the device.  side, rows, flags and item_mask are
+ * frecsys_recommend's.  pool == 0: the lists are frecsys_recommend(k = max
+ * k_list)'s (lam is ignored, div_flags must be 0).  pool > 0: they are
+ * frecsys_recommend_diverse(k = max k_list, pool, lam, div_flags)'s; div_flags
+ * is 0 or FRECSYS_DIV_RAW_SCORES.  With a ground truth (gt_ptr / gt_items,
+ * row i belongs to query row i; recall and ndcg then both given, host [n_rows *
+ * nk]) Recall / NDCG of the same lists come back too, by frecsys_rank_metrics'
+ * kernel: frecsys_list_metrics of those lists, bitwise.  Without one gt_ptr,
+ * recall and ndcg are all NULL.  Per row batch: the scan, the two MMR kernels
+ * (pool > 0), the metrics kernel (ground truth), then quality_kernel -- one wave
+ * per row closes the filled slots up in LDS and sweeps them once with the next
+ * four item rows in flight, lanes owning columns of the padded dim, one joint
+ * butterfly for (y.y, y.s) per slot -- and exposure_kernel, 64-bit integer
+ * atomics into [nk][n_items] counts that stay on the device across the batches
+ * and are copied to the host once.  Workspace: frecsys_recommend's buffer and
+ * budget (the MMR stage's as for frecsys_recommend_diverse) with 8 nk more bytes
+ * per row of a batch, and outside that budget 4 nk + 4 n_items (weights) +
+ * 8 nk n_items (counts) bytes; released by frecsys_release_workspaces.
+ * FRECSYS_ERR_INVALID: the cases above, then pool outside [1, 1024], max k_list
+ * above pool ("k must be in [1, pool]"), lam outside [0, 1] or NaN, an unknown
+ * flag, recall / ndcg without a ground truth or the reverse, then
+ * frecsys_recommend's and frecsys_rank_metrics' cases.  Timer keys "quality"
+ * and "quality.exposure" (one launch each per row batch) beside "recommend",
+ * "diversify.*" and "rank_metrics"; frecsys_work("quality"), every slot booked
+ * as filled: per row 6 K d flops with ild (two dot products and an axpy per
+ * slot), bytes = K (4 Dp + 4, + 4 with novelty) + 4 nk per output, + 8 K nk
+ * for the exposure's adds. */
+int frecsys_rank_quality(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                         int32_t flags, const uint8_t* item_mask, const int32_t* k_list,
+                         int32_t nk, int32_t pool, float lam, int32_t div_flags,
+                         const float* item_weight, const int64_t* gt_ptr, const int32_t* gt_items,
+                         float* ild, float* novelty, float* recall, float* ndcg,
+                         int64_t* exposure);
+/* The same two kernels on caller lists [n][list_k] (host) against the
+ * context's ITEM table: the lists are uploaded in row batches within the
+ * recommend budget (4 list_k + 8 nk bytes per row, at least one row), as
+ * frecsys_diversify uploads its pools.  No ground truth here:
+ * frecsys_list_metrics takes the same lists on the host.  FRECSYS_ERR_INVALID
+ * also for a null context, list_k < 1, no item embeddings, null lists. */
+int frecsys_lists_quality(frecsys_ctx* ctx, const int32_t* lists, int64_t n, int32_t list_k,
+                          const int32_t* k_list, int32_t nk, const float* item_weight, float* ild,
+                          float* novelty, int64_t* exposure);
 /* Train-loss diagnostics (ComputeLosses / PrintLosses, ials.h:226-305,
  * safer2.h:337-413), all rows of both sides on every rank: observed = sum
  * over every USER-side interaction of (v.u - 1)^2 (per-user fp32 sums,

@@ -146,6 +146,56 @@ int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* his
 int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float* list_scores,
                             int64_t n, int32_t pool, int32_t k, float lam, int32_t raw_scores,
                             int32_t* items, float* scores, float* mmr);
+/* List quality of a serving configuration for trained users
+ * (frecsys_rank_quality, frecsys_hip.h: the definitions of ILD, novelty and
+ * exposure, the tolerance and what is exact are stated there): the lists are
+ * frecsys_model_recommend(k = max k_list)'s when pool == 0 (lam ignored,
+ * raw_scores 0) and frecsys_model_recommend_diverse(k = max k_list, pool, lam,
+ * raw_scores)'s when pool > 0, measured on the device.  ild, novelty: host
+ * [n * nk]; exposure: host int64 [nk * n_items]; item_weight: host [n_items]
+ * with novelty, NULL without.  A ground truth (gt_ptr / gt_items, row i belongs
+ * to users[i]) is optional: with it recall and ndcg [n * nk] are both given and
+ * hold frecsys_model_evaluate's values of the same lists; without it gt_ptr,
+ * gt_items, recall and ndcg are NULL.  summary (or NULL): double
+ * [(6 + 2 na) nk] -- mean ILD [nk] and mean novelty [nk] (double sums of the
+ * per-row values in row order, over n), coverage [nk] and Gini [nk] of each
+ * exposure row among the items of item_mask (frecsys_exposure_summary), then
+ * frecsys_model_evaluate's summary widened: mean recall, mean ndcg, recall
+ * CVaR [na][nk], ndcg CVaR [na][nk]; a block whose output was not asked for
+ * holds 0.  FRECSYS_ERR_INVALID, every check before any device work:
+ * frecsys_rank_quality's cases in this layer's words, raw_scores outside
+ * {0, 1} or without a pool, a bad alpha_list, frecsys_model_evaluate's
+ * ground-truth cases, exclude_seen on a serve-only model. */
+int frecsys_model_evaluate_quality(frecsys_model* m, const int64_t* users, int64_t n,
+                                   const int32_t* k_list, int32_t nk, int32_t pool, float lam,
+                                   int32_t raw_scores, const float* item_weight,
+                                   const int64_t* gt_ptr, const int32_t* gt_items,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   const uint8_t* item_mask, float* ild, float* novelty,
+                                   float* recall, float* ndcg, int64_t* exposure,
+                                   double* summary);
+/* The same for n unseen users given by their histories (CSR), as
+ * frecsys_model_recommend_fold_in: the model's fold-in projection, then the
+ * quality of the projected rows' lists; exclude_seen drops the given history.
+ * A bad argument is reported before anything is projected. */
+int frecsys_model_evaluate_quality_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                           const int32_t* hist_items, int64_t n,
+                                           const int32_t* k_list, int32_t nk, int32_t pool,
+                                           float lam, int32_t raw_scores,
+                                           const float* item_weight, const int64_t* gt_ptr,
+                                           const int32_t* gt_items, const float* alpha_list,
+                                           int32_t na, int32_t exclude_seen,
+                                           const uint8_t* item_mask, float* ild, float* novelty,
+                                           float* recall, float* ndcg, int64_t* exposure,
+                                           double* summary);
+/* The same measures of caller-supplied lists [n * list_k] (negative: an empty
+ * slot) against the model's item table (frecsys_lists_quality; its errors).
+ * item_mask only selects the items of the summary; summary (or NULL): double
+ * [4 nk], the first four blocks above. */
+int frecsys_model_list_quality(frecsys_model* m, const int32_t* lists, int64_t n, int32_t list_k,
+                               const int32_t* k_list, int32_t nk, const float* item_weight,
+                               const uint8_t* item_mask, float* ild, float* novelty,
+                               int64_t* exposure, double* summary);
 /* scores[i] = the model's score of items[i] for trained user users[i] (a row
  * of U), n pairs, any order, repeats allowed; host arrays [n].  Bit for bit
  * the score frecsys_model_recommend lists for that user and item

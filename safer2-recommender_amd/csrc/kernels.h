@@ -557,6 +557,39 @@ struct RankMetricsArgs {
 };
 hipError_t launch_rank_metrics(const RankMetricsArgs& a, hipStream_t s);
 
+// List quality of ranked lists in device memory (quality.hip; the definitions
+// are frecsys_list_quality's in include/frecsys_hip.h).  Row i of the batch has
+// the slots lists[i*list_k .. i*list_k+k) (negative: empty; a repeated id is a
+// slot of its own), each id below the table's rows.  launch_quality writes, per
+// row and cut-off, ILD (float64 running sum over the item rows, ld = Dp) and
+// novelty (the mean of weight[id] over the filled slots) -- either output may
+// be nullptr, not both; launch_exposure adds 1 to counts[q][id] for every
+// filled slot below cut-off q (the caller zeroes counts).
+struct QualityArgs {
+  const float* Y;         // items, ld = Dp (with ild)
+  int Dp;
+  const int32_t* lists;   // [n][list_k]
+  int64_t n;              // rows of this batch
+  int list_k;             // slots per row in memory, >= k
+  int k;                  // slots swept = max k_list, 1 .. kMetricMaxK
+  const int32_t* k_list;  // [nk], each 1 .. k
+  int nk;                 // 1 .. kMetricMaxCutoffs
+  const float* weight;    // [items] (with novelty), or nullptr
+  float* ild;             // [n][nk], or nullptr
+  float* novelty;         // [n][nk], or nullptr
+};
+struct ExposureArgs {
+  const int32_t* lists;   // [n][list_k]
+  int64_t n;
+  int list_k, k;
+  const int32_t* k_list;  // [nk]
+  int nk;
+  int64_t m;              // items
+  unsigned long long* counts;  // [nk][m]
+};
+hipError_t launch_quality(const QualityArgs& a, hipStream_t s);
+hipError_t launch_exposure(const ExposureArgs& a, hipStream_t s);
+
 // Candidate lists of sampled evaluation (sampled.hip): the list of query row
 // i of the batch -- cand[cand_ptr[r0 + i] - cand_base ..), RankCandArgs'
 // layout -- is the row's ground truth gt[gt_ptr[r0 + i] .. gt_ptr[r0 + i + 1])

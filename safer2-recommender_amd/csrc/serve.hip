@@ -2,12 +2,13 @@
 // (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
 // frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
 // frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions,
-// frecsys_explain, frecsys_recommend_diverse, frecsys_diversify, and the
-// host-only frecsys_sample_negatives, frecsys_list_metrics,
-// frecsys_position_metrics, frecsys_metric_cvar, frecsys_mmr_select.  No
-// kernels here: recommend.hip, similar.hip, rerank.hip, sampled.hip,
-// metrics.hip, positions.hip, explain.hip and diversify.hip hold them
-// (kernels.h).
+// frecsys_explain, frecsys_recommend_diverse, frecsys_diversify,
+// frecsys_rank_quality, frecsys_lists_quality, and the host-only
+// frecsys_sample_negatives, frecsys_list_metrics, frecsys_position_metrics,
+// frecsys_metric_cvar, frecsys_mmr_select, frecsys_list_quality,
+// frecsys_exposure_summary.  No kernels here: recommend.hip, similar.hip,
+// rerank.hip, sampled.hip, metrics.hip, positions.hip, explain.hip,
+// diversify.hip and quality.hip hold them (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -31,7 +32,10 @@
 //   pools (diversify): budget / bytes per row (the pool, its Gramian, the
 //     selection), at least one row; recommend_diverse adds the selection to
 //     the scan's bytes per row and forms the Gramians in sub-batches of the
-//     batch, within a budget of their own.
+//     batch, within a budget of their own;
+//   quality (rank_quality): the scan's batches with the two result rows more
+//     per row; caller lists (lists_quality): budget / bytes per row (the list
+//     and the result rows), at least one row.
 // Rows are independent, so the batch size never changes a result.
 //
 // Checks.  Each entry point keeps its own order of checks and its own point
@@ -571,6 +575,7 @@ struct DiversifyStage {
         t.stop();
       }
     }
+    if (!rq.items) return FRECSYS_OK;  // the selection stays on the device (QualityStage reads it)
     HIP_TRY(c, to_host(c, rq.items + r0 * k, da.out_items, (size_t)cnt * k));
     HIP_TRY(c, to_host(c, rq.scores + r0 * k, da.out_scores, (size_t)cnt * k));
     if (rq.mmr) HIP_TRY(c, to_host(c, rq.mmr + r0 * k, da.out_mmr, (size_t)cnt * k));
@@ -593,6 +598,124 @@ struct DiversifyStage {
   }
 };
 
+// What the quality calls add to a ranking: the cut-offs, the item weights of
+// novelty (or nullptr) and where the results go (host; each may be nullptr).
+struct QualityRequest {
+  const int32_t* k_list;
+  int32_t nk;
+  const float* item_weight;
+  float* ild;
+  float* novelty;
+  int64_t* exposure;
+};
+
+// The arguments every quality call checks, in this order: the cut-offs (each in
+// [1, max_k]), the outputs (`others`: the call has outputs beside these three),
+// novelty and its weights (one with the other, every weight finite); "" when
+// fine.  tools/model_capi.cc restates these checks in the model layer's words,
+// in the same order: the two lists stay in step.
+std::string quality_args_error(const QualityRequest& q, int32_t max_k, int64_t n_items,
+                               bool others) {
+  if (!q.k_list || q.nk < 1 || q.nk > kMetricMaxCutoffs)
+    return "k_list must hold 1 to " + std::to_string(kMetricMaxCutoffs) + " cut-offs";
+  for (int32_t i = 0; i < q.nk; ++i)
+    if (q.k_list[i] < 1 || q.k_list[i] > max_k)
+      return "cut-offs must be in [1, " + std::to_string(max_k) + "]";
+  if (!q.ild && !q.novelty && !q.exposure && !others) return "every output is null";
+  if (q.novelty && !q.item_weight) return "novelty needs item_weight";
+  if (q.item_weight && !q.novelty) return "item_weight without a novelty output";
+  if (q.item_weight)
+    for (int64_t j = 0; j < n_items; ++j)
+      if (!std::isfinite(q.item_weight[j]))
+        return "item_weight[" + std::to_string(j) + "] is not finite";
+  return "";
+}
+int32_t max_cutoff(const int32_t* k_list, int32_t nk) {
+  return *std::max_element(k_list, k_list + nk);
+}
+
+// The list quality behind lists of list_k slots that are on the device:
+// quality_kernel writes the ILD / novelty rows of a batch, which go to the
+// host; exposure_kernel adds the batch's filled slots into counts[nk][items],
+// zeroed by upload() and fetched once by finish().  Per row of a batch: the two
+// result rows; per call: the cut-offs, the weights and the counts.
+struct QualityStage {
+  const QualityRequest& rq;
+  const int64_t n, m;
+  const size_t nk;
+  QualityArgs qa{};
+  ExposureArgs ea{};
+
+  QualityStage(const frecsys_ctx* c, const QualityRequest& r, int64_t rows, int k)
+      : rq(r), n(rows), m(c->n[1]), nk((size_t)r.nk) {
+    qa.Y = c->emb[1];
+    qa.Dp = c->Dp;
+    qa.k = ea.k = k;
+    qa.nk = ea.nk = r.nk;
+    ea.m = m;
+  }
+  size_t row_bytes() const { return nk * 8; }
+  void carve_rows(Carver& cv, int64_t nb) {
+    qa.ild = cv.take_if<float>(rq.ild != nullptr, (size_t)nb * nk);
+    qa.novelty = cv.take_if<float>(rq.novelty != nullptr, (size_t)nb * nk);
+  }
+  // outside the per-row budget
+  void carve_inputs(Carver& cv) {
+    qa.k_list = ea.k_list = cv.take<int32_t>(nk);
+    qa.weight = cv.take_if<float>(rq.item_weight != nullptr, (size_t)m);
+    ea.counts = cv.take_if<unsigned long long>(rq.exposure != nullptr, nk * (size_t)m);
+  }
+  int upload(frecsys_ctx* c) {
+    HIP_TRY(c, to_device(c, qa.k_list, rq.k_list, nk));
+    if (qa.weight) HIP_TRY(c, to_device(c, qa.weight, rq.item_weight, (size_t)m));
+    if (ea.counts) HIP_TRY(c, hipMemsetAsync(ea.counts, 0, nk * (size_t)m * 8, c->stream));
+    return FRECSYS_OK;
+  }
+  // rows [r0, r0 + cnt) of the call, their lists at `lists` with list_k slots
+  // a row; the result rows are on their way to the host when it returns (the
+  // caller synchronises)
+  int run(frecsys_ctx* c, const int32_t* lists, int list_k, int64_t r0, int64_t cnt) {
+    if (qa.ild || qa.novelty) {
+      qa.lists = lists;
+      qa.list_k = list_k;
+      qa.n = cnt;
+      ScopedTimer t(c, "quality");
+      HIP_TRY(c, launch_quality(qa, c->stream));
+      t.stop();
+      if (rq.ild) HIP_TRY(c, to_host(c, rq.ild + r0 * nk, qa.ild, (size_t)cnt * nk));
+      if (rq.novelty) HIP_TRY(c, to_host(c, rq.novelty + r0 * nk, qa.novelty, (size_t)cnt * nk));
+    }
+    if (ea.counts) {
+      ea.lists = lists;
+      ea.list_k = list_k;
+      ea.n = cnt;
+      ScopedTimer t(c, "quality.exposure");
+      HIP_TRY(c, launch_exposure(ea, c->stream));
+      t.stop();
+    }
+    return FRECSYS_OK;
+  }
+  // after the last batch: the counts, once per call
+  int finish(frecsys_ctx* c) {
+    if (!ea.counts) return FRECSYS_OK;
+    HIP_TRY(c, to_host(c, reinterpret_cast<unsigned long long*>(rq.exposure), ea.counts,
+                       nk * (size_t)m));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FRECSYS_OK;
+  }
+  // every slot booked as filled.  ILD: per slot two dot products and one axpy
+  // over the logical dim; bytes: the slot's padded item row, its id and its
+  // weight, the result rows; the exposure's adds are booked as 8 bytes each
+  void book(frecsys_ctx* c) const {
+    const double k = qa.k, d = c->dim;
+    add_work(c, "quality", rq.ild ? (double)n * k * 6.0 * d : 0.0,
+             (double)n * (k * ((rq.ild ? c->Dp * 4.0 : 0.0) + 4.0 + (rq.novelty ? 4.0 : 0.0)) +
+                          (double)nk * ((rq.ild ? 4.0 : 0.0) + (rq.novelty ? 4.0 : 0.0))) +
+                 (rq.exposure ? (double)n * k * (double)nk * 8.0 : 0.0),
+             n);
+  }
+};
+
 // The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
 // to the host), frecsys_rank_metrics (mt given: every batch's lists stay on
 // the device and the metric rows go to the host) and frecsys_recommend_diverse
@@ -603,11 +726,12 @@ struct DiversifyStage {
 int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
                    int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
                    int32_t* items, float* scores, const MetricsRequest* mt,
-                   const DiversifyRequest* dv = nullptr) {
+                   const DiversifyRequest* dv = nullptr, const QualityRequest* ql = nullptr) {
   const std::string w = std::string(what) + ": ";
   int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
   if (rc) return rc;
-  if (n_rows < 0 || (n_rows > 0 && (mt   ? (!mt->recall || !mt->ndcg)
+  if (n_rows < 0 || (n_rows > 0 && (ql   ? false  // frecsys_rank_quality checks its own
+                                    : mt ? (!mt->recall || !mt->ndcg)
                                     : dv ? (!dv->items || !dv->scores)
                                          : !items)))
     return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
@@ -619,18 +743,26 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     const std::string e = metric_args_error(n, mt->gt_ptr, mt->gt_items, mt->k_list, mt->nk, m, &mk);
     if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
   }
-  if (n == 0) return FRECSYS_OK;
+  if (n == 0) {
+    if (ql && ql->exposure) std::memset(ql->exposure, 0, sizeof(int64_t) * (size_t)ql->nk * (size_t)m);
+    return FRECSYS_OK;
+  }
   HIP_TRY(c, hipSetDevice(c->device));
+  // the lists the stages behind the scan read: the selection's k slots when
+  // there is one (only a quality call has both dv and mt), else the scan's
+  const int list_k = dv ? dv->k : k;
   const MetricsRequest none{};
-  MetricsStage ms(mt ? *mt : none, n, k);
+  MetricsStage ms(mt ? *mt : none, n, list_k);
   const DiversifyRequest no_dv{};
   DiversifyStage ds(c, dv ? *dv : no_dv, n, k);
+  const QualityRequest no_ql{};
+  QualityStage qs(c, ql ? *ql : no_ql, n, list_k);
   // per row of a batch beside the scan's own: history bits, the two metric
-  // rows, the pool Gramian and the selection
+  // rows, the pool Gramian and the selection, the two quality rows
   const ScanPlan p =
       scan_plan(c, k, m, n,
                 (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8 +
-                    (dv ? DiversifyStage::out_bytes(dv->k) : 0));
+                    (dv ? DiversifyStage::out_bytes(dv->k) : 0) + (ql ? qs.row_bytes() : 0));
   c->rec_splits = p.splits;
   RecommendArgs a = scan_args(c, side, FRECSYS_SIDE_ITEM, k, p.splits, exclude);
   rc = Carver::run(c, [&](Carver& cv) {
@@ -642,11 +774,16 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     // outside the scan's per-row budget: the Gramians of a sub-batch, within a
     // budget of their own
     if (dv) ds.carve_rows(cv, p.nb, workspace_budget());
+    if (ql) {
+      qs.carve_rows(cv, p.nb);
+      qs.carve_inputs(cv);
+    }
   });
   if (rc) return rc;
   const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
   HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
   if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  if (ql && (rc = qs.upload(c))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (int64_t r0 = 0; r0 < n; r0 += p.nb) {  // one timed launch group per row batch
     a.r0 = r0;
@@ -663,7 +800,18 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     } else {
       t.stop();
     }
-    if (mt) {
+    if (ql) {
+      // the selection (when asked), then the metrics (when there is a ground
+      // truth) and the quality of the same lists, where the stage before left them
+      const int32_t* lists = a.out_items;
+      if (dv) {
+        if ((rc = ds.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
+        lists = ds.da.out_items;
+      }
+      if (mt && (rc = ms.run(c, lists, r0, a.n))) return rc;
+      if ((rc = qs.run(c, lists, list_k, r0, a.n))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (mt) {
       if ((rc = ms.run(c, a.out_items, r0, a.n))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else if (dv) {
@@ -679,6 +827,10 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
            ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
   if (mt) ms.book(c);
   if (dv) ds.book(c);
+  if (ql) {
+    if ((rc = qs.finish(c))) return rc;
+    qs.book(c);
+  }
   return FRECSYS_OK;
 }
 
@@ -1004,6 +1156,177 @@ int frecsys_diversify(frecsys_ctx* c, const int32_t* lists, const float* list_sc
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   ds.book(c);
+  return FRECSYS_OK;
+}
+
+int frecsys_rank_quality(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                         int32_t flags, const uint8_t* item_mask, const int32_t* k_list,
+                         int32_t nk, int32_t pool, float lam, int32_t div_flags,
+                         const float* item_weight, const int64_t* gt_ptr, const int32_t* gt_items,
+                         float* ild, float* novelty, float* recall, float* ndcg,
+                         int64_t* exposure) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_quality: null context");
+  const std::string w = "rank_quality: ";
+  const QualityRequest ql{k_list, nk, item_weight, ild, novelty, exposure};
+  std::string e = quality_args_error(ql, kMetricMaxK, c->n[1], recall || ndcg);
+  if (e.empty() && !gt_ptr && (recall || ndcg)) e = "recall / ndcg need a ground truth";
+  if (e.empty() && gt_ptr && (!recall || !ndcg)) e = "a ground truth needs recall and ndcg";
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  const int32_t k = max_cutoff(k_list, nk);  // the list length is the largest cut-off
+  if (pool != 0) {
+    const int rc = check_diversify(c, w, k, pool, lam, div_flags, FRECSYS_DIV_RAW_SCORES);
+    if (rc) return rc;
+  } else if (div_flags != 0) {
+    return fail(c, FRECSYS_ERR_INVALID, w + "div_flags without a pool");
+  }
+  if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
+  const DiversifyRequest dv{k, lam, div_flags, nullptr, nullptr, nullptr};
+  return recommend_impl(c, "rank_quality", side, rows, n_rows, pool ? pool : k, flags, item_mask,
+                        nullptr, nullptr, gt_ptr ? &mt : nullptr, pool ? &dv : nullptr, &ql);
+}
+
+int frecsys_lists_quality(frecsys_ctx* c, const int32_t* lists, int64_t n, int32_t list_k,
+                          const int32_t* k_list, int32_t nk, const float* item_weight, float* ild,
+                          float* novelty, int64_t* exposure) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "lists_quality: null context");
+  const std::string w = "lists_quality: ";
+  if (list_k < 1) return fail(c, FRECSYS_ERR_INVALID, w + "list_k must be positive");
+  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
+  const int64_t m = c->n[1];
+  const QualityRequest ql{k_list, nk, item_weight, ild, novelty, exposure};
+  const std::string e = quality_args_error(ql, std::min<int32_t>(kMetricMaxK, list_k), m, false);
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n > 0 && !lists) return fail(c, FRECSYS_ERR_INVALID, w + "null lists");
+  if (n > INT64_MAX / list_k) return fail(c, FRECSYS_ERR_INVALID, w + "n * list_k overflows");
+  for (int64_t p = 0; p < n * list_k; ++p)
+    if (lists[p] >= m)
+      return fail(c, FRECSYS_ERR_INVALID,
+                  w + "item id " + std::to_string(lists[p]) + " out of range");
+  if (n == 0) {
+    if (exposure) std::memset(exposure, 0, sizeof(int64_t) * (size_t)nk * (size_t)m);
+    return FRECSYS_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  QualityStage qs(c, ql, n, max_cutoff(k_list, nk));
+  // per row of a batch: its list and its result rows; at least one row per batch
+  const size_t per_row = (size_t)list_k * 4 + qs.row_bytes();
+  const int64_t nb =
+      std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(workspace_budget() / per_row)));
+  int32_t* d_lists = nullptr;
+  int rc = Carver::run(c, [&](Carver& cv) {
+    d_lists = cv.take<int32_t>((size_t)nb * list_k);
+    qs.carve_rows(cv, nb);
+    qs.carve_inputs(cv);
+  });
+  if (rc) return rc;
+  if ((rc = qs.upload(c))) return rc;
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {
+    const int64_t cnt = std::min(nb, n - r0);
+    HIP_TRY(c, to_device(c, d_lists, lists + r0 * list_k, (size_t)cnt * list_k));
+    if ((rc = qs.run(c, d_lists, list_k, r0, cnt))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if ((rc = qs.finish(c))) return rc;
+  qs.book(c);
+  return FRECSYS_OK;
+}
+
+int frecsys_list_quality(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                         const int32_t* lists, int64_t n, int32_t list_k, const int32_t* k_list,
+                         int32_t nk, const float* item_weight, float* ild, float* novelty,
+                         int64_t* exposure) {
+  const std::string w = "list_quality: ";
+  if (list_k < 1) return fail(nullptr, FRECSYS_ERR_INVALID, w + "list_k must be positive");
+  if (n_items < 1) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be positive");
+  const QualityRequest ql{k_list, nk, item_weight, ild, novelty, exposure};
+  const std::string e =
+      quality_args_error(ql, std::min<int32_t>(kMetricMaxK, list_k), n_items, false);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  if (ild && (!item_table || dim < 1 || ld < dim))
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, dim < 1, ld < dim)");
+  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n > 0 && !lists) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null lists");
+  if (n > INT64_MAX / list_k)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n * list_k overflows");
+  for (int64_t p = 0; p < n * list_k; ++p)
+    if (lists[p] >= n_items)
+      return fail(nullptr, FRECSYS_ERR_INVALID,
+                  w + "item id " + std::to_string(lists[p]) + " out of range");
+  if (exposure) std::memset(exposure, 0, sizeof(int64_t) * (size_t)nk * (size_t)n_items);
+  const int32_t mk = max_cutoff(k_list, nk);
+  // C and the weight sum after every filled slot count 0 .. mk, then per cut-off
+  std::vector<double> s(ild ? (size_t)dim : 0), run_c((size_t)mk + 1), run_w((size_t)mk + 1);
+  std::vector<int32_t> filled_below((size_t)mk + 1);  // filled slots among positions < j
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t* list = lists + i * list_k;
+    std::fill(s.begin(), s.end(), 0.0);
+    double C = 0.0, W = 0.0;
+    int32_t b = 0;
+    run_c[0] = run_w[0] = 0.0;
+    for (int32_t j = 0; j < mk; ++j) {
+      filled_below[(size_t)j] = b;
+      const int32_t id = list[j];
+      if (id < 0) continue;
+      if (ild) {
+        const float* y = item_table + (int64_t)id * ld;
+        double n2 = 0.0, ys = 0.0;
+        for (int32_t cc = 0; cc < dim; ++cc) n2 += (double)y[cc] * (double)y[cc];
+        const double inv = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
+        for (int32_t cc = 0; cc < dim; ++cc) ys += (inv * (double)y[cc]) * s[(size_t)cc];
+        C += ys;
+        for (int32_t cc = 0; cc < dim; ++cc) s[(size_t)cc] += inv * (double)y[cc];
+      }
+      if (item_weight) W += (double)item_weight[id];
+      if (exposure)
+        for (int32_t q = 0; q < nk; ++q)
+          if (j < k_list[q]) ++exposure[(int64_t)q * n_items + id];
+      ++b;
+      run_c[(size_t)b] = C;
+      run_w[(size_t)b] = W;
+    }
+    filled_below[(size_t)mk] = b;
+    for (int32_t q = 0; q < nk; ++q) {
+      const int32_t nq = filled_below[(size_t)k_list[q]];
+      if (ild)
+        ild[i * nk + q] =
+            nq >= 2 ? (float)(1.0 - run_c[(size_t)nq] / (double)((int64_t)nq * (nq - 1) / 2))
+                    : 0.0f;
+      if (novelty) novelty[i * nk + q] = nq >= 1 ? (float)(run_w[(size_t)nq] / (double)nq) : 0.0f;
+    }
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_exposure_summary(const int64_t* exposure, int64_t n_items, const uint8_t* item_mask,
+                             double* coverage, double* gini, int64_t* total, int64_t* covered) {
+  const std::string w = "exposure_summary: ";
+  if (!exposure || n_items < 1)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad arguments (null exposure, n_items < 1)");
+  std::vector<int64_t> cs;
+  int64_t S = 0, cov = 0;
+  for (int64_t j = 0; j < n_items; ++j) {
+    if (item_mask && !item_mask[j]) continue;
+    if (exposure[j] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative count");
+    if (exposure[j] > INT64_MAX - S) return fail(nullptr, FRECSYS_ERR_INVALID, w + "counts overflow");
+    cs.push_back(exposure[j]);
+    S += exposure[j];
+    cov += exposure[j] > 0;
+  }
+  const int64_t M = (int64_t)cs.size();
+  double cv = 0.0, g = 0.0;
+  if (M > 0 && S > 0) {
+    std::sort(cs.begin(), cs.end());
+    __int128 num = 0;  // sum over the ascending counts of (2 i - M - 1) c_(i), i = 1 .. M
+    for (int64_t i = 0; i < M; ++i) num += (__int128)(2 * (i + 1) - M - 1) * cs[(size_t)i];
+    cv = (double)cov / (double)M;
+    g = (double)num / (double)((__int128)M * S);
+  }
+  if (coverage) *coverage = cv;
+  if (gini) *gini = g;
+  if (total) *total = S;
+  if (covered) *covered = cov;
   return FRECSYS_OK;
 }
 

@@ -56,7 +56,8 @@ EXPORTS = (
     "frecsys_similar", "frecsys_sample_negatives", "frecsys_rank_candidates_metrics",
     "frecsys_sampled_metrics", "frecsys_position_metrics", "frecsys_rank_positions",
     "frecsys_explain", "frecsys_csr_row_lengths", "frecsys_mmr_select", "frecsys_diversify",
-    "frecsys_recommend_diverse",
+    "frecsys_recommend_diverse", "frecsys_list_quality", "frecsys_exposure_summary",
+    "frecsys_rank_quality", "frecsys_lists_quality",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -75,7 +76,8 @@ MODEL_EXPORTS = (
     "frecsys_model_save", "frecsys_model_load", "frecsys_model_file_info",
     "frecsys_model_epochs", "frecsys_model_explain", "frecsys_model_explain_fold_in",
     "frecsys_model_recommend_diverse", "frecsys_model_recommend_diverse_fold_in",
-    "frecsys_model_diversify",
+    "frecsys_model_diversify", "frecsys_model_evaluate_quality",
+    "frecsys_model_evaluate_quality_fold_in", "frecsys_model_list_quality",
 )
 
 
@@ -224,6 +226,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_diversify": (ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, P, P, P]),
         "frecsys_recommend_diverse": (ctypes.c_int,
                                       [P, I32, P, I64, I32, I32, F, I32, P, P, P, P]),
+        "frecsys_list_quality": (ctypes.c_int, [P, I64, I32, I64, P, I64, I32, P, I32, P, P, P, P]),
+        "frecsys_exposure_summary": (ctypes.c_int, [P, I64, P, P, P, P, P]),
+        "frecsys_rank_quality": (ctypes.c_int, [P, I32, P, I64, I32, P, P, I32, I32, F, I32, P, P,
+                                                P, P, P, P, P, P]),
+        "frecsys_lists_quality": (ctypes.c_int, [P, P, I64, I32, P, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -291,6 +298,14 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_recommend_diverse_fold_in": (
             ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, I32, P, P, P, P]),
         "frecsys_model_diversify": (ctypes.c_int, [P, P, P, I64, I32, I32, F, I32, P, P, P]),
+        "frecsys_model_evaluate_quality": (
+            ctypes.c_int,
+            [P, P, I64, P, I32, I32, F, I32, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
+        "frecsys_model_evaluate_quality_fold_in": (
+            ctypes.c_int,
+            [P, P, P, I64, P, I32, I32, F, I32, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
+        "frecsys_model_list_quality": (ctypes.c_int,
+                                       [P, P, I64, I32, P, I32, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -375,6 +390,71 @@ def list_metrics(lists, gt_ptr, gt_items, k_list) -> Tuple[np.ndarray, np.ndarra
                                   _ptr(ks), len(ks), _ptr(rec), _ptr(ndcg))
     _check_host(lib, rc)
     return rec, ndcg
+
+
+def _quality_args(lists, k_list, item_weight, n_items, exposure):
+    """The arrays of a quality call: lists int32 [n, list_k] (or None), the
+    cut-offs, the weights, and the outputs ild, novelty (None without
+    weights), exposure (None unless asked for)."""
+    ls = None
+    if lists is not None:
+        ls = np.ascontiguousarray(lists, dtype=np.int32)
+        assert ls.ndim == 2, ls.shape
+    ks = np.ascontiguousarray(k_list, dtype=np.int32).reshape(-1)
+    wt = None
+    if item_weight is not None:
+        wt = np.ascontiguousarray(item_weight, dtype=np.float32).reshape(-1)
+        assert wt.shape == (n_items,), (wt.shape, n_items)
+    return ls, ks, wt, (np.zeros((len(ks), n_items), dtype=np.int64) if exposure else None)
+
+
+def _quality_out(n: int, nk: int, wt):
+    ild = np.zeros((n, nk), dtype=np.float32)
+    return ild, (np.zeros_like(ild) if wt is not None else None)
+
+
+def list_quality(item_table, lists, k_list, item_weight=None, exposure: bool = True):
+    """(ild float32 [n, nk], novelty float32 [n, nk] or None, exposure int64
+    [nk, n_items] or None) of ranked lists (int32 [n, list_k]; negative = empty
+    slot) against item_table float32 [n_items, dim] on the host
+    (frecsys_list_quality: the definition Context.rank_quality and
+    Context.lists_quality compute on the GPU; no GPU needed).  ILD@K = 1 - the
+    mean pairwise cosine of the filled slots below K; novelty@K = their mean
+    item_weight (None: no novelty); exposure[q, i] = how often item i is listed
+    below k_list[q]."""
+    lib = load_library()
+    tab = np.asarray(item_table, dtype=np.float32)
+    assert tab.ndim == 2, tab.shape
+    if tab.strides[1] != 4 or tab.strides[0] % 4 or tab.strides[0] < 4 * tab.shape[1]:
+        tab = np.ascontiguousarray(tab)
+    ls, ks, wt, ex = _quality_args(lists, k_list, item_weight, tab.shape[0], exposure)
+    ild, nov = _quality_out(ls.shape[0], len(ks), wt)
+    rc = lib.frecsys_list_quality(_ptr(tab), tab.shape[0], tab.shape[1], tab.strides[0] // 4,
+                                  _ptr(ls), ls.shape[0], ls.shape[1], _ptr(ks), len(ks), _ptr(wt),
+                                  _ptr(ild), _ptr(nov), _ptr(ex))
+    _check_host(lib, rc)
+    return ild, nov, ex
+
+
+def exposure_summary(exposure, item_mask=None) -> dict:
+    """{"coverage", "gini", "total", "covered"} of one exposure row (int64
+    [n_items]) among the items of item_mask (None: all) -- on the host
+    (frecsys_exposure_summary): the share of items listed at least once and
+    the Gini coefficient of the counts, its numerator summed exactly."""
+    lib = load_library()
+    ex = np.ascontiguousarray(exposure, dtype=np.int64).reshape(-1)
+    mk = None
+    if item_mask is not None:
+        mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+        assert mk.shape == ex.shape, (mk.shape, ex.shape)
+    cov, gini = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    total, covered = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib.frecsys_exposure_summary(_ptr(ex), len(ex), _ptr(mk), ctypes.byref(cov),
+                                      ctypes.byref(gini), ctypes.byref(total),
+                                      ctypes.byref(covered))
+    _check_host(lib, rc)
+    return {"coverage": cov.value, "gini": gini.value, "total": int(total.value),
+            "covered": int(covered.value)}
 
 
 def default_pool(k: int) -> int:
@@ -796,6 +876,57 @@ class Context:
                                                DIV_RAW_SCORES if raw_scores else 0, _ptr(items),
                                                _ptr(out), _ptr(mmr)))
         return (items, out, mmr) if return_mmr else (items, out)
+
+    def rank_quality(self, side: int, k_list, rows=None, pool: Optional[int] = None,
+                     lam: float = 0.7, raw_scores: bool = False, item_weight=None, gt=None,
+                     exclude_history: bool = True, item_mask=None, ild: bool = True,
+                     exposure: bool = True) -> dict:
+        """List quality of a serving configuration, computed on the GPU without
+        the lists leaving it (frecsys_rank_quality): a dict of "ild" float32
+        [n, nk], "novelty" float32 [n, nk] (item_weight [n_items] given),
+        "exposure" int64 [nk, n_items], "recall" / "ndcg" float32 [n, nk] (gt =
+        (gt_ptr, gt_items) given) -- None for what was not asked for.  The lists
+        are recommend(side, max(k_list), ...)'s (pool None) or
+        recommend_diverse(side, max(k_list), pool, lam, ...)'s; the values are
+        list_quality's and list_metrics' of those lists (ILD and novelty to the
+        last fp32 bit or the one beside it, the rest exactly)."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        _, ks, wt, ex = _quality_args(None, k_list, item_weight, self.n[SIDE_ITEM], exposure)
+        out_ild, nov = _quality_out(n, len(ks), wt)
+        if not ild:
+            out_ild = None
+        gp = gi = rec = ndcg = None
+        if gt is not None:
+            gp, gi = _ground_truth(*gt)
+            assert len(gp) == n + 1, (len(gp), n)
+            rec = np.zeros((n, len(ks)), dtype=np.float32)
+            ndcg = np.zeros_like(rec)
+        self._check(self.lib.frecsys_rank_quality(
+            self.h, side, _ptr(r), n, REC_EXCLUDE_HISTORY if exclude_history else 0, _ptr(mk),
+            _ptr(ks), len(ks), 0 if pool is None else pool, lam,
+            DIV_RAW_SCORES if raw_scores else 0, _ptr(wt), _ptr(gp), _ptr(gi), _ptr(out_ild),
+            _ptr(nov), _ptr(rec), _ptr(ndcg), _ptr(ex)))
+        return {"ild": out_ild, "novelty": nov, "exposure": ex, "recall": rec, "ndcg": ndcg,
+                "k_list": ks}
+
+    def lists_quality(self, lists, k_list, item_weight=None, ild: bool = True,
+                      exposure: bool = True) -> dict:
+        """The same measures of caller-supplied lists (int32 [n, list_k];
+        negative = empty slot) against the context's item table, on the GPU
+        (frecsys_lists_quality): a dict of "ild", "novelty" and "exposure"."""
+        ls, ks, wt, ex = _quality_args(lists, k_list, item_weight, self.n[SIDE_ITEM], exposure)
+        out_ild, nov = _quality_out(ls.shape[0], len(ks), wt)
+        if not ild:
+            out_ild = None
+        self._check(self.lib.frecsys_lists_quality(self.h, _ptr(ls), ls.shape[0], ls.shape[1],
+                                                   _ptr(ks), len(ks), _ptr(wt), _ptr(out_ild),
+                                                   _ptr(nov), _ptr(ex)))
+        return {"ild": out_ild, "novelty": nov, "exposure": ex, "k_list": ks}
 
     def rank_metrics(self, side: int, k_list, gt_ptr, gt_items, rows=None,
                      exclude_history: bool = True,
@@ -1321,6 +1452,86 @@ class Model:
                                                      ls.shape[1], k, lam, int(bool(raw_scores)),
                                                      _ptr(items), _ptr(out), _ptr(mmr)))
         return (items, out, mmr) if return_mmr else (items, out)
+
+    def item_self_information(self) -> np.ndarray:
+        """float32 [n_items]: -log2(max(h_i, 1) / n_users) with h_i the number
+        of training users of item i (the item side's CSR lengths) -- the usual
+        item_weight of novelty.  Needs the training data on the device: raises
+        on a serve-only model."""
+        h = self.context().csr_row_lengths(SIDE_ITEM, n=self.n_items)
+        return (-np.log2(np.maximum(h, 1).astype(np.float64) / self.n_users)).astype(np.float32)
+
+    @staticmethod
+    def _quality_dict(ks, ild, nov, ex, summary):
+        nk = len(ks)
+        return {"ild": ild, "novelty": nov, "exposure": ex, "k_list": ks,
+                "mean_ild": summary[:nk].copy(),
+                "mean_novelty": summary[nk:2 * nk].copy() if nov is not None else None,
+                "coverage": summary[2 * nk:3 * nk].copy(), "gini": summary[3 * nk:4 * nk].copy()}
+
+    def _evaluate_quality(self, head, n, k_list, pool, lam, gt, item_weight, exclude_seen,
+                          item_mask, alpha_list=EVAL_ALPHA_LIST):
+        mk = self._mask(item_mask)
+        _, ks, wt, ex = _quality_args(None, k_list, item_weight, self.n_items, True)
+        nk = len(ks)
+        ild, nov = _quality_out(n, nk, wt)
+        al = np.ascontiguousarray(alpha_list, dtype=np.float32).reshape(-1)
+        na = len(al)
+        gp = gi = rec = ndcg = None
+        if gt is not None:
+            gp, gi = _ground_truth(*gt)
+            assert len(gp) == n + 1, (len(gp), n)
+            rec = np.zeros((n, nk), dtype=np.float32)
+            ndcg = np.zeros_like(rec)
+        summary = np.zeros((6 + 2 * na) * nk, dtype=np.float64)
+        self._call("evaluate_quality", head, n, _ptr(ks), nk, 0 if pool is None else pool, lam, 0,
+                   _ptr(wt), _ptr(gp), _ptr(gi), _ptr(al), na, int(bool(exclude_seen)), _ptr(mk),
+                   _ptr(ild), _ptr(nov), _ptr(rec), _ptr(ndcg), _ptr(ex), _ptr(summary))
+        out = self._quality_dict(ks, ild, nov, ex, summary)
+        if gt is not None:
+            t = summary[4 * nk:].astype(np.float32)
+            out.update({"recall": rec, "ndcg": ndcg, "alpha_list": al,
+                        "mean_recall": t[:nk].copy(), "mean_ndcg": t[nk:2 * nk].copy(),
+                        "recall_cvar": t[2 * nk:(2 + na) * nk].reshape(na, nk).copy(),
+                        "ndcg_cvar": t[(2 + na) * nk:].reshape(na, nk).copy()})
+        return out
+
+    def evaluate_quality(self, users, k_list, pool: Optional[int] = None, lam: float = 0.7,
+                         gt=None, item_weight=None, exclude_seen: bool = True, item_mask=None):
+        """What a serving configuration buys, for trained users
+        (frecsys_model_evaluate_quality), measured on the GPU: a dict of per-user
+        "ild" and "novelty" (item_weight [n_items] given, e.g.
+        item_self_information()) float32 [n, nk], "exposure" int64 [nk,
+        n_items], and per cut-off "mean_ild", "mean_novelty", "coverage" and
+        "gini" (of the exposure among the items of item_mask).  pool None: the
+        lists are recommend(users, max(k_list))'s; else
+        recommend_diverse(users, max(k_list), pool, lam)'s.  gt = (gt_ptr,
+        gt_items) adds evaluate()'s "recall", "ndcg" and summary of the same
+        lists."""
+        return self._evaluate_quality(*self._head(users), k_list, pool, lam, gt, item_weight,
+                                      exclude_seen, item_mask)
+
+    def evaluate_quality_fold_in(self, hist_ptr, hist_items, k_list, pool: Optional[int] = None,
+                                 lam: float = 0.7, gt=None, item_weight=None,
+                                 exclude_seen: bool = True, item_mask=None):
+        """The same for unseen users given by their histories (CSR), as
+        recommend_fold_in (frecsys_model_evaluate_quality_fold_in)."""
+        return self._evaluate_quality(*self._head(hist=(hist_ptr, hist_items)), k_list, pool, lam,
+                                      gt, item_weight, exclude_seen, item_mask)
+
+    def list_quality(self, lists, k_list, item_weight=None, item_mask=None):
+        """The same measures of caller-supplied lists (int32 [n, list_k];
+        negative = empty slot) against the model's item table
+        (frecsys_model_list_quality); item_mask selects the items of "coverage"
+        and "gini"."""
+        mk = self._mask(item_mask)
+        ls, ks, wt, ex = _quality_args(lists, k_list, item_weight, self.n_items, True)
+        ild, nov = _quality_out(ls.shape[0], len(ks), wt)
+        summary = np.zeros(4 * len(ks), dtype=np.float64)
+        self._check(self.lib.frecsys_model_list_quality(
+            self.h, _ptr(ls), ls.shape[0], ls.shape[1], _ptr(ks), len(ks), _ptr(wt), _ptr(mk),
+            _ptr(ild), _ptr(nov), _ptr(ex), _ptr(summary)))
+        return self._quality_dict(ks, ild, nov, ex, summary)
 
     def _explain(self, head, n, tgt_ptr, tgt_items, top, full):
         tp = np.ascontiguousarray(tgt_ptr, dtype=np.int64).reshape(-1)

@@ -701,6 +701,128 @@ int evaluate_ranks(frecsys_model* m, const std::string& w, const Query& q, const
   return summarize(q.n, &one, 1, alpha_list, na, mrr, auc, summary);
 }
 
+// The arguments and outputs of a list-quality evaluation (frecsys_hip.h).
+struct Quality {
+  const int32_t* k_list;
+  int32_t nk;
+  const float* item_weight;
+  const uint8_t* item_mask;
+  float* ild;
+  float* novelty;
+  int64_t* exposure;
+  double* summary;
+};
+
+// The cases the quality calls reject, before any projection, in this layer's
+// words; max_k: the longest list a cut-off may ask for.  The same checks in the
+// same order as quality_args_error of csrc/serve.hip (32 and 1024 are its
+// kMetricMaxCutoffs and kMetricMaxK, frecsys_hip.h's limits): keep the two in
+// step.  The context runs them again, as it does for every call.
+std::string quality_args_error(const Quality& ql, int32_t max_k, int64_t n_items, bool others) {
+  if (!ql.k_list || ql.nk < 1 || ql.nk > 32) return "k_list must hold 1 to 32 cut-offs";
+  for (int32_t q = 0; q < ql.nk; ++q)
+    if (ql.k_list[q] < 1 || ql.k_list[q] > max_k)
+      return "cut-offs must be in [1, " + std::to_string(max_k) + "]";
+  if (!ql.ild && !ql.novelty && !ql.exposure && !others) return "null outputs";
+  if (ql.novelty && !ql.item_weight) return "novelty needs item_weight";
+  if (ql.item_weight && !ql.novelty) return "item_weight without a novelty output";
+  if (ql.item_weight)
+    for (int64_t j = 0; j < n_items; ++j)
+      if (!std::isfinite(ql.item_weight[j]))
+        return "item_weight[" + std::to_string(j) + "] is not finite";
+  return "";
+}
+
+// summary[0 .. 4 nk): the mean ILD and the mean novelty per cut-off (double sums
+// of the per-row values in row order, over n), then coverage and Gini of each
+// exposure row among the masked items (frecsys_exposure_summary); 0 where the
+// output was not asked for.
+int summarize_quality(int64_t n, int64_t n_items, const Quality& ql) {
+  if (!ql.summary) return FRECSYS_OK;
+  const int32_t nk = ql.nk;
+  std::fill(ql.summary, ql.summary + 4 * (size_t)nk, 0.0);
+  for (int32_t q = 0; q < nk; ++q) {
+    double si = 0.0, sn = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      if (ql.ild) si += (double)ql.ild[i * nk + q];
+      if (ql.novelty) sn += (double)ql.novelty[i * nk + q];
+    }
+    if (n > 0) {
+      ql.summary[q] = si / (double)n;
+      ql.summary[nk + q] = sn / (double)n;
+    }
+    if (ql.exposure)
+      if (int rc = frecsys_exposure_summary(ql.exposure + (int64_t)q * n_items, n_items,
+                                            ql.item_mask, &ql.summary[2 * nk + q],
+                                            &ql.summary[3 * nk + q], nullptr, nullptr))
+        return model_fail(rc, frecsys_last_error(nullptr));
+  }
+  return FRECSYS_OK;
+}
+
+// The Recall / NDCG part of a quality evaluation: absent (gt_ptr null, recall
+// and ndcg null) or whole.
+struct Truth {
+  const int64_t* gt_ptr;
+  const int32_t* gt_items;
+  const float* alpha_list;
+  int32_t na;
+  float* recall;
+  float* ndcg;
+};
+
+// summary[4 nk .. (6 + 2 na) nk): summarize()'s floats, widened; 0 without a
+// ground truth.
+void summarize_truth(int64_t n, const Quality& ql, const Truth& tr) {
+  if (!ql.summary) return;
+  const size_t len = (size_t)(2 + 2 * tr.na) * ql.nk;
+  std::vector<float> tmp(len, 0.0f);
+  if (tr.gt_ptr)
+    summarize(n, ql.k_list, ql.nk, tr.alpha_list, tr.na, tr.recall, tr.ndcg, tmp.data());
+  for (size_t t = 0; t < len; ++t) ql.summary[4 * (size_t)ql.nk + t] = (double)tmp[t];
+}
+
+int evaluate_quality(frecsys_model* m, const std::string& w, const Query& q, const Quality& ql,
+                     int32_t pool, float lam, int32_t raw_scores, const Truth& tr,
+                     int32_t exclude_seen) {
+  Rows r;
+  int64_t items = 0;
+  const auto own = [&](int64_t n_items) -> std::string {
+    items = n_items;
+    std::string e = quality_args_error(ql, 1024, n_items, tr.recall || tr.ndcg);
+    if (!e.empty()) return e;
+    if (pool < 0 || pool > 1024) return "pool must be 0 or in [1, 1024]";
+    if (raw_scores != 0 && raw_scores != 1) return "raw_scores must be 0 or 1";
+    if (pool > 0) {
+      for (int32_t c = 0; c < ql.nk; ++c)
+        if (ql.k_list[c] > pool) return "cut-offs must not exceed pool";
+      if (!(lam >= 0.0f && lam <= 1.0f)) return "lam must be in [0, 1]";
+    } else if (raw_scores) {
+      return "raw_scores without a pool";
+    }
+    if (!(e = alpha_error(tr.alpha_list, tr.na)).empty()) return e;
+    if (!tr.gt_ptr) return tr.recall || tr.ndcg ? "recall / ndcg need a ground truth" : "";
+    if (!tr.recall || !tr.ndcg) return "a ground truth needs recall and ndcg";
+    if (!(e = truth_head_error(q.n, tr.gt_ptr)).empty()) return e;
+    if (q.n > 0 && !tr.gt_items) return "null gt_items";
+    return truth_rows_error(q.n, n_items, tr.gt_ptr, tr.gt_items);
+  };
+  const int rc = open_query(m, w, q, exclude_seen, own, &r);
+  if (rc && rc != kNoRows) return rc;
+  if (rc == kNoRows) {
+    if (ql.exposure) std::fill(ql.exposure, ql.exposure + (int64_t)ql.nk * items, (int64_t)0);
+  } else if (int e = frecsys_rank_quality(
+                 r.dev().raw(), r.side, r.ids, q.n, exclude_flag(exclude_seen), ql.item_mask,
+                 ql.k_list, ql.nk, pool, lam, raw_scores ? FRECSYS_DIV_RAW_SCORES : 0,
+                 ql.item_weight, tr.gt_ptr, tr.gt_items, ql.ild, ql.novelty, tr.recall, tr.ndcg,
+                 ql.exposure)) {
+    return context_status(r.dev(), e);
+  }
+  if (int e = summarize_quality(q.n, items, ql)) return e;
+  summarize_truth(q.n, ql, tr);
+  return FRECSYS_OK;
+}
+
 int model_similar(frecsys_model* m, const char* what, int side, const int64_t* rows, int64_t n,
                   int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids, float* scores) {
   if (!m || n < 0 || (n > 0 && !ids))
@@ -912,6 +1034,57 @@ int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float*
   return context_status(dm->device(), dm->Diversify(lists, list_scores, n, pool, k, lam,
                                                     diverse_flags(0, raw_scores), items, scores,
                                                     mmr));
+}
+
+int frecsys_model_evaluate_quality(frecsys_model* m, const int64_t* users, int64_t n,
+                                   const int32_t* k_list, int32_t nk, int32_t pool, float lam,
+                                   int32_t raw_scores, const float* item_weight,
+                                   const int64_t* gt_ptr, const int32_t* gt_items,
+                                   const float* alpha_list, int32_t na, int32_t exclude_seen,
+                                   const uint8_t* item_mask, float* ild, float* novelty,
+                                   float* recall, float* ndcg, int64_t* exposure,
+                                   double* summary) {
+  return evaluate_quality(m, "frecsys_model_evaluate_quality: ", trained(users, n),
+                          Quality{k_list, nk, item_weight, item_mask, ild, novelty, exposure,
+                                  summary},
+                          pool, lam, raw_scores,
+                          Truth{gt_ptr, gt_items, alpha_list, na, recall, ndcg}, exclude_seen);
+}
+
+int frecsys_model_evaluate_quality_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                           const int32_t* hist_items, int64_t n,
+                                           const int32_t* k_list, int32_t nk, int32_t pool,
+                                           float lam, int32_t raw_scores,
+                                           const float* item_weight, const int64_t* gt_ptr,
+                                           const int32_t* gt_items, const float* alpha_list,
+                                           int32_t na, int32_t exclude_seen,
+                                           const uint8_t* item_mask, float* ild, float* novelty,
+                                           float* recall, float* ndcg, int64_t* exposure,
+                                           double* summary) {
+  return evaluate_quality(m, "frecsys_model_evaluate_quality_fold_in: ",
+                          unseen(hist_ptr, hist_items, n),
+                          Quality{k_list, nk, item_weight, item_mask, ild, novelty, exposure,
+                                  summary},
+                          pool, lam, raw_scores,
+                          Truth{gt_ptr, gt_items, alpha_list, na, recall, ndcg}, exclude_seen);
+}
+
+int frecsys_model_list_quality(frecsys_model* m, const int32_t* lists, int64_t n, int32_t list_k,
+                               const int32_t* k_list, int32_t nk, const float* item_weight,
+                               const uint8_t* item_mask, float* ild, float* novelty,
+                               int64_t* exposure, double* summary) {
+  const std::string w = "frecsys_model_list_quality: ";
+  if (!m || n < 0 || list_k < 1 || (n > 0 && !lists))
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  const int64_t n_items = dev.rows(DeviceContext::ITEM);
+  const Quality ql{k_list, nk, item_weight, item_mask, ild, novelty, exposure, summary};
+  const std::string e = quality_args_error(ql, std::min<int32_t>(1024, list_k), n_items, false);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  if (int rc = frecsys_lists_quality(dev.raw(), lists, n, list_k, k_list, nk, item_weight, ild,
+                                     novelty, exposure))
+    return context_status(dev, rc);
+  return summarize_quality(n, n_items, ql);
 }
 
 void frecsys_model_destroy(frecsys_model* m) { delete m; }
