@@ -812,6 +812,108 @@ int frecsys_diversify(frecsys_ctx* ctx, const int32_t* lists, const float* list_
 int frecsys_recommend_diverse(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                               int32_t k, int32_t pool, float lam, int32_t flags,
                               const uint8_t* item_mask, int32_t* items, float* scores, float* mmr);
+/* Diversified lists by a determinantal point process (DPP): the greedy MAP
+ * of Chen, Zhang and Zhou (NeurIPS 2018) over the same pools (no reference
+ * counterpart).  Where MMR charges a candidate its largest cosine with a
+ * selected item, the DPP charges it the part of it that lies in the span of
+ * all of them: the selection greedily maximises det(L[sel, sel]), L =
+ * diag(sqrt w) S diag(sqrt w), by an incremental Cholesky factorisation in
+ * fp32.  The three calls below share one definition, fixed to the bit;
+ * frecsys_dpp_select is that definition in scalar C++ on the host, and the two
+ * device calls return its bits.
+ *   Pool, relevance, similarity: frecsys_mmr_select's (above), to the bit: the
+ * slots, p, rel_b (FRECSYS_DIV_RAW_SCORES or the min-max normalisation), the
+ * chain g, n2_r, inv_r, and S(a, b) = (g * inv_a) * inv_b + 0.0f.
+ *   Quality.  x_b = theta * rel_b, one fp32 multiply, then fminf(fmaxf(x_b,
+ * -64.0f), 64.0f); w_b = dpp_exp2(x_b):  n = rintf(x) (to nearest, ties to
+ * even), f = x - n (exact), q = c7, then q = fmaf(q, f, c_i) for i = 6 .. 0,
+ * and the result is ldexpf(q, (int)n) (exact).  c_i = ln(2)^i / i! rounded to
+ * fp32:  c0 = 0x1p+0, c1 = 0x1.62e430p-1, c2 = 0x1.ebfbe0p-3, c3 =
+ * 0x1.c6b08ep-5, c4 = 0x1.3b2ab6p-7, c5 = 0x1.5d87fep-10, c6 = 0x1.430912p-13,
+ * c7 = 0x1.ffcbfcp-17.  dpp_exp2 is a definition, not an approximation of
+ * libm: host and device run this sequence.  It is within 1e-6 (relative) of
+ * 2^x on [-64, 64]: the degree-7 remainder at |f| <= 1/2 is 5e-9, the eight
+ * roundings add at most a few ulp.  theta = 0: w = 1 everywhere (pure
+ * diversity); a larger theta moves the list toward the relevance order.
+ *   Greedy selection.  State: r_b = n2_b > 0 ? 1.0f : 0.0f (the residual
+ * variance; a zero item row starts at 0), a factor C with no rows, m = 0 DPP
+ * steps.  For t = 0 .. min(k, p) - 1: E = the unselected filled slots with r_b
+ * >= eps.
+ *   E not empty (a DPP step): v_b = w_b * r_b + 0.0f for b in E; s_t is the
+ * slot of E with the largest word score_key(v_b) << 32 | ~b (the largest v,
+ * ties to the lower slot); gain[t] = v at s_t; delta = sqrtf(r at s_t); for
+ * every unselected filled b other than s_t (inside E or not): acc =
+ * fmaf(C[u][b], C[u][s_t], acc) over u = 0 .. m-1 ascending from +0, e =
+ * (S(s_t, b) - acc) / delta, C[m][b] = e, r_b = fmaf(-e, e, r_b); then m += 1.
+ *   E empty (the fallback): s_t is the lowest unselected filled slot, gain[t]
+ * = 0.0f, and nothing else changes -- every later step is a fallback too.  In
+ * a pool from frecsys_recommend that is score order.  rank(S) <= dim, so the
+ * fallback starts after at most dim selections.
+ *   Every multiply, subtraction, division and sqrt is one correctly rounded
+ * fp32 operation, never contracted; an fma only where fmaf is written.
+ *   Outputs (host), per row and t < k: items[t] = the id of s_t, scores[t] =
+ * its pool score with its bits unchanged, and, unless gain is NULL, gain[t].
+ * For t >= p: -1, -FLT_MAX and -FLT_MAX.
+ * No output bit depends on the batch, the grid, the sub-batch, the workspace
+ * budget, the item splits, the other rows, or where C is kept.
+ * FRECSYS_ERR_INVALID for all three: pool outside [1, 1024], k outside
+ * [1, pool], theta negative or not finite, eps outside (0, 1] or NaN, an
+ * unknown flag bit, a negative row count, null outputs (items, scores) with
+ * rows > 0.  Zero rows return FRECSYS_OK and touch nothing.
+ *
+ * frecsys_dpp_select: host only -- no context, no HIP call.  Arrays as for
+ * frecsys_mmr_select, gain [n][k] or NULL.  Also FRECSYS_ERR_INVALID: a null
+ * table or pool array, an id >= n_items, a non-finite score in a filled slot,
+ * and (without FRECSYS_DIV_RAW_SCORES) a non-finite range. */
+int frecsys_dpp_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
+                       int32_t k, float theta, float eps, int32_t flags, int32_t* items,
+                       float* scores, float* gain);
+/* frecsys_dpp_select (above, to the bit) of caller-supplied pools against the
+ * context's ITEM table; batching as in frecsys_diversify.  Per sub-batch
+ * div_gram_kernel forms the pool Gramians (frecsys_diversify's kernel,
+ * unchanged) and dpp_select_kernel runs the greedy steps, one workgroup of 1, 2
+ * or 4 waves per row (pool <= 256, <= 512, above).
+ * The factor C ([k][pool] fp32 per row) lies in LDS when 4 k pool <= 40 KiB,
+ * else in the workspace; FRECSYS_DPP_FACTOR=ws (read per call, changes no
+ * result bit) keeps it in the workspace at every shape.  Workspace:
+ * frecsys_recommend's buffer and budget; per row of a batch 8 pool + 4 pool^2
+ * + 12 k bytes and, with C in the workspace, 4 k pool more; at least one row
+ * per batch; released by frecsys_release_workspaces.  Rank-local.
+ * FRECSYS_ERR_INVALID, before any device call: the common cases above, a null
+ * context, a null pool array, an id >= items, a non-finite score in a filled
+ * slot, a non-finite range (normalised mode).  Timer keys "diversify.gram"
+ * (shared with the MMR calls) and "dpp.select" (one launch each per
+ * sub-batch); frecsys_work("dpp"): per row pool (pool + 1) d + k (k - 1) pool
+ * flops (the Gramian's triangle, then the factor's chains, sum over t < k of
+ * 2 t pool, every step booked as a DPP step), bytes = 4 pool d + 4 pool^2 (the
+ * item rows read, the Gramian written) + 4 k pool (its rows read) + 8 pool +
+ * 4 k pool (the factor written) + 2 k (k - 1) pool (the factor read) + 8 k
+ * (12 k with gain). */
+int frecsys_diversify_dpp(frecsys_ctx* ctx, const int32_t* lists, const float* list_scores,
+                          int64_t n, int32_t pool, int32_t k, float theta, float eps,
+                          int32_t flags, int32_t* items, float* scores, float* gain);
+/* frecsys_recommend(side, rows, k = pool, flags & FRECSYS_REC_EXCLUDE_HISTORY,
+ * item_mask) followed by frecsys_dpp_select (above, to the bit) on the lists
+ * and scores it returns, with the pools never leaving the device: behind each
+ * row batch's scan the two kernels of frecsys_diversify_dpp run where the scan
+ * left the lists, and only the [rows][k] selection goes to the host.  side is
+ * USER or EVAL; flags is a subset of FRECSYS_REC_EXCLUDE_HISTORY |
+ * FRECSYS_DIV_RAW_SCORES.  At eps = 1 step 0 takes the most relevant slot and
+ * every residual that moved is below eps, so on a table without exactly
+ * orthogonal pairs every later step is a fallback and the result is
+ * frecsys_recommend(k)'s.  Workspace, knobs and rejections are
+ * frecsys_recommend's, with 12 k more bytes per row of a batch, and the common
+ * cases above; the Gramians and factors lie behind the batch regions in
+ * sub-batches within a budget of the same size, as for
+ * frecsys_recommend_diverse.  Like that call it cannot look at the pools
+ * before the device forms them and assumes finite scores and a finite range.
+ * Timer keys "recommend", "diversify.gram", "dpp.select";
+ * frecsys_work("recommend") as frecsys_recommend(k = pool),
+ * frecsys_work("dpp") as frecsys_diversify_dpp. */
+int frecsys_recommend_dpp(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
+                          int32_t k, int32_t pool, float theta, float eps, int32_t flags,
+                          const uint8_t* item_mask, int32_t* items, float* scores, float* gain);
 /* ---- list quality: intra-list diversity, novelty, item exposure ----
  * What a serving configuration buys beside Recall / NDCG (no reference
  * counterpart): how varied each list is, how far down the popularity tail it

@@ -146,6 +146,30 @@ int frecsys_model_recommend_diverse_fold_in(frecsys_model* m, const int64_t* his
 int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float* list_scores,
                             int64_t n, int32_t pool, int32_t k, float lam, int32_t raw_scores,
                             int32_t* items, float* scores, float* mmr);
+/* The DPP counterparts of the three calls above (frecsys_recommend_dpp,
+ * frecsys_diversify_dpp, frecsys_hip.h, where the quality w = dpp_exp2(theta
+ * rel), the greedy steps of the incremental Cholesky, the fallback below eps,
+ * the tie order and the outputs are fixed to the bit):
+ * frecsys_model_recommend(k = pool) followed by frecsys_dpp_select on its
+ * lists against the model's item table, with the pools never leaving the
+ * device.  1 <= k <= pool <= 1024; theta finite and >= 0 (0: pure diversity);
+ * eps in (0, 1]; raw_scores, exclude_seen and item_mask as for the MMR calls.
+ * items / scores: host [n * k]; gain: host [n * k] or NULL, the gain of each
+ * selection (0 in the fallback).  The errors are frecsys_recommend_dpp's /
+ * frecsys_diversify_dpp's, reported before any device call and, for the
+ * fold-in form, before anything is projected. */
+int frecsys_model_recommend_dpp(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                int32_t pool, float theta, float eps, int32_t raw_scores,
+                                int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                                float* scores, float* gain);
+int frecsys_model_recommend_dpp_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                        const int32_t* hist_items, int64_t n, int32_t k,
+                                        int32_t pool, float theta, float eps, int32_t raw_scores,
+                                        int32_t exclude_seen, const uint8_t* item_mask,
+                                        int32_t* items, float* scores, float* gain);
+int frecsys_model_diversify_dpp(frecsys_model* m, const int32_t* lists, const float* list_scores,
+                                int64_t n, int32_t pool, int32_t k, float theta, float eps,
+                                int32_t raw_scores, int32_t* items, float* scores, float* gain);
 /* List quality of a serving configuration for trained users
  * (frecsys_rank_quality, frecsys_hip.h: the definitions of ILD, novelty and
  * exposure, the tolerance and what is exact are stated there): the lists are

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <vector>
 
 namespace frecsys_hip {
@@ -491,6 +492,52 @@ struct DiversifyArgs {
 };
 hipError_t launch_diversify_gram(const DiversifyArgs& a, hipStream_t s);
 hipError_t launch_diversify_select(const DiversifyArgs& a, hipStream_t s);
+
+// Greedy DPP re-ranking of a pool per row (dpp.hip; the semantics are
+// frecsys_dpp_select's in include/frecsys_hip.h, to the bit).  The pools and
+// G are DiversifyArgs' (launch_diversify_gram writes G); launch_dpp_select
+// writes the k selected ids, their pool scores and (unless out_gain is null)
+// their gains, -1 / -FLT_MAX / -FLT_MAX beyond the filled count.  The factor
+// C, [k][pool] fp32 per row, lies in LDS when dpp_factor_in_lds(pool, k) and
+// C is null, else at C (which may be given at any shape); where it lies
+// changes no output bit.
+constexpr int kDppLdsBytes = 40 * 1024;  // of the CU's 160 KiB: four rows (waves) per CU at the limit
+struct DppArgs {
+  int64_t n;                 // rows of this batch
+  int pool;                  // slots per row, 1 .. kDiversifyMaxPool
+  int k;                     // 1 .. pool
+  float theta;               // finite, >= 0
+  float eps;                 // in (0, 1]
+  int raw;                   // != 0: rel = score (FRECSYS_DIV_RAW_SCORES)
+  const int32_t* ids;        // [n][pool], each negative or in [0, items)
+  const float* pool_scores;  // [n][pool]
+  const float* G;            // [n][pool][pool]
+  float* C;                  // [n][k][pool] (workspace), or nullptr: LDS
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k]
+  float* out_gain;           // [n][k], or nullptr
+};
+size_t dpp_factor_bytes(int pool, int k);  // 4 k pool
+bool dpp_factor_in_lds(int pool, int k);   // dpp_factor_bytes <= kDppLdsBytes
+hipError_t launch_dpp_select(const DppArgs& a, hipStream_t s);
+
+// dpp_exp2 of include/frecsys_hip.h: 2^x for |x| <= 64 as a fixed sequence of
+// fp32 operations, the same on the host and on the device (rintf in the
+// default rounding mode, an exact subtraction, seven explicit fmas over the
+// coefficients ln(2)^i / i! rounded to fp32, an exact scaling).
+__host__ __device__ inline float dpp_exp2(float x) {
+  const float n = rintf(x);
+  const float f = x - n;
+  float q = 0x1.ffcbfcp-17f;
+  q = fmaf(q, f, 0x1.430912p-13f);
+  q = fmaf(q, f, 0x1.5d87fep-10f);
+  q = fmaf(q, f, 0x1.3b2ab6p-7f);
+  q = fmaf(q, f, 0x1.c6b08ep-5f);
+  q = fmaf(q, f, 0x1.ebfbe0p-3f);
+  q = fmaf(q, f, 0x1.62e430p-1f);
+  q = fmaf(q, f, 1.0f);
+  return ldexpf(q, (int)n);
+}
 
 // Scores of caller-supplied pairs and rankings of caller-supplied candidate
 // lists (rerank.hip).  Every score is the chain acc = fmaf(y[c], x[c], acc),

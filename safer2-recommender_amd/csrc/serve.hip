@@ -3,6 +3,7 @@
 // frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
 // frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions,
 // frecsys_explain, frecsys_recommend_diverse, frecsys_diversify,
+// frecsys_recommend_dpp, frecsys_diversify_dpp, frecsys_dpp_select,
 // frecsys_rank_quality, frecsys_lists_quality, and the host-only
 // frecsys_sample_negatives, frecsys_list_metrics, frecsys_position_metrics,
 // frecsys_metric_cvar, frecsys_mmr_select, frecsys_list_quality,
@@ -598,6 +599,120 @@ struct DiversifyStage {
   }
 };
 
+// What the DPP calls add to a ranking: the selection and where it goes (host).
+struct DppRequest {
+  int32_t k;
+  float theta, eps;
+  int32_t flags;
+  int32_t* items;
+  float* scores;
+  float* gain;  // or nullptr
+};
+
+// The arguments every DPP call checks first: the MMR calls' common cases (k,
+// pool, the flags), then theta finite and >= 0 and eps in (0, 1] (a NaN fails
+// both comparisons).
+int check_dpp(frecsys_ctx* c, const std::string& w, int32_t k, int32_t pool, float theta, float eps,
+              int32_t flags, int32_t known_flags) {
+  if (int rc = check_diversify(c, w, k, pool, 0.0f, flags, known_flags)) return rc;
+  if (!(theta >= 0.0f && std::isfinite(theta)))
+    return fail(c, FRECSYS_ERR_INVALID, w + "theta must be finite and >= 0");
+  if (!(eps > 0.0f && eps <= 1.0f)) return fail(c, FRECSYS_ERR_INVALID, w + "eps must be in (0, 1]");
+  return FRECSYS_OK;
+}
+
+// FRECSYS_DPP_FACTOR (read per call; changes no result bit): "ws" keeps the
+// factor C in the workspace at every shape; unset: in LDS where it fits
+// (dpp_factor_in_lds).
+bool dpp_factor_ws(int pool, int k) {
+  const char* v = getenv("FRECSYS_DPP_FACTOR");
+  return (v && !strcmp(v, "ws")) || !dpp_factor_in_lds(pool, k);
+}
+
+// The DPP selection behind pools of `pool` slots that are on the device:
+// div_gram_kernel writes the pool Gramians of a sub-batch of `gb` rows (as for
+// DiversifyStage, and for its reason), dpp_select_kernel reads them, and
+// [cnt][k] outputs go to the host.  Per row of a batch: the three output rows;
+// per row of a sub-batch: the Gramian and, where the factor does not fit LDS,
+// its 4 k pool bytes.
+struct DppStage {
+  const DppRequest& rq;
+  const int64_t n;
+  int64_t gb = 1;
+  bool ws;
+  DiversifyArgs ga{};  // the Gramian launch
+  DppArgs pa{};
+
+  DppStage(const frecsys_ctx* c, const DppRequest& r, int64_t rows, int pool)
+      : rq(r), n(rows), ws(r.k >= 1 && dpp_factor_ws(pool, r.k)) {
+    ga.Y = c->emb[1];
+    ga.Dp = c->Dp;
+    ga.pool = pa.pool = pool;
+    ga.k = pa.k = r.k;
+    pa.theta = r.theta;
+    pa.eps = r.eps;
+    pa.raw = (r.flags & FRECSYS_DIV_RAW_SCORES) != 0;
+  }
+  static size_t out_bytes(int k) { return (size_t)k * 12; }
+  // per row of a sub-batch
+  size_t sub_bytes() const {
+    return (size_t)pa.pool * pa.pool * 4 + (ws ? dpp_factor_bytes(pa.pool, pa.k) : 0);
+  }
+  // nb rows of a batch, their Gramians and factors in sub-batches within
+  // `budget` bytes (at least one row)
+  void carve_rows(Carver& cv, int64_t nb, size_t budget) {
+    gb = std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(budget / sub_bytes())));
+    ga.G = cv.take<float>((size_t)gb * pa.pool * pa.pool);
+    pa.C = cv.take_if<float>(ws, (size_t)gb * pa.k * pa.pool);
+    pa.out_items = cv.take<int32_t>((size_t)nb * pa.k);
+    pa.out_scores = cv.take<float>((size_t)nb * pa.k);
+    pa.out_gain = cv.take_if<float>(rq.gain != nullptr, (size_t)nb * pa.k);
+  }
+  // rows [r0, r0 + cnt) of the call, their pools at ids / pool_scores; the
+  // outputs are on their way to the host when it returns (the caller
+  // synchronises)
+  int run(frecsys_ctx* c, const int32_t* ids, const float* pool_scores, int64_t r0, int64_t cnt) {
+    const size_t k = (size_t)pa.k, P = (size_t)pa.pool;
+    DiversifyArgs g = ga;
+    DppArgs sub = pa;
+    sub.G = ga.G;
+    for (int64_t s0 = 0; s0 < cnt; s0 += gb) {  // two timed launches per sub-batch
+      g.n = sub.n = std::min(gb, cnt - s0);
+      g.ids = sub.ids = ids + (size_t)s0 * P;
+      g.pool_scores = sub.pool_scores = pool_scores + (size_t)s0 * P;
+      g.out_items = sub.out_items = pa.out_items + (size_t)s0 * k;
+      g.out_scores = sub.out_scores = pa.out_scores + (size_t)s0 * k;
+      sub.out_gain = pa.out_gain ? pa.out_gain + (size_t)s0 * k : nullptr;
+      {
+        ScopedTimer t(c, "diversify.gram");
+        HIP_TRY(c, launch_diversify_gram(g, c->stream));
+        t.stop();
+      }
+      {
+        ScopedTimer t(c, "dpp.select");
+        HIP_TRY(c, launch_dpp_select(sub, c->stream));
+        t.stop();
+      }
+    }
+    HIP_TRY(c, to_host(c, rq.items + r0 * k, pa.out_items, (size_t)cnt * k));
+    HIP_TRY(c, to_host(c, rq.scores + r0 * k, pa.out_scores, (size_t)cnt * k));
+    if (rq.gain) HIP_TRY(c, to_host(c, rq.gain + r0 * k, pa.out_gain, (size_t)cnt * k));
+    return FRECSYS_OK;
+  }
+  // flops at the logical dim: the lower triangle of every pool Gramian, then
+  // the factor's chains, sum over t < k of 2 t pool, every step booked as a
+  // DPP step; bytes: the pool's item rows gathered once, the Gramian written,
+  // k of its rows and the pool read by the selection, the factor written once
+  // and read sum over t < k of t pool words, the outputs
+  void book(frecsys_ctx* c) const {
+    const double P = pa.pool, k = pa.k, d = c->dim;
+    add_work(c, "dpp", (double)n * (P * (P + 1.0) * d + k * (k - 1.0) * P),
+             (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 + k * P * 4.0 +
+                          k * (k - 1.0) * P * 2.0 + k * (rq.gain ? 12.0 : 8.0)),
+             n);
+  }
+};
+
 // What the quality calls add to a ranking: the cut-offs, the item weights of
 // novelty (or nullptr) and where the results go (host; each may be nullptr).
 struct QualityRequest {
@@ -723,16 +838,20 @@ struct QualityStage {
 // and the selection goes to the host).  The scan is the same launch with the
 // same workspace layout in all three; the ground truth, the tables and the
 // metric outputs, or the pool Gramians and the selection, lie behind it.
+// frecsys_recommend_dpp (dp given) is frecsys_recommend_diverse's shape with the
+// DPP stage in the MMR stage's place; dp comes with none of mt, dv and ql.
 int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
                    int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
                    int32_t* items, float* scores, const MetricsRequest* mt,
-                   const DiversifyRequest* dv = nullptr, const QualityRequest* ql = nullptr) {
+                   const DiversifyRequest* dv = nullptr, const QualityRequest* ql = nullptr,
+                   const DppRequest* dp = nullptr) {
   const std::string w = std::string(what) + ": ";
   int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
   if (rc) return rc;
   if (n_rows < 0 || (n_rows > 0 && (ql   ? false  // frecsys_rank_quality checks its own
                                     : mt ? (!mt->recall || !mt->ndcg)
                                     : dv ? (!dv->items || !dv->scores)
+                                    : dp ? (!dp->items || !dp->scores)
                                          : !items)))
     return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
   const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
@@ -757,12 +876,15 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
   DiversifyStage ds(c, dv ? *dv : no_dv, n, k);
   const QualityRequest no_ql{};
   QualityStage qs(c, ql ? *ql : no_ql, n, list_k);
+  const DppRequest no_dp{};
+  DppStage ps(c, dp ? *dp : no_dp, n, k);
   // per row of a batch beside the scan's own: history bits, the two metric
   // rows, the pool Gramian and the selection, the two quality rows
   const ScanPlan p =
       scan_plan(c, k, m, n,
                 (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8 +
-                    (dv ? DiversifyStage::out_bytes(dv->k) : 0) + (ql ? qs.row_bytes() : 0));
+                    (dv ? DiversifyStage::out_bytes(dv->k) : 0) + (ql ? qs.row_bytes() : 0) +
+                    (dp ? DppStage::out_bytes(dp->k) : 0));
   c->rec_splits = p.splits;
   RecommendArgs a = scan_args(c, side, FRECSYS_SIDE_ITEM, k, p.splits, exclude);
   rc = Carver::run(c, [&](Carver& cv) {
@@ -774,6 +896,7 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     // outside the scan's per-row budget: the Gramians of a sub-batch, within a
     // budget of their own
     if (dv) ds.carve_rows(cv, p.nb, workspace_budget());
+    if (dp) ps.carve_rows(cv, p.nb, workspace_budget());
     if (ql) {
       qs.carve_rows(cv, p.nb);
       qs.carve_inputs(cv);
@@ -817,6 +940,9 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
     } else if (dv) {
       if ((rc = ds.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (dp) {
+      if ((rc = ps.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else if ((rc = fetch_lists(c, items, scores, k, r0, a.n, a.out_items, a.out_scores))) {
       return rc;
     }
@@ -827,6 +953,7 @@ int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t
            ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
   if (mt) ms.book(c);
   if (dv) ds.book(c);
+  if (dp) ps.book(c);
   if (ql) {
     if ((rc = qs.finish(c))) return rc;
     qs.book(c);
@@ -1159,6 +1286,62 @@ int frecsys_diversify(frecsys_ctx* c, const int32_t* lists, const float* list_sc
   return FRECSYS_OK;
 }
 
+int frecsys_recommend_dpp(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                          int32_t k, int32_t pool, float theta, float eps, int32_t flags,
+                          const uint8_t* item_mask, int32_t* items, float* scores, float* gain) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend_dpp: null context");
+  const int rc = check_dpp(c, "recommend_dpp: ", k, pool, theta, eps, flags,
+                           FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  const DppRequest dp{k, theta, eps, flags, items, scores, gain};
+  return recommend_impl(c, "recommend_dpp", side, rows, n_rows, pool,
+                        flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, &dp);
+}
+
+int frecsys_diversify_dpp(frecsys_ctx* c, const int32_t* lists, const float* list_scores,
+                          int64_t n, int32_t pool, int32_t k, float theta, float eps,
+                          int32_t flags, int32_t* items, float* scores, float* gain) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "diversify_dpp: null context");
+  const std::string w = "diversify_dpp: ";
+  int rc = check_dpp(c, w, k, pool, theta, eps, flags, FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n == 0) return FRECSYS_OK;
+  if (!lists || !list_scores || !items || !scores)
+    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
+  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
+  const std::string e = pool_error(lists, list_scores, n, pool, c->n[1], raw);
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const DppRequest dp{k, theta, eps, flags, items, scores, gain};
+  DppStage ps(c, dp, n, pool);
+  // per row of a batch: its pool (ids and scores), its Gramian, its factor
+  // where that is not in LDS, and its outputs; at least one row per batch, and
+  // one sub-batch per batch
+  const size_t budget = workspace_budget();
+  const size_t per_row = (size_t)pool * 8 + ps.sub_bytes() + DppStage::out_bytes(k);
+  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(budget / per_row)));
+  int32_t* d_ids = nullptr;
+  float* d_sc = nullptr;
+  rc = Carver::run(c, [&](Carver& cv) {
+    d_ids = cv.take<int32_t>((size_t)nb * pool);
+    d_sc = cv.take<float>((size_t)nb * pool);
+    ps.carve_rows(cv, nb, std::max(budget, (size_t)nb * ps.sub_bytes()));
+  });
+  if (rc) return rc;
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {
+    const int64_t cnt = std::min(nb, n - r0);
+    HIP_TRY(c, to_device(c, d_ids, lists + r0 * pool, (size_t)cnt * pool));
+    HIP_TRY(c, to_device(c, d_sc, list_scores + r0 * pool, (size_t)cnt * pool));
+    if ((rc = ps.run(c, d_ids, d_sc, r0, cnt))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  ps.book(c);
+  return FRECSYS_OK;
+}
+
 int frecsys_rank_quality(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
                          int32_t flags, const uint8_t* item_mask, const int32_t* k_list,
                          int32_t nk, int32_t pool, float lam, int32_t div_flags,
@@ -1422,6 +1605,122 @@ int frecsys_mmr_select(const float* item_table, int64_t n_items, int32_t dim, in
   };
   // rows are independent: host threads over row ranges when there is enough work
   const double cost = (double)n * pool * (double)k * dim;
+  const int nt = cost < 1e8 ? 1
+                            : (int)std::min<int64_t>(
+                                  n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+  if (nt <= 1) {
+    work(0, n);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
+    for (auto& t : th) t.join();
+  }
+  return FRECSYS_OK;
+}
+
+int frecsys_dpp_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
+                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
+                       int32_t k, float theta, float eps, int32_t flags, int32_t* items,
+                       float* scores, float* gain) {
+#pragma clang fp contract(off)
+  const std::string w = "dpp_select: ";
+  int rc = check_dpp(nullptr, w, k, pool, theta, eps, flags, FRECSYS_DIV_RAW_SCORES);
+  if (rc) return rc;
+  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n == 0) return FRECSYS_OK;
+  if (!item_table || n_items < 1 || dim < 1 || ld < dim)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, n_items < 1, ld < dim)");
+  if (!lists || !list_scores || !items || !scores)
+    return fail(nullptr, FRECSYS_ERR_INVALID, w + "null pointer");
+  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
+  const std::string e = pool_error(lists, list_scores, n, pool, n_items, raw);
+  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
+  auto dot = [&](int32_t x, int32_t y) {
+    const float* px = item_table + (int64_t)x * ld;
+    const float* py = item_table + (int64_t)y * ld;
+    float acc = 0.0f;
+    for (int32_t cc = 0; cc < dim; ++cc) acc = std::fmaf(px[cc], py[cc], acc);
+    return acc;
+  };
+  auto work = [&](int64_t i0, int64_t i1) {
+    const size_t P = (size_t)pool;
+    std::vector<float> wq(P), r(P), inv(P), C((size_t)k * P);
+    std::vector<uint8_t> alive(P);
+    for (int64_t i = i0; i < i1; ++i) {
+      const int32_t* ids = lists + i * pool;
+      const float* sc = list_scores + i * pool;
+      float smax = -INFINITY, smin = INFINITY;
+      int32_t p = 0;
+      for (int32_t b = 0; b < pool; ++b) {
+        alive[(size_t)b] = ids[b] >= 0;
+        if (!alive[(size_t)b]) continue;
+        ++p;
+        smax = std::fmax(smax, sc[b]);
+        smin = std::fmin(smin, sc[b]);
+        const float n2 = dot(ids[b], ids[b]);
+        inv[(size_t)b] = n2 > 0.0f ? 1.0f / std::sqrt(n2) : 0.0f;
+        r[(size_t)b] = n2 > 0.0f ? 1.0f : 0.0f;
+      }
+      const float range = smax - smin;
+      for (int32_t b = 0; b < pool; ++b) {
+        if (!alive[(size_t)b]) continue;
+        const float rel = raw ? sc[b] : (range > 0.0f ? (sc[b] - smin) / range : 0.0f);
+        const float x = theta * rel;
+        wq[(size_t)b] = dpp_exp2(std::fmin(std::fmax(x, -64.0f), 64.0f));
+      }
+      const int32_t steps = std::min(p, k);
+      int32_t m = 0;
+      for (int32_t t = 0; t < steps; ++t) {
+        uint64_t best = 0;
+        for (int32_t b = 0; b < pool; ++b) {
+          if (!alive[(size_t)b]) continue;
+          uint32_t key = 0;  // below eps: the fallback's word, the lowest slot wins
+          if (r[(size_t)b] >= eps) {
+            const float v = wq[(size_t)b] * r[(size_t)b] + 0.0f;
+            uint32_t u;
+            std::memcpy(&u, &v, 4);
+            key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // score_key
+          }
+          const uint64_t word = ((uint64_t)key << 32) | (0xFFFFFFFFu - (uint32_t)b);
+          if (word > best) best = word;
+        }
+        const int32_t s = (int32_t)(0xFFFFFFFFu - (uint32_t)best);
+        const uint32_t key = (uint32_t)(best >> 32);
+        const uint32_t u = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;  // score_unkey
+        items[i * k + t] = ids[s];
+        scores[i * k + t] = sc[s];
+        if (gain) {
+          if (key) std::memcpy(&gain[i * k + t], &u, 4);
+          else gain[i * k + t] = 0.0f;
+        }
+        alive[(size_t)s] = 0;
+        if (key == 0 || t + 1 == steps) continue;  // the last step's update is never read
+        const float delta = std::sqrt(r[(size_t)s]);
+        const float* cs = C.data() + (size_t)s;
+        for (int32_t b = 0; b < pool; ++b) {
+          if (!alive[(size_t)b]) continue;
+          const float g = dot(ids[s], ids[b]);
+          const float gs = g * inv[(size_t)s];
+          const float sim = gs * inv[(size_t)b] + 0.0f;
+          float acc = 0.0f;
+          for (int32_t uu = 0; uu < m; ++uu)
+            acc = std::fmaf(C[(size_t)uu * P + (size_t)b], cs[(size_t)uu * P], acc);
+          const float d = sim - acc;
+          const float ev = d / delta;
+          C[(size_t)m * P + (size_t)b] = ev;
+          r[(size_t)b] = std::fmaf(-ev, ev, r[(size_t)b]);
+        }
+        ++m;
+      }
+      for (int32_t t = steps; t < k; ++t) {
+        items[i * k + t] = -1;
+        scores[i * k + t] = -FLT_MAX;
+        if (gain) gain[i * k + t] = -FLT_MAX;
+      }
+    }
+  };
+  // rows are independent: host threads over row ranges when there is enough work
+  const double cost = (double)n * pool * (double)k * ((double)dim + 0.5 * k);
   const int nt = cost < 1e8 ? 1
                             : (int)std::min<int64_t>(
                                   n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));

@@ -57,7 +57,8 @@ EXPORTS = (
     "frecsys_sampled_metrics", "frecsys_position_metrics", "frecsys_rank_positions",
     "frecsys_explain", "frecsys_csr_row_lengths", "frecsys_mmr_select", "frecsys_diversify",
     "frecsys_recommend_diverse", "frecsys_list_quality", "frecsys_exposure_summary",
-    "frecsys_rank_quality", "frecsys_lists_quality",
+    "frecsys_rank_quality", "frecsys_lists_quality", "frecsys_dpp_select",
+    "frecsys_diversify_dpp", "frecsys_recommend_dpp",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -78,6 +79,8 @@ MODEL_EXPORTS = (
     "frecsys_model_recommend_diverse", "frecsys_model_recommend_diverse_fold_in",
     "frecsys_model_diversify", "frecsys_model_evaluate_quality",
     "frecsys_model_evaluate_quality_fold_in", "frecsys_model_list_quality",
+    "frecsys_model_recommend_dpp", "frecsys_model_recommend_dpp_fold_in",
+    "frecsys_model_diversify_dpp",
 )
 
 
@@ -231,6 +234,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_rank_quality": (ctypes.c_int, [P, I32, P, I64, I32, P, P, I32, I32, F, I32, P, P,
                                                 P, P, P, P, P, P]),
         "frecsys_lists_quality": (ctypes.c_int, [P, P, I64, I32, P, I32, P, P, P, P]),
+        "frecsys_dpp_select": (ctypes.c_int,
+                               [P, I64, I32, I64, P, P, I64, I32, I32, F, F, I32, P, P, P]),
+        "frecsys_diversify_dpp": (ctypes.c_int, [P, P, P, I64, I32, I32, F, F, I32, P, P, P]),
+        "frecsys_recommend_dpp": (ctypes.c_int,
+                                  [P, I32, P, I64, I32, I32, F, F, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -306,6 +314,12 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
             [P, P, P, I64, P, I32, I32, F, I32, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
         "frecsys_model_list_quality": (ctypes.c_int,
                                        [P, P, I64, I32, P, I32, P, P, P, P, P, P]),
+        "frecsys_model_recommend_dpp": (ctypes.c_int,
+                                        [P, P, I64, I32, I32, F, F, I32, I32, P, P, P, P]),
+        "frecsys_model_recommend_dpp_fold_in": (
+            ctypes.c_int, [P, P, P, I64, I32, I32, F, F, I32, I32, P, P, P, P]),
+        "frecsys_model_diversify_dpp": (ctypes.c_int,
+                                        [P, P, P, I64, I32, I32, F, F, I32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -496,6 +510,30 @@ def mmr_select(item_table, lists, scores, k: int, lam: float = 0.7, raw_scores: 
                                 _ptr(mmr))
     _check_host(lib, rc)
     return (items, out, mmr) if return_mmr else (items, out)
+
+
+def dpp_select(item_table, lists, scores, k: int, theta: float = 4.0, eps: float = 1e-3,
+               raw_scores: bool = False, return_gain: bool = False):
+    """(items int32 [n, k], scores float32 [n, k][, gain float32 [n, k]]): greedy
+    DPP selection (the incremental Cholesky of Chen, Zhang and Zhou) of k slots
+    from each row's pool against item_table, on the host (frecsys_dpp_select:
+    the definition Context.diversify_dpp and Context.recommend_dpp return bit
+    for bit; no GPU needed).  Arrays as for mmr_select; theta scales the
+    relevance in the quality 2^(theta rel) (0: pure diversity), and a slot
+    whose residual is below eps is taken only in pool order, with gain 0."""
+    lib = load_library()
+    tab = np.asarray(item_table, dtype=np.float32)
+    assert tab.ndim == 2, tab.shape
+    if tab.strides[1] != 4 or tab.strides[0] % 4 or tab.strides[0] < 4 * tab.shape[1]:
+        tab = np.ascontiguousarray(tab)
+    ls, sc = _pools(lists, scores)
+    items, out, gain = _diverse_out(ls.shape[0], k, return_gain)
+    rc = lib.frecsys_dpp_select(_ptr(tab), tab.shape[0], tab.shape[1], tab.strides[0] // 4,
+                                _ptr(ls), _ptr(sc), ls.shape[0], ls.shape[1], k, theta, eps,
+                                DIV_RAW_SCORES if raw_scores else 0, _ptr(items), _ptr(out),
+                                _ptr(gain))
+    _check_host(lib, rc)
+    return (items, out, gain) if return_gain else (items, out)
 
 
 def sample_negatives(n_items: int, gt_ptr, gt_items, n_neg: int, seed: int = 0, rows=None,
@@ -876,6 +914,40 @@ class Context:
                                                DIV_RAW_SCORES if raw_scores else 0, _ptr(items),
                                                _ptr(out), _ptr(mmr)))
         return (items, out, mmr) if return_mmr else (items, out)
+
+    def recommend_dpp(self, side: int, k: int, pool: Optional[int] = None, theta: float = 4.0,
+                      eps: float = 1e-3, rows=None, raw_scores: bool = False,
+                      exclude_history: bool = True, item_mask=None, return_gain: bool = False):
+        """(items int32 [n, k], scores float32 [n, k][, gain float32 [n, k]]):
+        dpp_select of recommend(side, pool, ...)'s lists against the item
+        table, bit for bit, with the pools never leaving the GPU
+        (frecsys_recommend_dpp).  pool defaults to default_pool(k)."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        items, scores, gain = _diverse_out(n, k, return_gain)
+        flags = (REC_EXCLUDE_HISTORY if exclude_history else 0) | \
+            (DIV_RAW_SCORES if raw_scores else 0)
+        self._check(self.lib.frecsys_recommend_dpp(
+            self.h, side, _ptr(r), n, k, default_pool(k) if pool is None else pool, theta, eps,
+            flags, _ptr(mk), _ptr(items), _ptr(scores), _ptr(gain)))
+        return (items, scores, gain) if return_gain else (items, scores)
+
+    def diversify_dpp(self, lists, scores, k: int, theta: float = 4.0, eps: float = 1e-3,
+                      raw_scores: bool = False, return_gain: bool = False):
+        """The same selection from caller-supplied pools against the context's
+        item table, on the GPU (frecsys_diversify_dpp): dpp_select's result bit
+        for bit."""
+        ls, sc = _pools(lists, scores)
+        items, out, gain = _diverse_out(ls.shape[0], k, return_gain)
+        self._check(self.lib.frecsys_diversify_dpp(self.h, _ptr(ls), _ptr(sc), ls.shape[0],
+                                                   ls.shape[1], k, theta, eps,
+                                                   DIV_RAW_SCORES if raw_scores else 0,
+                                                   _ptr(items), _ptr(out), _ptr(gain)))
+        return (items, out, gain) if return_gain else (items, out)
 
     def rank_quality(self, side: int, k_list, rows=None, pool: Optional[int] = None,
                      lam: float = 0.7, raw_scores: bool = False, item_weight=None, gt=None,
@@ -1452,6 +1524,46 @@ class Model:
                                                      ls.shape[1], k, lam, int(bool(raw_scores)),
                                                      _ptr(items), _ptr(out), _ptr(mmr)))
         return (items, out, mmr) if return_mmr else (items, out)
+
+    def _recommend_dpp(self, head, n, k, pool, theta, eps, raw_scores, exclude_seen, item_mask,
+                       return_gain):
+        mk = self._mask(item_mask)
+        items, scores, gain = _diverse_out(n, k, return_gain)
+        self._call("recommend_dpp", head, n, k, default_pool(k) if pool is None else pool, theta,
+                   eps, int(bool(raw_scores)), int(bool(exclude_seen)), _ptr(mk), _ptr(items),
+                   _ptr(scores), _ptr(gain))
+        return (items, scores, gain) if return_gain else (items, scores)
+
+    def recommend_dpp(self, users, k: int, pool: Optional[int] = None, theta: float = 4.0,
+                      eps: float = 1e-3, exclude_seen: bool = True, item_mask=None,
+                      raw_scores: bool = False, return_gain: bool = False):
+        """(items int32 [n, k], scores float32 [n, k][, gain float32 [n, k]]) for
+        trained users (frecsys_model_recommend_dpp): greedy DPP re-ranking of
+        recommend(users, pool)'s lists down to k against the item table --
+        dpp_select's result bit for bit, computed on the GPU.  pool defaults to
+        default_pool(k); theta = 0 is pure diversity."""
+        return self._recommend_dpp(*self._head(users), k, pool, theta, eps, raw_scores,
+                                   exclude_seen, item_mask, return_gain)
+
+    def recommend_dpp_fold_in(self, hist_ptr, hist_items, k: int, pool: Optional[int] = None,
+                              theta: float = 4.0, eps: float = 1e-3, exclude_seen: bool = True,
+                              item_mask=None, raw_scores: bool = False,
+                              return_gain: bool = False):
+        """The same for unseen users given by their histories (CSR), as
+        recommend_fold_in (frecsys_model_recommend_dpp_fold_in)."""
+        return self._recommend_dpp(*self._head(hist=(hist_ptr, hist_items)), k, pool, theta, eps,
+                                   raw_scores, exclude_seen, item_mask, return_gain)
+
+    def diversify_dpp(self, lists, scores, k: int, theta: float = 4.0, eps: float = 1e-3,
+                      raw_scores: bool = False, return_gain: bool = False):
+        """The same selection from caller-supplied pools against the model's
+        item table (frecsys_model_diversify_dpp)."""
+        ls, sc = _pools(lists, scores)
+        items, out, gain = _diverse_out(ls.shape[0], k, return_gain)
+        self._check(self.lib.frecsys_model_diversify_dpp(
+            self.h, _ptr(ls), _ptr(sc), ls.shape[0], ls.shape[1], k, theta, eps,
+            int(bool(raw_scores)), _ptr(items), _ptr(out), _ptr(gain)))
+        return (items, out, gain) if return_gain else (items, out)
 
     def item_self_information(self) -> np.ndarray:
         """float32 [n_items]: -log2(max(h_i, 1) / n_users) with h_i the number

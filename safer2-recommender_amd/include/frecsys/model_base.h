@@ -126,6 +126,20 @@ class DeviceModel : public Recommender {
     return frecsys_diversify(dev_->raw(), lists, list_scores, n, pool, k, lam, flags, items, scores,
                              mmr);
   }
+  // The DPP selection in the MMR selection's place (frecsys_recommend_dpp,
+  // frecsys_diversify_dpp): the same rows, pools, flags and outputs, theta and
+  // eps for lam, gain for mmr.
+  int RecommendDpp(int side, const int64_t* rows, int64_t n, int k, int pool, float theta,
+                   float eps, int flags, const uint8_t* mask, int32_t* items, float* scores,
+                   float* gain) {
+    return frecsys_recommend_dpp(dev_->raw(), side, rows, n, k, pool, theta, eps, flags, mask,
+                                 items, scores, gain);
+  }
+  int DiversifyDpp(const int32_t* lists, const float* list_scores, int64_t n, int pool, int k,
+                   float theta, float eps, int flags, int32_t* items, float* scores, float* gain) {
+    return frecsys_diversify_dpp(dev_->raw(), lists, list_scores, n, pool, k, theta, eps, flags,
+                                 items, scores, gain);
+  }
 
   // The solve parameters of the model's own fold-in projection -- the ones
   // its FoldIn passes, omega = 1 where the fold-in uses it.  iALS++ and

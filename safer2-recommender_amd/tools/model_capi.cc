@@ -451,6 +451,19 @@ std::string diverse_args_error(int32_t k, int32_t pool, float lam, int32_t raw_s
   return "";
 }
 
+// The cases the DPP calls reject (frecsys_hip.h): the MMR calls' with theta
+// and eps in lam's place.
+std::string dpp_args_error(int32_t k, int32_t pool, float theta, float eps, int32_t raw_scores,
+                           int64_t n, const int32_t* items, const float* scores) {
+  if (pool < 1 || pool > 1024) return "pool must be in [1, 1024]";
+  if (k < 1 || k > pool) return "k must be in [1, pool]";
+  if (!(theta >= 0.0f && std::isfinite(theta))) return "theta must be finite and >= 0";
+  if (!(eps > 0.0f && eps <= 1.0f)) return "eps must be in (0, 1]";
+  if (raw_scores != 0 && raw_scores != 1) return "raw_scores must be 0 or 1";
+  if (n > 0 && (!items || !scores)) return "null outputs";
+  return "";
+}
+
 int32_t diverse_flags(int32_t exclude_seen, int32_t raw_scores) {
   return exclude_flag(exclude_seen) | (raw_scores ? FRECSYS_DIV_RAW_SCORES : 0);
 }
@@ -566,6 +579,19 @@ int recommend_diverse(frecsys_model* m, const std::string& w, const Query& q, in
   return context_status(r.dev(), r.dm->RecommendDiverse(r.side, r.ids, q.n, k, pool, lam,
                                                         diverse_flags(exclude_seen, raw_scores),
                                                         item_mask, items, scores, mmr));
+}
+
+int recommend_dpp(frecsys_model* m, const std::string& w, const Query& q, int32_t k, int32_t pool,
+                  float theta, float eps, int32_t raw_scores, int32_t exclude_seen,
+                  const uint8_t* item_mask, int32_t* items, float* scores, float* gain) {
+  Rows r;
+  const auto own = [&](int64_t) {
+    return dpp_args_error(k, pool, theta, eps, raw_scores, q.n, items, scores);
+  };
+  if (int rc = open_query(m, w, q, exclude_seen, own, &r)) return answered(rc);
+  return context_status(r.dev(), r.dm->RecommendDpp(r.side, r.ids, q.n, k, pool, theta, eps,
+                                                    diverse_flags(exclude_seen, raw_scores),
+                                                    item_mask, items, scores, gain));
 }
 
 // DeviceModel::Explain / ExplainFoldIn on the opened rows: trained users are
@@ -1034,6 +1060,38 @@ int frecsys_model_diversify(frecsys_model* m, const int32_t* lists, const float*
   return context_status(dm->device(), dm->Diversify(lists, list_scores, n, pool, k, lam,
                                                     diverse_flags(0, raw_scores), items, scores,
                                                     mmr));
+}
+
+int frecsys_model_recommend_dpp(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                int32_t pool, float theta, float eps, int32_t raw_scores,
+                                int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
+                                float* scores, float* gain) {
+  return recommend_dpp(m, "frecsys_model_recommend_dpp: ", trained(users, n), k, pool, theta, eps,
+                       raw_scores, exclude_seen, item_mask, items, scores, gain);
+}
+
+int frecsys_model_recommend_dpp_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                        const int32_t* hist_items, int64_t n, int32_t k,
+                                        int32_t pool, float theta, float eps, int32_t raw_scores,
+                                        int32_t exclude_seen, const uint8_t* item_mask,
+                                        int32_t* items, float* scores, float* gain) {
+  return recommend_dpp(m, "frecsys_model_recommend_dpp_fold_in: ", unseen(hist_ptr, hist_items, n),
+                       k, pool, theta, eps, raw_scores, exclude_seen, item_mask, items, scores,
+                       gain);
+}
+
+int frecsys_model_diversify_dpp(frecsys_model* m, const int32_t* lists, const float* list_scores,
+                                int64_t n, int32_t pool, int32_t k, float theta, float eps,
+                                int32_t raw_scores, int32_t* items, float* scores, float* gain) {
+  const std::string w = "frecsys_model_diversify_dpp: ";
+  if (!m || n < 0 || (n > 0 && (!lists || !list_scores)))
+    return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  const std::string e = dpp_args_error(k, pool, theta, eps, raw_scores, n, items, scores);
+  if (!e.empty()) return model_fail(FRECSYS_ERR_INVALID, w + e);
+  frecsys::detail::DeviceModel* dm = frecsys::AsDeviceModel(m->rec.get());
+  return context_status(dm->device(), dm->DiversifyDpp(lists, list_scores, n, pool, k, theta, eps,
+                                                       diverse_flags(0, raw_scores), items, scores,
+                                                       gain));
 }
 
 int frecsys_model_evaluate_quality(frecsys_model* m, const int64_t* users, int64_t n,
