@@ -1,15 +1,9 @@
 // serve.hip -- host side of the ranking and evaluation calls of the C-ABI
-// (include/frecsys_hip.h): frecsys_recommend, frecsys_rank_metrics,
-// frecsys_score_pairs, frecsys_rank_candidates, frecsys_rank_candidates_metrics,
-// frecsys_sampled_metrics, frecsys_similar, frecsys_rank_positions,
-// frecsys_explain, frecsys_recommend_diverse, frecsys_diversify,
-// frecsys_recommend_dpp, frecsys_diversify_dpp, frecsys_dpp_select,
-// frecsys_rank_quality, frecsys_lists_quality, and the host-only
-// frecsys_sample_negatives, frecsys_list_metrics, frecsys_position_metrics,
-// frecsys_metric_cvar, frecsys_mmr_select, frecsys_list_quality,
-// frecsys_exposure_summary.  No kernels here: recommend.hip, similar.hip,
-// rerank.hip, sampled.hip, metrics.hip, positions.hip, explain.hip,
-// diversify.hip and quality.hip hold them (kernels.h).
+// (include/frecsys_hip.h) that take a context and drive the device.  The
+// context-free host calls are serve_host.hip's; serve.h holds what the two
+// units share.  No kernels here: recommend.hip, similar.hip, rerank.hip,
+// sampled.hip, metrics.hip, positions.hip, explain.hip, diversify.hip, dpp.hip
+// and quality.hip hold them (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -18,42 +12,35 @@
 // tables, cut-offs).  The budget (workspace_budget) bounds the batch regions
 // only.
 //
-// Batches.  A call runs its rows in batches, one timed launch group each, and
+// Drivers.  A call runs its rows in batches, one timed launch group each, and
 // synchronises after each batch's copy-back:
-//   scan calls (recommend, rank_metrics, similar): budget / bytes per row,
-//     rounded down to whole 64-row blocks, with the item splits of scan_plan;
+//   scan (scan_impl with one object behind the scan: recommend,
+//     rank_metrics, recommend_diverse, recommend_dpp, rank_quality; similar,
+//     with a loop of its own): budget / bytes per row, the scan's and what is
+//     behind it, in whole 64-row blocks, with the item splits of scan_plan; a
+//     selection forms its Gramians in sub-batches, within a budget of their own;
+//   pools (pools_impl: diversify, diversify_dpp): budget / bytes per row (the
+//     pool, its Gramian, the selection), at least one row;
+//   candidate lists (rank_candidates; cand_metrics_impl for
+//     rank_candidates_metrics): rows in order while their fixed bytes and ids
+//     fit the budget (cut_by_candidates); sampled lists (sampled_metrics): by
+//     their fixed bytes within half the budget, then by ids within the other;
+//   caller lists (lists_quality): budget / bytes per row (the list and the
+//     result rows), at least one row;
 //   pairs (score_pairs): budget / 16 B, at least 64;
-//   caller lists (rank_candidates, rank_candidates_metrics): rows in order
-//     while their fixed bytes and ids fit the budget (cut_by_candidates);
-//   positions (rank_positions): the same cut by the ground-truth entries;
-//   sampled lists (sampled_metrics): rows by their fixed bytes within half the
-//     budget, then sub-batches whose ids fit the other half;
+//   positions (rank_positions): cut_by_candidates by the ground-truth entries;
 //   explanations (explain): the same cut by the contributions, h floats per
-//     (row, target) pair;
-//   pools (diversify): budget / bytes per row (the pool, its Gramian, the
-//     selection), at least one row; recommend_diverse adds the selection to
-//     the scan's bytes per row and forms the Gramians in sub-batches of the
-//     batch, within a budget of their own;
-//   quality (rank_quality): the scan's batches with the two result rows more
-//     per row; caller lists (lists_quality): budget / bytes per row (the list
-//     and the result rows), at least one row.
+//     (row, target) pair.
 // Rows are independent, so the batch size never changes a result.
 //
 // Checks.  Each entry point keeps its own order of checks and its own point
 // of return for zero rows; the checkers below are its pieces.
-#include <algorithm>
-#include <atomic>
-#include <cfloat>
 #include <climits>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <thread>
-#include <vector>
+#include <optional>
 
-#include "../include/frecsys/parallel.h"
-#include "ctx.h"
+#include "serve.h"
 
 namespace {
 
@@ -272,120 +259,45 @@ RankCandArgs cand_args(const frecsys_ctx* c, int side, int k, bool exclude) {
   return a;
 }
 
-// A batch's lists to the host, and the end of the batch.
-int fetch_lists(frecsys_ctx* c, int32_t* items, float* scores, int k, int64_t r0, int64_t cnt,
-                const int32_t* d_items, const float* d_scores) {
+// A batch's lists on their way to the host (the caller synchronises).
+int copy_lists(frecsys_ctx* c, int32_t* items, float* scores, int k, int64_t r0, int64_t cnt,
+               const int32_t* d_items, const float* d_scores) {
   HIP_TRY(c, to_host(c, items + r0 * k, d_items, (size_t)(cnt * k)));
   if (scores) HIP_TRY(c, to_host(c, scores + r0 * k, d_scores, (size_t)(cnt * k)));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FRECSYS_OK;
 }
 
-// gain[j] = 1 / log2(j + 2) and its sequential prefix idcg[m] = gain[0] + ...
-// + gain[m-1] (idcg[0] = 0), in double with the host's std::log2: the terms
-// and the norm of RankMetrics (recommender.h:152-182) in its own order.
-struct MetricTables {
-  double gain[kMetricMaxK];
-  double idcg[kMetricMaxK + 1];
+// What lies behind the scan of a ranking call (scan_impl).  Every step is
+// virtual: a stage states its own with `override`, so a misnamed one fails to
+// compile.
+struct BehindScan {
+  virtual size_t scan_bytes() const { return 0; }                // per row of a batch
+  virtual void scan_carve(Carver&, int64_t) {}                   // regions: per row, then per call
+  virtual int scan_upload(frecsys_ctx*) { return FRECSYS_OK; }   // per call, before the first batch
+  virtual int scan_overlap(frecsys_ctx*) { return FRECSYS_OK; }  // host work during the first scan
+  // a batch's lists and scores, where the scan left them
+  virtual int run(frecsys_ctx* c, const int32_t* lists, const float* scores, int64_t r0,
+                  int64_t cnt) = 0;
+  virtual void book(frecsys_ctx*) const {}
+  // after the last batch: what is left to fetch, and the work booked
+  virtual int finish(frecsys_ctx* c) {
+    book(c);
+    return FRECSYS_OK;
+  }
+  virtual void no_rows(const frecsys_ctx*) const {}  // a call of zero rows passed its checks
 };
-const MetricTables& metric_tables() {
-  static const MetricTables tab = [] {
-    MetricTables t;
-    t.idcg[0] = 0.0;
-    for (int j = 0; j < kMetricMaxK; ++j) {
-      t.gain[j] = 1.0 / std::log2(j + 2.0);
-      t.idcg[j + 1] = t.idcg[j] + t.gain[j];
-    }
-    return t;
-  }();
-  return tab;
-}
 
-// The rules of a ground-truth pointer array over n rows: starts at 0, monotone,
-// no empty row; "" when fine.
-std::string gt_ptr_error(int64_t n, const int64_t* gt_ptr) {
-  if (gt_ptr[0] != 0) return "gt_ptr[0] must be 0";
-  for (int64_t i = 0; i < n; ++i) {
-    if (gt_ptr[i + 1] < gt_ptr[i]) return "gt_ptr not monotone at row " + std::to_string(i);
-    if (gt_ptr[i + 1] == gt_ptr[i]) return "row " + std::to_string(i) + " has no ground truth";
+// frecsys_recommend: the lists and (unless null) the scores go to the host.
+struct ListsOut : BehindScan {
+  int32_t* items;
+  float* scores;
+  int k;
+  ListsOut(int32_t* i, float* s, int k_) : items(i), scores(s), k(k_) {}
+  int run(frecsys_ctx* c, const int32_t* lists, const float* list_scores, int64_t r0,
+          int64_t cnt) override {
+    return copy_lists(c, items, scores, k, r0, cnt, lists, list_scores);
   }
-  return "";
-}
-
-// The argument checks frecsys_list_metrics and frecsys_rank_metrics share;
-// "" when fine.  n_items < 0: no upper bound on the ground-truth ids.
-std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
-                              const int32_t* k_list, int32_t nk, int64_t n_items,
-                              int32_t* max_k) {
-  if (n < 0 || !gt_ptr || !k_list) return "bad arguments (null gt_ptr / k_list, n < 0)";
-  if (nk < 1 || nk > kMetricMaxCutoffs)
-    return "nk must be in [1, " + std::to_string(kMetricMaxCutoffs) + "]";
-  int32_t mk = 0;
-  for (int32_t q = 0; q < nk; ++q) {
-    if (k_list[q] < 1 || k_list[q] > kMetricMaxK)
-      return "k_list[" + std::to_string(q) + "] must be in [1, " + std::to_string(kMetricMaxK) +
-             "]";
-    mk = std::max(mk, k_list[q]);
-  }
-  *max_k = mk;
-  const std::string e = gt_ptr_error(n, gt_ptr);
-  if (!e.empty()) return e;
-  if (n > 0 && !gt_items) return "null gt_items";
-  for (int64_t p = 0; p < gt_ptr[n]; ++p)
-    if (gt_items[p] < 0 || (n_items >= 0 && gt_items[p] >= n_items))
-      return "ground-truth id " + std::to_string(gt_items[p]) + " out of range";
-  return "";
-}
-
-// The ground truth as sets: every row ascending and distinct.  Rows are sorted
-// in place in a copy (a row already strictly ascending is left alone), on host
-// threads over nnz-balanced row ranges when there is enough of it, then
-// closed up over the dropped repeats; the result does not depend on the
-// thread count.
-void sorted_ground_truth(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
-                         std::vector<int64_t>* sp, std::vector<int32_t>* sg) {
-  const int64_t total = gt_ptr[n];
-  sg->assign(gt_items, gt_items + total);
-  sp->assign((size_t)n + 1, 0);
-  std::vector<int64_t> cnt((size_t)n);
-  int32_t* base = sg->data();
-  auto work = [&](int64_t a, int64_t b) {
-    for (int64_t i = a; i < b; ++i) {
-      int32_t* p = base + gt_ptr[i];
-      int32_t* e = base + gt_ptr[i + 1];
-      bool ascending = true;
-      for (int32_t* q = p + 1; q < e; ++q)
-        if (q[-1] >= q[0]) {
-          ascending = false;
-          break;
-        }
-      if (!ascending) {
-        std::sort(p, e);
-        e = std::unique(p, e);
-      }
-      cnt[(size_t)i] = e - p;
-    }
-  };
-  const int nt = total < (1 << 16)
-                     ? 1
-                     : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (nt == 1) {
-    work(0, n);
-  } else {
-    std::vector<int64_t> bounds((size_t)nt + 1);
-    partition_rows(n, gt_ptr, nt, bounds.data());
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(work, bounds[(size_t)t], bounds[(size_t)t + 1]);
-    for (auto& t : th) t.join();
-  }
-  int64_t w = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    if (w != gt_ptr[i]) std::memmove(base + w, base + gt_ptr[i], sizeof(int32_t) * (size_t)cnt[(size_t)i]);
-    w += cnt[(size_t)i];
-    (*sp)[(size_t)i + 1] = w;
-  }
-  sg->resize((size_t)w);
-}
+};
 
 // What the metric calls add to a ranking call.
 struct MetricsRequest {
@@ -401,7 +313,7 @@ struct MetricsRequest {
 // the device, rank_metrics_kernel reads them there and 2 nk floats per row go
 // to the host.  The order of its steps is the caller's: sort() before or
 // during the first scan, the regions where the call's layout has them.
-struct MetricsStage {
+struct MetricsStage final : BehindScan {
   const MetricsRequest& mt;
   const int64_t n;
   const size_t nk;
@@ -438,7 +350,7 @@ struct MetricsStage {
   }
   // rows [r0, r0 + cnt) of the call, their lists at `lists`; the metric rows
   // are on their way to the host when it returns (the caller synchronises)
-  int run(frecsys_ctx* c, const int32_t* lists, int64_t r0, int64_t cnt) {
+  int run(frecsys_ctx* c, const int32_t* lists, const float*, int64_t r0, int64_t cnt) override {
     ma.lists = lists;
     ma.r0 = r0;
     ma.n = cnt;
@@ -449,9 +361,20 @@ struct MetricsStage {
     HIP_TRY(c, to_host(c, mt.ndcg + r0 * nk, ma.ndcg, (size_t)cnt * nk));
     return FRECSYS_OK;
   }
+  // behind the scan: room for every id (repeats are dropped); the ground truth
+  // is sorted while the first batch is scanned, and uploaded behind it
+  size_t scan_bytes() const override { return nk * 8; }
+  void scan_carve(Carver& cv, int64_t nb) override {
+    carve_inputs(cv, (size_t)mt.gt_ptr[n]);
+    carve_rows(cv, nb);
+  }
+  int scan_overlap(frecsys_ctx* c) override {
+    sort();
+    return upload(c);
+  }
   // two double divisions per (row, cut-off); bytes: the lists and the ground
   // truth read, the metric rows written
-  void book(frecsys_ctx* c) const {
+  void book(frecsys_ctx* c) const override {
     add_work(c, "rank_metrics", 2.0 * (double)n * (double)nk,
              (double)n * ma.k * 4.0 + (double)sg.size() * 4.0 + ((double)n + 1.0) * 8.0 +
                  (double)n * (double)nk * 8.0,
@@ -459,60 +382,16 @@ struct MetricsStage {
   }
 };
 
-// What the MMR calls add to a ranking: the selection and where it goes (host).
-struct DiversifyRequest {
-  int32_t k;
-  float lam;
-  int32_t flags;
+// What the MMR and DPP calls add to a ranking: the selection and where it goes
+// (host; extra: the MMR values or gains, or nullptr; items null: it stays on
+// the device for QualityStage).
+struct PoolRequest {
+  int32_t k, flags;
   int32_t* items;
   float* scores;
-  float* mmr;  // or nullptr
+  float* extra;
 };
 
-// The arguments every MMR call checks first: 1 <= k <= pool <= 1024, lam in
-// [0, 1] (a NaN fails both comparisons), the flags.
-int check_diversify(frecsys_ctx* c, const std::string& w, int32_t k, int32_t pool, float lam,
-                    int32_t flags, int32_t known_flags) {
-  if (pool < 1 || pool > kDiversifyMaxPool)
-    return fail(c, FRECSYS_ERR_INVALID, w + "pool must be in [1, 1024]");
-  if (k < 1 || k > pool) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, pool]");
-  if (!(lam >= 0.0f && lam <= 1.0f))
-    return fail(c, FRECSYS_ERR_INVALID, w + "lam must be in [0, 1]");
-  if (flags & ~known_flags) return fail(c, FRECSYS_ERR_INVALID, w + "unknown flag");
-  return FRECSYS_OK;
-}
-
-// A pool array [n][pool] against a catalogue of m items: ids below m, finite
-// scores in the filled slots and, in normalised mode, a finite max - min per
-// row; "" when fine.
-std::string pool_error(const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
-                       int64_t m, bool raw) {
-  for (int64_t i = 0; i < n; ++i) {
-    float smax = -INFINITY, smin = INFINITY;
-    bool any = false;
-    for (int32_t b = 0; b < pool; ++b) {
-      const int32_t id = lists[i * pool + b];
-      if (id < 0) continue;
-      if (id >= m) return "item id " + std::to_string(id) + " out of range";
-      const float s = list_scores[i * pool + b];
-      if (!std::isfinite(s)) return "non-finite score in row " + std::to_string(i);
-      smax = std::fmax(smax, s);
-      smin = std::fmin(smin, s);
-      any = true;
-    }
-    if (any && !raw && !std::isfinite(smax - smin))
-      return "score range of row " + std::to_string(i) + " is not finite";
-  }
-  return "";
-}
-
-// The MMR selection behind pools of `pool` slots that are on the device:
-// div_gram_kernel writes the pool Gramians of a sub-batch of `gb` rows,
-// div_select_kernel reads them, and [cnt][k] outputs go to the host.  Per row
-// of a batch: the three output rows; per row of a sub-batch: the Gramian.  The
-// Gramians have a sub-batch of their own because they are 4 pool^2 bytes a
-// row -- 4 MiB at pool 1024, where they would cut the scan of
-// frecsys_recommend_diverse into batches of 59 rows, one 64-row block each.
 // FRECSYS_DIVERSIFY_VARIANT (read per call; changes no result bit): "gram"
 // forms the pool Gramians, "lazy" computes a Gramian row per step in the
 // selection and needs no Gramian workspace; unset: kDiversifyLazyDefault.
@@ -524,103 +403,6 @@ bool diversify_lazy() {
   return kDiversifyLazyDefault;
 }
 
-struct DiversifyStage {
-  const DiversifyRequest& rq;
-  const int64_t n;
-  int64_t gb = 1;
-  DiversifyArgs da{};
-
-  DiversifyStage(const frecsys_ctx* c, const DiversifyRequest& r, int64_t rows, int pool)
-      : rq(r), n(rows) {
-    da.Y = c->emb[1];
-    da.Dp = c->Dp;
-    da.pool = pool;
-    da.k = r.k;
-    da.lam = r.lam;
-    da.raw = (r.flags & FRECSYS_DIV_RAW_SCORES) != 0;
-    da.lazy = diversify_lazy();
-  }
-  static size_t out_bytes(int k) { return (size_t)k * 12; }
-  size_t gram_bytes() const { return da.lazy ? 0 : (size_t)da.pool * da.pool * 4; }
-  // nb rows of a batch, their Gramians in sub-batches within `budget` bytes
-  // (at least one row)
-  void carve_rows(Carver& cv, int64_t nb, size_t budget) {
-    gb = da.lazy ? nb
-                 : std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(budget / gram_bytes())));
-    da.G = cv.take_if<float>(!da.lazy, (size_t)gb * da.pool * da.pool);
-    da.out_items = cv.take<int32_t>((size_t)nb * da.k);
-    da.out_scores = cv.take<float>((size_t)nb * da.k);
-    da.out_mmr = cv.take_if<float>(rq.mmr != nullptr, (size_t)nb * da.k);
-  }
-  // rows [r0, r0 + cnt) of the call, their pools at ids / pool_scores; the
-  // outputs are on their way to the host when it returns (the caller
-  // synchronises)
-  int run(frecsys_ctx* c, const int32_t* ids, const float* pool_scores, int64_t r0, int64_t cnt) {
-    const size_t k = (size_t)da.k, P = (size_t)da.pool;
-    DiversifyArgs sub = da;
-    for (int64_t s0 = 0; s0 < cnt; s0 += gb) {  // two timed launches per sub-batch
-      sub.n = std::min(gb, cnt - s0);
-      sub.ids = ids + (size_t)s0 * P;
-      sub.pool_scores = pool_scores + (size_t)s0 * P;
-      sub.out_items = da.out_items + (size_t)s0 * k;
-      sub.out_scores = da.out_scores + (size_t)s0 * k;
-      sub.out_mmr = da.out_mmr ? da.out_mmr + (size_t)s0 * k : nullptr;
-      if (!da.lazy) {
-        ScopedTimer t(c, "diversify.gram");
-        HIP_TRY(c, launch_diversify_gram(sub, c->stream));
-        t.stop();
-      }
-      {
-        ScopedTimer t(c, "diversify.select");
-        HIP_TRY(c, launch_diversify_select(sub, c->stream));
-        t.stop();
-      }
-    }
-    if (!rq.items) return FRECSYS_OK;  // the selection stays on the device (QualityStage reads it)
-    HIP_TRY(c, to_host(c, rq.items + r0 * k, da.out_items, (size_t)cnt * k));
-    HIP_TRY(c, to_host(c, rq.scores + r0 * k, da.out_scores, (size_t)cnt * k));
-    if (rq.mmr) HIP_TRY(c, to_host(c, rq.mmr + r0 * k, da.out_mmr, (size_t)cnt * k));
-    return FRECSYS_OK;
-  }
-  // flops at the logical dim: the lower triangle of every pool Gramian, then
-  // per step and slot two multiplies and a maximum, a multiply and a
-  // subtraction; bytes: the pool's item rows gathered once, the Gramian
-  // written, k of its rows and the pool read by the selection, the outputs
-  void book(frecsys_ctx* c) const {
-    const double P = da.pool, k = da.k, d = c->dim;
-    if (da.lazy)  // the norms, then per step one row of products: the item rows read k + 1 times
-      add_work(c, "diversify", (double)n * (2.0 * (k + 1.0) * P * d + 5.0 * k * P),
-               (double)n * ((k + 1.0) * P * d * 4.0 + P * 8.0 + k * (rq.mmr ? 12.0 : 8.0)), n);
-    else
-      add_work(c, "diversify", (double)n * (P * (P + 1.0) * d + 5.0 * k * P),
-               (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 +
-                            k * (rq.mmr ? 12.0 : 8.0)),
-               n);
-  }
-};
-
-// What the DPP calls add to a ranking: the selection and where it goes (host).
-struct DppRequest {
-  int32_t k;
-  float theta, eps;
-  int32_t flags;
-  int32_t* items;
-  float* scores;
-  float* gain;  // or nullptr
-};
-
-// The arguments every DPP call checks first: the MMR calls' common cases (k,
-// pool, the flags), then theta finite and >= 0 and eps in (0, 1] (a NaN fails
-// both comparisons).
-int check_dpp(frecsys_ctx* c, const std::string& w, int32_t k, int32_t pool, float theta, float eps,
-              int32_t flags, int32_t known_flags) {
-  if (int rc = check_diversify(c, w, k, pool, 0.0f, flags, known_flags)) return rc;
-  if (!(theta >= 0.0f && std::isfinite(theta)))
-    return fail(c, FRECSYS_ERR_INVALID, w + "theta must be finite and >= 0");
-  if (!(eps > 0.0f && eps <= 1.0f)) return fail(c, FRECSYS_ERR_INVALID, w + "eps must be in (0, 1]");
-  return FRECSYS_OK;
-}
-
 // FRECSYS_DPP_FACTOR (read per call; changes no result bit): "ws" keeps the
 // factor C in the workspace at every shape; unset: in LDS where it fits
 // (dpp_factor_in_lds).
@@ -629,124 +411,145 @@ bool dpp_factor_ws(int pool, int k) {
   return (v && !strcmp(v, "ws")) || !dpp_factor_in_lds(pool, k);
 }
 
-// The DPP selection behind pools of `pool` slots that are on the device:
-// div_gram_kernel writes the pool Gramians of a sub-batch of `gb` rows (as for
-// DiversifyStage, and for its reason), dpp_select_kernel reads them, and
-// [cnt][k] outputs go to the host.  Per row of a batch: the three output rows;
-// per row of a sub-batch: the Gramian and, where the factor does not fit LDS,
-// its 4 k pool bytes.
-struct DppStage {
-  const DppRequest& rq;
+// The selection behind pools of `pool` slots on the device, MMR
+// (div_select_kernel) or DPP (dpp_select_kernel): div_gram_kernel writes the
+// pool Gramians of a sub-batch of `gb` rows, the select kernel reads them, and
+// [cnt][k] outputs go to the host.  The Gramians have a sub-batch of their own
+// because they are 4 pool^2 bytes a row -- 4 MiB at pool 1024, where they
+// would cut the scan of frecsys_recommend_diverse into batches of 59 rows, one
+// 64-row block each.  The lazy MMR variant has no Gramian and one sub-batch;
+// where the DPP factor does not fit LDS, its 4 k pool bytes lie beside the
+// Gramian.
+struct PoolStage final : BehindScan {
+  const PoolRequest rq;
   const int64_t n;
+  const bool dpp, ws;        // the DPP selection; its factor in the workspace
   int64_t gb = 1;
-  bool ws;
-  DiversifyArgs ga{};  // the Gramian launch
+  DiversifyArgs ga{};        // the Gramian launch and the MMR selection
   DppArgs pa{};
+  float* d_extra = nullptr;  // the batch's third output row
 
-  DppStage(const frecsys_ctx* c, const DppRequest& r, int64_t rows, int pool)
-      : rq(r), n(rows), ws(r.k >= 1 && dpp_factor_ws(pool, r.k)) {
+  // x: lam (MMR; eps unused) or theta (DPP)
+  PoolStage(const frecsys_ctx* c, const PoolRequest& r, int64_t rows, int pool, bool is_dpp,
+            float x, float eps)
+      : rq(r), n(rows), dpp(is_dpp), ws(is_dpp && dpp_factor_ws(pool, r.k)) {
     ga.Y = c->emb[1];
     ga.Dp = c->Dp;
     ga.pool = pa.pool = pool;
     ga.k = pa.k = r.k;
-    pa.theta = r.theta;
-    pa.eps = r.eps;
-    pa.raw = (r.flags & FRECSYS_DIV_RAW_SCORES) != 0;
+    (dpp ? pa.theta : ga.lam) = x;
+    pa.eps = eps;
+    (dpp ? pa.raw : ga.raw) = raw();
+    ga.lazy = !dpp && diversify_lazy();
   }
-  static size_t out_bytes(int k) { return (size_t)k * 12; }
-  // per row of a sub-batch
+  bool raw() const { return (rq.flags & FRECSYS_DIV_RAW_SCORES) != 0; }
+  size_t scan_bytes() const override { return (size_t)ga.k * 12; }
+  // per row of a sub-batch (0: no sub-batches)
   size_t sub_bytes() const {
-    return (size_t)pa.pool * pa.pool * 4 + (ws ? dpp_factor_bytes(pa.pool, pa.k) : 0);
+    return ga.lazy ? 0 : (size_t)ga.pool * ga.pool * 4 + (ws ? dpp_factor_bytes(ga.pool, ga.k) : 0);
   }
-  // nb rows of a batch, their Gramians and factors in sub-batches within
-  // `budget` bytes (at least one row)
+  // nb rows: sub-batches within `budget` bytes (at least one row), the outputs
   void carve_rows(Carver& cv, int64_t nb, size_t budget) {
-    gb = std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(budget / sub_bytes())));
-    ga.G = cv.take<float>((size_t)gb * pa.pool * pa.pool);
-    pa.C = cv.take_if<float>(ws, (size_t)gb * pa.k * pa.pool);
-    pa.out_items = cv.take<int32_t>((size_t)nb * pa.k);
-    pa.out_scores = cv.take<float>((size_t)nb * pa.k);
-    pa.out_gain = cv.take_if<float>(rq.gain != nullptr, (size_t)nb * pa.k);
+    const size_t sub = sub_bytes(), k = (size_t)ga.k, P = (size_t)ga.pool;
+    gb = sub ? std::min<int64_t>(nb, std::max<int64_t>(1, (int64_t)(budget / sub))) : nb;
+    ga.G = cv.take_if<float>(!ga.lazy, (size_t)gb * P * P);
+    pa.C = cv.take_if<float>(ws, (size_t)gb * k * P);
+    ga.out_items = cv.take<int32_t>((size_t)nb * k);
+    ga.out_scores = cv.take<float>((size_t)nb * k);
+    d_extra = cv.take_if<float>(rq.extra != nullptr, (size_t)nb * k);
   }
-  // rows [r0, r0 + cnt) of the call, their pools at ids / pool_scores; the
-  // outputs are on their way to the host when it returns (the caller
-  // synchronises)
-  int run(frecsys_ctx* c, const int32_t* ids, const float* pool_scores, int64_t r0, int64_t cnt) {
-    const size_t k = (size_t)pa.k, P = (size_t)pa.pool;
+  // behind the scan: outside its per-row budget, within a budget of their own
+  void scan_carve(Carver& cv, int64_t nb) override { carve_rows(cv, nb, workspace_budget()); }
+  // rows [r0, r0 + cnt) of the call, their pools at ids / pool_scores: per
+  // sub-batch two timed launches; the outputs are on their way to the host
+  // when it returns (the caller synchronises)
+  int run(frecsys_ctx* c, const int32_t* ids, const float* pool_scores, int64_t r0,
+          int64_t cnt) override {
+    const size_t k = (size_t)ga.k, P = (size_t)ga.pool;
     DiversifyArgs g = ga;
-    DppArgs sub = pa;
-    sub.G = ga.G;
-    for (int64_t s0 = 0; s0 < cnt; s0 += gb) {  // two timed launches per sub-batch
-      g.n = sub.n = std::min(gb, cnt - s0);
-      g.ids = sub.ids = ids + (size_t)s0 * P;
-      g.pool_scores = sub.pool_scores = pool_scores + (size_t)s0 * P;
-      g.out_items = sub.out_items = pa.out_items + (size_t)s0 * k;
-      g.out_scores = sub.out_scores = pa.out_scores + (size_t)s0 * k;
-      sub.out_gain = pa.out_gain ? pa.out_gain + (size_t)s0 * k : nullptr;
-      {
+    DppArgs p = pa;
+    p.G = ga.G;
+    for (int64_t s0 = 0; s0 < cnt; s0 += gb) {
+      g.n = p.n = std::min(gb, cnt - s0);
+      g.ids = p.ids = ids + (size_t)s0 * P;
+      g.pool_scores = p.pool_scores = pool_scores + (size_t)s0 * P;
+      g.out_items = p.out_items = ga.out_items + (size_t)s0 * k;
+      g.out_scores = p.out_scores = ga.out_scores + (size_t)s0 * k;
+      g.out_mmr = p.out_gain = d_extra ? d_extra + (size_t)s0 * k : nullptr;
+      if (ga.G) {
         ScopedTimer t(c, "diversify.gram");
         HIP_TRY(c, launch_diversify_gram(g, c->stream));
         t.stop();
       }
-      {
-        ScopedTimer t(c, "dpp.select");
-        HIP_TRY(c, launch_dpp_select(sub, c->stream));
-        t.stop();
-      }
+      ScopedTimer t(c, dpp ? "dpp.select" : "diversify.select");
+      HIP_TRY(c, dpp ? launch_dpp_select(p, c->stream) : launch_diversify_select(g, c->stream));
+      t.stop();
     }
-    HIP_TRY(c, to_host(c, rq.items + r0 * k, pa.out_items, (size_t)cnt * k));
-    HIP_TRY(c, to_host(c, rq.scores + r0 * k, pa.out_scores, (size_t)cnt * k));
-    if (rq.gain) HIP_TRY(c, to_host(c, rq.gain + r0 * k, pa.out_gain, (size_t)cnt * k));
+    if (!rq.items) return FRECSYS_OK;
+    HIP_TRY(c, to_host(c, rq.items + r0 * k, ga.out_items, (size_t)cnt * k));
+    HIP_TRY(c, to_host(c, rq.scores + r0 * k, ga.out_scores, (size_t)cnt * k));
+    if (rq.extra) HIP_TRY(c, to_host(c, rq.extra + r0 * k, d_extra, (size_t)cnt * k));
     return FRECSYS_OK;
   }
   // flops at the logical dim: the lower triangle of every pool Gramian, then
-  // the factor's chains, sum over t < k of 2 t pool, every step booked as a
-  // DPP step; bytes: the pool's item rows gathered once, the Gramian written,
-  // k of its rows and the pool read by the selection, the factor written once
-  // and read sum over t < k of t pool words, the outputs
-  void book(frecsys_ctx* c) const {
-    const double P = pa.pool, k = pa.k, d = c->dim;
-    add_work(c, "dpp", (double)n * (P * (P + 1.0) * d + k * (k - 1.0) * P),
-             (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 + k * P * 4.0 +
-                          k * (k - 1.0) * P * 2.0 + k * (rq.gain ? 12.0 : 8.0)),
-             n);
+  // MMR: per step and slot two multiplies and a maximum, a multiply and a
+  // subtraction; DPP: the factor's chains, sum over t < k of 2 t pool, every
+  // step booked as a DPP step.  Bytes: the pool's item rows gathered once, the
+  // Gramian written, k of its rows and the pool read by the selection, the
+  // outputs; DPP: the factor written once and read sum over t < k of t pool
+  // words; lazy: the norms, then per step one row of products, so the item
+  // rows are read k + 1 times
+  void book(frecsys_ctx* c) const override {
+    const double P = ga.pool, k = ga.k, d = c->dim, out = k * (rq.extra ? 12.0 : 8.0);
+    if (dpp)
+      add_work(c, "dpp", (double)n * (P * (P + 1.0) * d + k * (k - 1.0) * P),
+               (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 + k * P * 4.0 +
+                            k * (k - 1.0) * P * 2.0 + out),
+               n);
+    else if (ga.lazy)
+      add_work(c, "diversify", (double)n * (2.0 * (k + 1.0) * P * d + 5.0 * k * P),
+               (double)n * ((k + 1.0) * P * d * 4.0 + P * 8.0 + out), n);
+    else
+      add_work(c, "diversify", (double)n * (P * (P + 1.0) * d + 5.0 * k * P),
+               (double)n * (P * d * 4.0 + P * P * 4.0 + k * P * 4.0 + P * 8.0 + out), n);
   }
 };
 
-// What the quality calls add to a ranking: the cut-offs, the item weights of
-// novelty (or nullptr) and where the results go (host; each may be nullptr).
-struct QualityRequest {
-  const int32_t* k_list;
-  int32_t nk;
-  const float* item_weight;
-  float* ild;
-  float* novelty;
-  int64_t* exposure;
-};
-
-// The arguments every quality call checks, in this order: the cut-offs (each in
-// [1, max_k]), the outputs (`others`: the call has outputs beside these three),
-// novelty and its weights (one with the other, every weight finite); "" when
-// fine.  tools/model_capi.cc restates these checks in the model layer's words,
-// in the same order: the two lists stay in step.
-std::string quality_args_error(const QualityRequest& q, int32_t max_k, int64_t n_items,
-                               bool others) {
-  if (!q.k_list || q.nk < 1 || q.nk > kMetricMaxCutoffs)
-    return "k_list must hold 1 to " + std::to_string(kMetricMaxCutoffs) + " cut-offs";
-  for (int32_t i = 0; i < q.nk; ++i)
-    if (q.k_list[i] < 1 || q.k_list[i] > max_k)
-      return "cut-offs must be in [1, " + std::to_string(max_k) + "]";
-  if (!q.ild && !q.novelty && !q.exposure && !others) return "every output is null";
-  if (q.novelty && !q.item_weight) return "novelty needs item_weight";
-  if (q.item_weight && !q.novelty) return "item_weight without a novelty output";
-  if (q.item_weight)
-    for (int64_t j = 0; j < n_items; ++j)
-      if (!std::isfinite(q.item_weight[j]))
-        return "item_weight[" + std::to_string(j) + "] is not finite";
-  return "";
-}
-int32_t max_cutoff(const int32_t* k_list, int32_t nk) {
-  return *std::max_element(k_list, k_list + nk);
+// frecsys_diversify and frecsys_diversify_dpp behind their first check.  Per
+// row of a batch: its pool (ids and scores), its sub-batch bytes and its
+// outputs; at least one row per batch, and one sub-batch per batch.
+int pools_impl(frecsys_ctx* c, const std::string& w, const int32_t* lists, const float* list_scores,
+               PoolStage& st) {
+  const int64_t n = st.n;
+  const int pool = st.ga.pool;
+  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
+  if (n == 0) return FRECSYS_OK;
+  if (!lists || !list_scores || !st.rq.items || !st.rq.scores)
+    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
+  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
+  const std::string e = pool_error(lists, list_scores, n, pool, c->n[1], st.raw());
+  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t budget = workspace_budget();
+  const size_t per_row = (size_t)pool * 8 + st.sub_bytes() + st.scan_bytes();
+  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(budget / per_row)));
+  int32_t* d_ids = nullptr;
+  float* d_sc = nullptr;
+  int rc = Carver::run(c, [&](Carver& cv) {
+    d_ids = cv.take<int32_t>((size_t)nb * pool);
+    d_sc = cv.take<float>((size_t)nb * pool);
+    st.carve_rows(cv, nb, std::max(budget, (size_t)nb * st.sub_bytes()));
+  });
+  if (rc) return rc;
+  for (int64_t r0 = 0; r0 < n; r0 += nb) {
+    const int64_t cnt = std::min(nb, n - r0);
+    HIP_TRY(c, to_device(c, d_ids, lists + r0 * pool, (size_t)cnt * pool));
+    HIP_TRY(c, to_device(c, d_sc, list_scores + r0 * pool, (size_t)cnt * pool));
+    if ((rc = st.run(c, d_ids, d_sc, r0, cnt))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  st.book(c);
+  return FRECSYS_OK;
 }
 
 // The list quality behind lists of list_k slots that are on the device:
@@ -770,12 +573,10 @@ struct QualityStage {
     ea.m = m;
   }
   size_t row_bytes() const { return nk * 8; }
-  void carve_rows(Carver& cv, int64_t nb) {
+  // per row of a batch, then outside the per-row budget
+  void carve(Carver& cv, int64_t nb) {
     qa.ild = cv.take_if<float>(rq.ild != nullptr, (size_t)nb * nk);
     qa.novelty = cv.take_if<float>(rq.novelty != nullptr, (size_t)nb * nk);
-  }
-  // outside the per-row budget
-  void carve_inputs(Carver& cv) {
     qa.k_list = ea.k_list = cv.take<int32_t>(nk);
     qa.weight = cv.take_if<float>(rq.item_weight != nullptr, (size_t)m);
     ea.counts = cv.take_if<unsigned long long>(rq.exposure != nullptr, nk * (size_t)m);
@@ -831,147 +632,121 @@ struct QualityStage {
   }
 };
 
-// The ranking behind frecsys_recommend (mt == nullptr: the lists and scores go
-// to the host), frecsys_rank_metrics (mt given: every batch's lists stay on
-// the device and the metric rows go to the host) and frecsys_recommend_diverse
-// (dv given: k is the pool, every batch's lists and scores stay on the device
-// and the selection goes to the host).  The scan is the same launch with the
-// same workspace layout in all three; the ground truth, the tables and the
-// metric outputs, or the pool Gramians and the selection, lie behind it.
-// frecsys_recommend_dpp (dp given) is frecsys_recommend_diverse's shape with the
-// DPP stage in the MMR stage's place; dp comes with none of mt, dv and ql.
-int recommend_impl(frecsys_ctx* c, const char* what, int32_t side, const int64_t* rows,
-                   int64_t n_rows, int32_t k, int32_t flags, const uint8_t* item_mask,
-                   int32_t* items, float* scores, const MetricsRequest* mt,
-                   const DiversifyRequest* dv = nullptr, const QualityRequest* ql = nullptr,
-                   const DppRequest* dp = nullptr) {
-  const std::string w = std::string(what) + ": ";
-  int rc = check_query(c, w, side, FRECSYS_SIDE_EVAL, &k, flags, FRECSYS_REC_EXCLUDE_HISTORY);
+// frecsys_rank_quality behind the scan: the selection (with a pool), then the
+// metrics (with a ground truth) and the quality of the lists it left.
+struct QualityBehind : BehindScan {
+  std::optional<PoolStage> ds;
+  std::optional<MetricsStage> ms;
+  QualityStage qs;
+
+  QualityBehind(const frecsys_ctx* c, const QualityRequest& ql, int64_t n, int list_k)
+      : qs(c, ql, n, list_k) {}
+  size_t scan_bytes() const override {
+    return (ms ? ms->scan_bytes() : 0) + (ds ? ds->scan_bytes() : 0) + qs.row_bytes();
+  }
+  void scan_carve(Carver& cv, int64_t nb) override {
+    if (ms) ms->scan_carve(cv, nb);
+    if (ds) ds->scan_carve(cv, nb);
+    qs.carve(cv, nb);
+  }
+  int scan_upload(frecsys_ctx* c) override { return qs.upload(c); }
+  int scan_overlap(frecsys_ctx* c) override { return ms ? ms->scan_overlap(c) : FRECSYS_OK; }
+  int run(frecsys_ctx* c, const int32_t* lists, const float* scores, int64_t r0,
+          int64_t cnt) override {
+    int rc;
+    if (ds) {
+      if ((rc = ds->run(c, lists, scores, r0, cnt))) return rc;
+      lists = ds->ga.out_items;
+    }
+    if (ms && (rc = ms->run(c, lists, nullptr, r0, cnt))) return rc;
+    return qs.run(c, lists, qs.qa.k, r0, cnt);
+  }
+  int finish(frecsys_ctx* c) override {  // the counts, between the stages' work and their own
+    if (ms) ms->book(c);
+    if (ds) ds->book(c);
+    if (int rc = qs.finish(c)) return rc;
+    qs.book(c);
+    return FRECSYS_OK;
+  }
+  void no_rows(const frecsys_ctx* c) const override {
+    if (qs.rq.exposure)
+      std::memset(qs.rq.exposure, 0, sizeof(int64_t) * qs.nk * (size_t)c->n[1]);
+  }
+};
+
+// The eligibility words and the query row ids of a scan, uploaded.
+int upload_query(frecsys_ctx* c, const RecommendArgs& a, const uint8_t* mask, const int64_t* rows,
+                 int64_t n) {
+  const std::vector<uint32_t> maskw = item_mask_words(a.m, mask);
+  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // maskw goes out of scope
+  return FRECSYS_OK;
+}
+
+// A ranking of the items for n query rows of a side; k is the length of the
+// scan's lists (the pool where a selection follows).  scan_impl runs it.
+struct ScanCall {
+  std::string w;
+  int32_t side;
+  const int64_t* rows;
+  int64_t n;
+  int32_t k;
+  int32_t flags;
+  const uint8_t* item_mask;
+};
+// The checks, before any device call (null_outputs is the caller's verdict on
+// its own outputs, gt or nullptr a ground truth), the return for zero rows,
+// and the device part: the same launch and workspace layout whatever lies
+// behind the scan.  A batch's lists and scores stay on the device for `behind`.
+int scan_impl(frecsys_ctx* c, const ScanCall& q, bool null_outputs, const MetricsRequest* gt,
+              BehindScan& behind) {
+  int rc = check_query(c, q.w, q.side, FRECSYS_SIDE_EVAL, &q.k, q.flags, FRECSYS_REC_EXCLUDE_HISTORY);
   if (rc) return rc;
-  if (n_rows < 0 || (n_rows > 0 && (ql   ? false  // frecsys_rank_quality checks its own
-                                    : mt ? (!mt->recall || !mt->ndcg)
-                                    : dv ? (!dv->items || !dv->scores)
-                                    : dp ? (!dp->items || !dp->scores)
-                                         : !items)))
-    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
-  const bool exclude = (flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
-  if ((rc = check_rows(c, w, side, FRECSYS_SIDE_ITEM, exclude, rows, n_rows))) return rc;
-  const int64_t m = c->n[1], n = n_rows;
-  if (mt) {
+  if (q.n < 0 || (q.n > 0 && null_outputs))
+    return fail(c, FRECSYS_ERR_INVALID, q.w + "bad arguments (null outputs)");
+  const bool exclude = (q.flags & FRECSYS_REC_EXCLUDE_HISTORY) != 0;
+  if ((rc = check_rows(c, q.w, q.side, FRECSYS_SIDE_ITEM, exclude, q.rows, q.n))) return rc;
+  const int64_t m = c->n[1], n = q.n;
+  if (gt) {
     int32_t mk = 0;
-    const std::string e = metric_args_error(n, mt->gt_ptr, mt->gt_items, mt->k_list, mt->nk, m, &mk);
-    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
+    const std::string e = metric_args_error(n, gt->gt_ptr, gt->gt_items, gt->k_list, gt->nk, m, &mk);
+    if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, q.w + e);
   }
   if (n == 0) {
-    if (ql && ql->exposure) std::memset(ql->exposure, 0, sizeof(int64_t) * (size_t)ql->nk * (size_t)m);
+    behind.no_rows(c);
     return FRECSYS_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  // the lists the stages behind the scan read: the selection's k slots when
-  // there is one (only a quality call has both dv and mt), else the scan's
-  const int list_k = dv ? dv->k : k;
-  const MetricsRequest none{};
-  MetricsStage ms(mt ? *mt : none, n, list_k);
-  const DiversifyRequest no_dv{};
-  DiversifyStage ds(c, dv ? *dv : no_dv, n, k);
-  const QualityRequest no_ql{};
-  QualityStage qs(c, ql ? *ql : no_ql, n, list_k);
-  const DppRequest no_dp{};
-  DppStage ps(c, dp ? *dp : no_dp, n, k);
-  // per row of a batch beside the scan's own: history bits, the two metric
-  // rows, the pool Gramian and the selection, the two quality rows
-  const ScanPlan p =
-      scan_plan(c, k, m, n,
-                (exclude ? (size_t)recommend_words(m) * 4 : 0) + ms.nk * 8 +
-                    (dv ? DiversifyStage::out_bytes(dv->k) : 0) + (ql ? qs.row_bytes() : 0) +
-                    (dp ? DppStage::out_bytes(dp->k) : 0));
+  // per row of a batch beside the scan's own: history bits, and what is behind
+  const ScanPlan p = scan_plan(
+      c, q.k, m, n, (exclude ? (size_t)recommend_words(m) * 4 : 0) + behind.scan_bytes());
   c->rec_splits = p.splits;
-  RecommendArgs a = scan_args(c, side, FRECSYS_SIDE_ITEM, k, p.splits, exclude);
+  RecommendArgs a = scan_args(c, q.side, FRECSYS_SIDE_ITEM, q.k, p.splits, exclude);
   rc = Carver::run(c, [&](Carver& cv) {
-    carve_scan(cv, a, p, rows != nullptr, n);
-    if (mt) {
-      ms.carve_inputs(cv, (size_t)mt->gt_ptr[n]);  // room for every id; repeats are dropped
-      ms.carve_rows(cv, p.nb);
-    }
-    // outside the scan's per-row budget: the Gramians of a sub-batch, within a
-    // budget of their own
-    if (dv) ds.carve_rows(cv, p.nb, workspace_budget());
-    if (dp) ps.carve_rows(cv, p.nb, workspace_budget());
-    if (ql) {
-      qs.carve_rows(cv, p.nb);
-      qs.carve_inputs(cv);
-    }
+    carve_scan(cv, a, p, q.rows != nullptr, n);
+    behind.scan_carve(cv, p.nb);
   });
   if (rc) return rc;
-  const std::vector<uint32_t> maskw = item_mask_words(m, item_mask);
-  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
-  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
-  if (ql && (rc = qs.upload(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = behind.scan_upload(c))) return rc;
+  if ((rc = upload_query(c, a, q.item_mask, q.rows, n))) return rc;
   for (int64_t r0 = 0; r0 < n; r0 += p.nb) {  // one timed launch group per row batch
     a.r0 = r0;
     a.n = std::min(p.nb, n - r0);
     ScopedTimer t(c, "recommend");
     HIP_TRY(c, launch_recommend(a, c->stream));
-    if (mt && r0 == 0) {
-      // the ground truth is sorted on the host while the first batch is
-      // scanned, and uploaded behind it with the tables and the cut-offs
-      t.mark();
-      ms.sort();
-      if ((rc = ms.upload(c))) return rc;
-      t.finish();
-    } else {
-      t.stop();
-    }
-    if (ql) {
-      // the selection (when asked), then the metrics (when there is a ground
-      // truth) and the quality of the same lists, where the stage before left them
-      const int32_t* lists = a.out_items;
-      if (dv) {
-        if ((rc = ds.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
-        lists = ds.da.out_items;
-      }
-      if (mt && (rc = ms.run(c, lists, r0, a.n))) return rc;
-      if ((rc = qs.run(c, lists, list_k, r0, a.n))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (mt) {
-      if ((rc = ms.run(c, a.out_items, r0, a.n))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (dv) {
-      if ((rc = ds.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (dp) {
-      if ((rc = ps.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if ((rc = fetch_lists(c, items, scores, k, r0, a.n, a.out_items, a.out_scores))) {
-      return rc;
-    }
+    t.mark();
+    if (r0 == 0 && (rc = behind.scan_overlap(c))) return rc;
+    t.finish();
+    if ((rc = behind.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   // scoring flops at the logical dim; bytes: both tables read once, lists written
   const double dd = c->dim;
   add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
-           ((double)n + (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
-  if (mt) ms.book(c);
-  if (dv) ds.book(c);
-  if (dp) ps.book(c);
-  if (ql) {
-    if ((rc = qs.finish(c))) return rc;
-    qs.book(c);
-  }
-  return FRECSYS_OK;
+           ((double)n + (double)m) * dd * 4.0 + (double)n * q.k * 8.0, n);
+  return behind.finish(c);
 }
-
-// splitmix64's finaliser and its increment: the generator of the sampled
-// negatives (include/frecsys_hip.h), uint64 arithmetic that wraps.
-inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 
 // What frecsys_rank_candidates_metrics and frecsys_sampled_metrics share.
 struct CandMetricsCall {
@@ -1016,11 +791,6 @@ int cand_metrics_check(frecsys_ctx* c, const std::string& w, const CandMetricsCa
       metric_args_error(q.n, q.mt.gt_ptr, q.mt.gt_items, q.mt.k_list, q.mt.nk, c->n[1], &mk);
   if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
   return FRECSYS_OK;
-}
-
-// Whole-pool rule of a row with pool size E among M maskable ids.
-inline bool whole_pool_row(int64_t n_neg, int64_t E, int64_t M) {
-  return 2 * n_neg > E || 64 * E < M;
 }
 
 // The device part of both: per row batch the candidate ids are uploaded
@@ -1099,7 +869,7 @@ int cand_metrics_impl(frecsys_ctx* c, const std::string& w, const CandMetricsCal
       HIP_TRY(c, launch_rank_candidates(a, c->stream));
       t.stop();
     }
-    return ms.run(c, a.out_items, s0, a.n);
+    return ms.run(c, a.out_items, nullptr, s0, a.n);
   };
   double pairs = 0.0;
   if (!sampled) {
@@ -1213,8 +983,9 @@ extern "C" {
 int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows, int32_t k,
                       int32_t flags, const uint8_t* item_mask, int32_t* items, float* scores) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend: null context");
-  return recommend_impl(c, "recommend", side, rows, n_rows, k, flags, item_mask, items, scores,
-                        nullptr);
+  ListsOut out(items, scores, k);
+  return scan_impl(c, {"recommend: ", side, rows, n_rows, k, flags, item_mask}, !items, nullptr,
+                   out);
 }
 
 int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
@@ -1223,11 +994,11 @@ int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int6
                          float* ndcg) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "rank_metrics: null context");
   int32_t k = 0;  // the list length is the largest cut-off
-  const int rc = check_cutoffs(c, "rank_metrics: ", k_list, nk, &k);
-  if (rc) return rc;
+  if (int rc = check_cutoffs(c, "rank_metrics: ", k_list, nk, &k)) return rc;
   const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
-  return recommend_impl(c, "rank_metrics", side, rows, n_rows, k, flags, item_mask, nullptr, nullptr,
-                        &mt);
+  MetricsStage ms(mt, n_rows, k);
+  return scan_impl(c, {"rank_metrics: ", side, rows, n_rows, k, flags, item_mask},
+                   !recall || !ndcg, &mt, ms);
 }
 
 int frecsys_recommend_diverse(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
@@ -1235,13 +1006,13 @@ int frecsys_recommend_diverse(frecsys_ctx* c, int32_t side, const int64_t* rows,
                               const uint8_t* item_mask, int32_t* items, float* scores,
                               float* mmr) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend_diverse: null context");
-  const int rc = check_diversify(c, "recommend_diverse: ", k, pool, lam, flags,
-                                 FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  const DiversifyRequest dv{k, lam, flags, items, scores, mmr};
-  return recommend_impl(c, "recommend_diverse", side, rows, n_rows, pool,
-                        flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask, nullptr, nullptr, nullptr,
-                        &dv);
+  const std::string w = "recommend_diverse: ";
+  if (int rc = check_diversify(c, w, k, pool, lam, flags,
+                               FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES))
+    return rc;
+  PoolStage ds(c, {k, flags, items, scores, mmr}, n_rows, pool, /*dpp=*/false, lam, 0.0f);
+  return scan_impl(c, {w, side, rows, n_rows, pool, flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask},
+                   !items || !scores, nullptr, ds);
 }
 
 int frecsys_diversify(frecsys_ctx* c, const int32_t* lists, const float* list_scores, int64_t n,
@@ -1249,54 +1020,22 @@ int frecsys_diversify(frecsys_ctx* c, const int32_t* lists, const float* list_sc
                       float* scores, float* mmr) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "diversify: null context");
   const std::string w = "diversify: ";
-  int rc = check_diversify(c, w, k, pool, lam, flags, FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n == 0) return FRECSYS_OK;
-  if (!lists || !list_scores || !items || !scores)
-    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
-  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
-  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
-  const std::string e = pool_error(lists, list_scores, n, pool, c->n[1], raw);
-  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
-  HIP_TRY(c, hipSetDevice(c->device));
-  const DiversifyRequest dv{k, lam, flags, items, scores, mmr};
-  DiversifyStage ds(c, dv, n, pool);
-  // per row of a batch: its pool (ids and scores), its Gramian and its
-  // outputs; at least one row per batch, and one Gramian sub-batch per batch
-  const size_t budget = workspace_budget();
-  const size_t per_row = (size_t)pool * 8 + ds.gram_bytes() + DiversifyStage::out_bytes(k);
-  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(budget / per_row)));
-  int32_t* d_ids = nullptr;
-  float* d_sc = nullptr;
-  rc = Carver::run(c, [&](Carver& cv) {
-    d_ids = cv.take<int32_t>((size_t)nb * pool);
-    d_sc = cv.take<float>((size_t)nb * pool);
-    ds.carve_rows(cv, nb, std::max(budget, (size_t)nb * ds.gram_bytes()));
-  });
-  if (rc) return rc;
-  for (int64_t r0 = 0; r0 < n; r0 += nb) {
-    const int64_t cnt = std::min(nb, n - r0);
-    HIP_TRY(c, to_device(c, d_ids, lists + r0 * pool, (size_t)cnt * pool));
-    HIP_TRY(c, to_device(c, d_sc, list_scores + r0 * pool, (size_t)cnt * pool));
-    if ((rc = ds.run(c, d_ids, d_sc, r0, cnt))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  ds.book(c);
-  return FRECSYS_OK;
+  if (int rc = check_diversify(c, w, k, pool, lam, flags, FRECSYS_DIV_RAW_SCORES)) return rc;
+  PoolStage ds(c, {k, flags, items, scores, mmr}, n, pool, /*dpp=*/false, lam, 0.0f);
+  return pools_impl(c, w, lists, list_scores, ds);
 }
 
 int frecsys_recommend_dpp(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
                           int32_t k, int32_t pool, float theta, float eps, int32_t flags,
                           const uint8_t* item_mask, int32_t* items, float* scores, float* gain) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend_dpp: null context");
-  const int rc = check_dpp(c, "recommend_dpp: ", k, pool, theta, eps, flags,
-                           FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  const DppRequest dp{k, theta, eps, flags, items, scores, gain};
-  return recommend_impl(c, "recommend_dpp", side, rows, n_rows, pool,
-                        flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, &dp);
+  const std::string w = "recommend_dpp: ";
+  if (int rc = check_dpp(c, w, k, pool, theta, eps, flags,
+                         FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_DIV_RAW_SCORES))
+    return rc;
+  PoolStage ps(c, {k, flags, items, scores, gain}, n_rows, pool, /*dpp=*/true, theta, eps);
+  return scan_impl(c, {w, side, rows, n_rows, pool, flags & FRECSYS_REC_EXCLUDE_HISTORY, item_mask},
+                   !items || !scores, nullptr, ps);
 }
 
 int frecsys_diversify_dpp(frecsys_ctx* c, const int32_t* lists, const float* list_scores,
@@ -1304,42 +1043,9 @@ int frecsys_diversify_dpp(frecsys_ctx* c, const int32_t* lists, const float* lis
                           int32_t flags, int32_t* items, float* scores, float* gain) {
   if (!c) return fail(c, FRECSYS_ERR_INVALID, "diversify_dpp: null context");
   const std::string w = "diversify_dpp: ";
-  int rc = check_dpp(c, w, k, pool, theta, eps, flags, FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n == 0) return FRECSYS_OK;
-  if (!lists || !list_scores || !items || !scores)
-    return fail(c, FRECSYS_ERR_INVALID, w + "null pointer");
-  if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
-  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
-  const std::string e = pool_error(lists, list_scores, n, pool, c->n[1], raw);
-  if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
-  HIP_TRY(c, hipSetDevice(c->device));
-  const DppRequest dp{k, theta, eps, flags, items, scores, gain};
-  DppStage ps(c, dp, n, pool);
-  // per row of a batch: its pool (ids and scores), its Gramian, its factor
-  // where that is not in LDS, and its outputs; at least one row per batch, and
-  // one sub-batch per batch
-  const size_t budget = workspace_budget();
-  const size_t per_row = (size_t)pool * 8 + ps.sub_bytes() + DppStage::out_bytes(k);
-  const int64_t nb = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(budget / per_row)));
-  int32_t* d_ids = nullptr;
-  float* d_sc = nullptr;
-  rc = Carver::run(c, [&](Carver& cv) {
-    d_ids = cv.take<int32_t>((size_t)nb * pool);
-    d_sc = cv.take<float>((size_t)nb * pool);
-    ps.carve_rows(cv, nb, std::max(budget, (size_t)nb * ps.sub_bytes()));
-  });
-  if (rc) return rc;
-  for (int64_t r0 = 0; r0 < n; r0 += nb) {
-    const int64_t cnt = std::min(nb, n - r0);
-    HIP_TRY(c, to_device(c, d_ids, lists + r0 * pool, (size_t)cnt * pool));
-    HIP_TRY(c, to_device(c, d_sc, list_scores + r0 * pool, (size_t)cnt * pool));
-    if ((rc = ps.run(c, d_ids, d_sc, r0, cnt))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  ps.book(c);
-  return FRECSYS_OK;
+  if (int rc = check_dpp(c, w, k, pool, theta, eps, flags, FRECSYS_DIV_RAW_SCORES)) return rc;
+  PoolStage ps(c, {k, flags, items, scores, gain}, n, pool, /*dpp=*/true, theta, eps);
+  return pools_impl(c, w, lists, list_scores, ps);
 }
 
 int frecsys_rank_quality(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
@@ -1357,16 +1063,20 @@ int frecsys_rank_quality(frecsys_ctx* c, int32_t side, const int64_t* rows, int6
   if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
   const int32_t k = max_cutoff(k_list, nk);  // the list length is the largest cut-off
   if (pool != 0) {
-    const int rc = check_diversify(c, w, k, pool, lam, div_flags, FRECSYS_DIV_RAW_SCORES);
-    if (rc) return rc;
+    if (int rc = check_diversify(c, w, k, pool, lam, div_flags, FRECSYS_DIV_RAW_SCORES)) return rc;
   } else if (div_flags != 0) {
     return fail(c, FRECSYS_ERR_INVALID, w + "div_flags without a pool");
   }
   if (n_rows < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
   const MetricsRequest mt{gt_ptr, gt_items, k_list, nk, recall, ndcg};
-  const DiversifyRequest dv{k, lam, div_flags, nullptr, nullptr, nullptr};
-  return recommend_impl(c, "rank_quality", side, rows, n_rows, pool ? pool : k, flags, item_mask,
-                        nullptr, nullptr, gt_ptr ? &mt : nullptr, pool ? &dv : nullptr, &ql);
+  // every stage reads lists of k slots: the selection's, else the scan's
+  QualityBehind behind(c, ql, n_rows, k);
+  if (pool)
+    behind.ds.emplace(c, PoolRequest{k, div_flags, nullptr, nullptr, nullptr}, n_rows, pool, false,
+                      lam, 0.0f);
+  if (gt_ptr) behind.ms.emplace(mt, n_rows, k);
+  return scan_impl(c, {w, side, rows, n_rows, pool ? pool : k, flags, item_mask}, false,
+                   gt_ptr ? &mt : nullptr, behind);
 }
 
 int frecsys_lists_quality(frecsys_ctx* c, const int32_t* lists, int64_t n, int32_t list_k,
@@ -1378,15 +1088,9 @@ int frecsys_lists_quality(frecsys_ctx* c, const int32_t* lists, int64_t n, int32
   if (!c->emb[1] || c->n[1] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no item embeddings");
   const int64_t m = c->n[1];
   const QualityRequest ql{k_list, nk, item_weight, ild, novelty, exposure};
-  const std::string e = quality_args_error(ql, std::min<int32_t>(kMetricMaxK, list_k), m, false);
+  std::string e = quality_args_error(ql, std::min<int32_t>(kMetricMaxK, list_k), m, false);
+  if (e.empty()) e = lists_error(lists, n, list_k, m);
   if (!e.empty()) return fail(c, FRECSYS_ERR_INVALID, w + e);
-  if (n < 0) return fail(c, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n > 0 && !lists) return fail(c, FRECSYS_ERR_INVALID, w + "null lists");
-  if (n > INT64_MAX / list_k) return fail(c, FRECSYS_ERR_INVALID, w + "n * list_k overflows");
-  for (int64_t p = 0; p < n * list_k; ++p)
-    if (lists[p] >= m)
-      return fail(c, FRECSYS_ERR_INVALID,
-                  w + "item id " + std::to_string(lists[p]) + " out of range");
   if (n == 0) {
     if (exposure) std::memset(exposure, 0, sizeof(int64_t) * (size_t)nk * (size_t)m);
     return FRECSYS_OK;
@@ -1400,8 +1104,7 @@ int frecsys_lists_quality(frecsys_ctx* c, const int32_t* lists, int64_t n, int32
   int32_t* d_lists = nullptr;
   int rc = Carver::run(c, [&](Carver& cv) {
     d_lists = cv.take<int32_t>((size_t)nb * list_k);
-    qs.carve_rows(cv, nb);
-    qs.carve_inputs(cv);
+    qs.carve(cv, nb);
   });
   if (rc) return rc;
   if ((rc = qs.upload(c))) return rc;
@@ -1413,324 +1116,6 @@ int frecsys_lists_quality(frecsys_ctx* c, const int32_t* lists, int64_t n, int32
   }
   if ((rc = qs.finish(c))) return rc;
   qs.book(c);
-  return FRECSYS_OK;
-}
-
-int frecsys_list_quality(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
-                         const int32_t* lists, int64_t n, int32_t list_k, const int32_t* k_list,
-                         int32_t nk, const float* item_weight, float* ild, float* novelty,
-                         int64_t* exposure) {
-  const std::string w = "list_quality: ";
-  if (list_k < 1) return fail(nullptr, FRECSYS_ERR_INVALID, w + "list_k must be positive");
-  if (n_items < 1) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be positive");
-  const QualityRequest ql{k_list, nk, item_weight, ild, novelty, exposure};
-  const std::string e =
-      quality_args_error(ql, std::min<int32_t>(kMetricMaxK, list_k), n_items, false);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  if (ild && (!item_table || dim < 1 || ld < dim))
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, dim < 1, ld < dim)");
-  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n > 0 && !lists) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null lists");
-  if (n > INT64_MAX / list_k)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n * list_k overflows");
-  for (int64_t p = 0; p < n * list_k; ++p)
-    if (lists[p] >= n_items)
-      return fail(nullptr, FRECSYS_ERR_INVALID,
-                  w + "item id " + std::to_string(lists[p]) + " out of range");
-  if (exposure) std::memset(exposure, 0, sizeof(int64_t) * (size_t)nk * (size_t)n_items);
-  const int32_t mk = max_cutoff(k_list, nk);
-  // C and the weight sum after every filled slot count 0 .. mk, then per cut-off
-  std::vector<double> s(ild ? (size_t)dim : 0), run_c((size_t)mk + 1), run_w((size_t)mk + 1);
-  std::vector<int32_t> filled_below((size_t)mk + 1);  // filled slots among positions < j
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t* list = lists + i * list_k;
-    std::fill(s.begin(), s.end(), 0.0);
-    double C = 0.0, W = 0.0;
-    int32_t b = 0;
-    run_c[0] = run_w[0] = 0.0;
-    for (int32_t j = 0; j < mk; ++j) {
-      filled_below[(size_t)j] = b;
-      const int32_t id = list[j];
-      if (id < 0) continue;
-      if (ild) {
-        const float* y = item_table + (int64_t)id * ld;
-        double n2 = 0.0, ys = 0.0;
-        for (int32_t cc = 0; cc < dim; ++cc) n2 += (double)y[cc] * (double)y[cc];
-        const double inv = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
-        for (int32_t cc = 0; cc < dim; ++cc) ys += (inv * (double)y[cc]) * s[(size_t)cc];
-        C += ys;
-        for (int32_t cc = 0; cc < dim; ++cc) s[(size_t)cc] += inv * (double)y[cc];
-      }
-      if (item_weight) W += (double)item_weight[id];
-      if (exposure)
-        for (int32_t q = 0; q < nk; ++q)
-          if (j < k_list[q]) ++exposure[(int64_t)q * n_items + id];
-      ++b;
-      run_c[(size_t)b] = C;
-      run_w[(size_t)b] = W;
-    }
-    filled_below[(size_t)mk] = b;
-    for (int32_t q = 0; q < nk; ++q) {
-      const int32_t nq = filled_below[(size_t)k_list[q]];
-      if (ild)
-        ild[i * nk + q] =
-            nq >= 2 ? (float)(1.0 - run_c[(size_t)nq] / (double)((int64_t)nq * (nq - 1) / 2))
-                    : 0.0f;
-      if (novelty) novelty[i * nk + q] = nq >= 1 ? (float)(run_w[(size_t)nq] / (double)nq) : 0.0f;
-    }
-  }
-  return FRECSYS_OK;
-}
-
-int frecsys_exposure_summary(const int64_t* exposure, int64_t n_items, const uint8_t* item_mask,
-                             double* coverage, double* gini, int64_t* total, int64_t* covered) {
-  const std::string w = "exposure_summary: ";
-  if (!exposure || n_items < 1)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad arguments (null exposure, n_items < 1)");
-  std::vector<int64_t> cs;
-  int64_t S = 0, cov = 0;
-  for (int64_t j = 0; j < n_items; ++j) {
-    if (item_mask && !item_mask[j]) continue;
-    if (exposure[j] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative count");
-    if (exposure[j] > INT64_MAX - S) return fail(nullptr, FRECSYS_ERR_INVALID, w + "counts overflow");
-    cs.push_back(exposure[j]);
-    S += exposure[j];
-    cov += exposure[j] > 0;
-  }
-  const int64_t M = (int64_t)cs.size();
-  double cv = 0.0, g = 0.0;
-  if (M > 0 && S > 0) {
-    std::sort(cs.begin(), cs.end());
-    __int128 num = 0;  // sum over the ascending counts of (2 i - M - 1) c_(i), i = 1 .. M
-    for (int64_t i = 0; i < M; ++i) num += (__int128)(2 * (i + 1) - M - 1) * cs[(size_t)i];
-    cv = (double)cov / (double)M;
-    g = (double)num / (double)((__int128)M * S);
-  }
-  if (coverage) *coverage = cv;
-  if (gini) *gini = g;
-  if (total) *total = S;
-  if (covered) *covered = cov;
-  return FRECSYS_OK;
-}
-
-int frecsys_mmr_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
-                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
-                       int32_t k, float lam, int32_t flags, int32_t* items, float* scores,
-                       float* mmr) {
-#pragma clang fp contract(off)
-  const std::string w = "mmr_select: ";
-  int rc = check_diversify(nullptr, w, k, pool, lam, flags, FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n == 0) return FRECSYS_OK;
-  if (!item_table || n_items < 1 || dim < 1 || ld < dim)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, n_items < 1, ld < dim)");
-  if (!lists || !list_scores || !items || !scores)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "null pointer");
-  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
-  const std::string e = pool_error(lists, list_scores, n, pool, n_items, raw);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  const float oml = 1.0f - lam;
-  auto dot = [&](int32_t x, int32_t y) {
-    const float* px = item_table + (int64_t)x * ld;
-    const float* py = item_table + (int64_t)y * ld;
-    float acc = 0.0f;
-    for (int32_t cc = 0; cc < dim; ++cc) acc = std::fmaf(px[cc], py[cc], acc);
-    return acc;
-  };
-  auto work = [&](int64_t i0, int64_t i1) {
-    std::vector<float> base((size_t)pool), mm((size_t)pool), inv((size_t)pool);
-    std::vector<uint8_t> alive((size_t)pool);
-    for (int64_t i = i0; i < i1; ++i) {
-      const int32_t* ids = lists + i * pool;
-      const float* sc = list_scores + i * pool;
-      float smax = -INFINITY, smin = INFINITY;
-      int32_t p = 0;
-      for (int32_t b = 0; b < pool; ++b) {
-        alive[(size_t)b] = ids[b] >= 0;
-        if (!alive[(size_t)b]) continue;
-        ++p;
-        smax = std::fmax(smax, sc[b]);
-        smin = std::fmin(smin, sc[b]);
-        const float n2 = dot(ids[b], ids[b]);
-        inv[(size_t)b] = n2 > 0.0f ? 1.0f / std::sqrt(n2) : 0.0f;
-      }
-      const float range = smax - smin;
-      for (int32_t b = 0; b < pool; ++b) {
-        if (!alive[(size_t)b]) continue;
-        const float rel = raw ? sc[b] : (range > 0.0f ? (sc[b] - smin) / range : 0.0f);
-        base[(size_t)b] = lam * rel;
-        mm[(size_t)b] = -INFINITY;
-      }
-      const int32_t steps = std::min(p, k);
-      for (int32_t t = 0; t < steps; ++t) {
-        uint64_t best = 0;
-        for (int32_t b = 0; b < pool; ++b) {
-          if (!alive[(size_t)b]) continue;
-          float v;
-          if (t == 0) {
-            v = base[(size_t)b] + 0.0f;
-          } else {
-            const float pen = oml * mm[(size_t)b];
-            v = (base[(size_t)b] - pen) + 0.0f;
-          }
-          uint32_t u;
-          std::memcpy(&u, &v, 4);
-          const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // score_key
-          const uint64_t word = ((uint64_t)key << 32) | (0xFFFFFFFFu - (uint32_t)b);
-          if (word > best) best = word;
-        }
-        const int32_t s = (int32_t)(0xFFFFFFFFu - (uint32_t)best);
-        const uint32_t key = (uint32_t)(best >> 32);
-        const uint32_t u = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;  // score_unkey
-        items[i * k + t] = ids[s];
-        scores[i * k + t] = sc[s];
-        if (mmr) std::memcpy(&mmr[i * k + t], &u, 4);
-        alive[(size_t)s] = 0;
-        if (t + 1 == steps) break;
-        for (int32_t b = 0; b < pool; ++b) {
-          if (!alive[(size_t)b]) continue;
-          const float g = dot(ids[s], ids[b]);
-          const float gs = g * inv[(size_t)s];
-          const float cs = gs * inv[(size_t)b] + 0.0f;
-          mm[(size_t)b] = std::fmax(mm[(size_t)b], cs);
-        }
-      }
-      for (int32_t t = steps; t < k; ++t) {
-        items[i * k + t] = -1;
-        scores[i * k + t] = -FLT_MAX;
-        if (mmr) mmr[i * k + t] = -FLT_MAX;
-      }
-    }
-  };
-  // rows are independent: host threads over row ranges when there is enough work
-  const double cost = (double)n * pool * (double)k * dim;
-  const int nt = cost < 1e8 ? 1
-                            : (int)std::min<int64_t>(
-                                  n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
-  if (nt <= 1) {
-    work(0, n);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
-    for (auto& t : th) t.join();
-  }
-  return FRECSYS_OK;
-}
-
-int frecsys_dpp_select(const float* item_table, int64_t n_items, int32_t dim, int64_t ld,
-                       const int32_t* lists, const float* list_scores, int64_t n, int32_t pool,
-                       int32_t k, float theta, float eps, int32_t flags, int32_t* items,
-                       float* scores, float* gain) {
-#pragma clang fp contract(off)
-  const std::string w = "dpp_select: ";
-  int rc = check_dpp(nullptr, w, k, pool, theta, eps, flags, FRECSYS_DIV_RAW_SCORES);
-  if (rc) return rc;
-  if (n < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n == 0) return FRECSYS_OK;
-  if (!item_table || n_items < 1 || dim < 1 || ld < dim)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad item table (null, n_items < 1, ld < dim)");
-  if (!lists || !list_scores || !items || !scores)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "null pointer");
-  const bool raw = (flags & FRECSYS_DIV_RAW_SCORES) != 0;
-  const std::string e = pool_error(lists, list_scores, n, pool, n_items, raw);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  auto dot = [&](int32_t x, int32_t y) {
-    const float* px = item_table + (int64_t)x * ld;
-    const float* py = item_table + (int64_t)y * ld;
-    float acc = 0.0f;
-    for (int32_t cc = 0; cc < dim; ++cc) acc = std::fmaf(px[cc], py[cc], acc);
-    return acc;
-  };
-  auto work = [&](int64_t i0, int64_t i1) {
-    const size_t P = (size_t)pool;
-    std::vector<float> wq(P), r(P), inv(P), C((size_t)k * P);
-    std::vector<uint8_t> alive(P);
-    for (int64_t i = i0; i < i1; ++i) {
-      const int32_t* ids = lists + i * pool;
-      const float* sc = list_scores + i * pool;
-      float smax = -INFINITY, smin = INFINITY;
-      int32_t p = 0;
-      for (int32_t b = 0; b < pool; ++b) {
-        alive[(size_t)b] = ids[b] >= 0;
-        if (!alive[(size_t)b]) continue;
-        ++p;
-        smax = std::fmax(smax, sc[b]);
-        smin = std::fmin(smin, sc[b]);
-        const float n2 = dot(ids[b], ids[b]);
-        inv[(size_t)b] = n2 > 0.0f ? 1.0f / std::sqrt(n2) : 0.0f;
-        r[(size_t)b] = n2 > 0.0f ? 1.0f : 0.0f;
-      }
-      const float range = smax - smin;
-      for (int32_t b = 0; b < pool; ++b) {
-        if (!alive[(size_t)b]) continue;
-        const float rel = raw ? sc[b] : (range > 0.0f ? (sc[b] - smin) / range : 0.0f);
-        const float x = theta * rel;
-        wq[(size_t)b] = dpp_exp2(std::fmin(std::fmax(x, -64.0f), 64.0f));
-      }
-      const int32_t steps = std::min(p, k);
-      int32_t m = 0;
-      for (int32_t t = 0; t < steps; ++t) {
-        uint64_t best = 0;
-        for (int32_t b = 0; b < pool; ++b) {
-          if (!alive[(size_t)b]) continue;
-          uint32_t key = 0;  // below eps: the fallback's word, the lowest slot wins
-          if (r[(size_t)b] >= eps) {
-            const float v = wq[(size_t)b] * r[(size_t)b] + 0.0f;
-            uint32_t u;
-            std::memcpy(&u, &v, 4);
-            key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // score_key
-          }
-          const uint64_t word = ((uint64_t)key << 32) | (0xFFFFFFFFu - (uint32_t)b);
-          if (word > best) best = word;
-        }
-        const int32_t s = (int32_t)(0xFFFFFFFFu - (uint32_t)best);
-        const uint32_t key = (uint32_t)(best >> 32);
-        const uint32_t u = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;  // score_unkey
-        items[i * k + t] = ids[s];
-        scores[i * k + t] = sc[s];
-        if (gain) {
-          if (key) std::memcpy(&gain[i * k + t], &u, 4);
-          else gain[i * k + t] = 0.0f;
-        }
-        alive[(size_t)s] = 0;
-        if (key == 0 || t + 1 == steps) continue;  // the last step's update is never read
-        const float delta = std::sqrt(r[(size_t)s]);
-        const float* cs = C.data() + (size_t)s;
-        for (int32_t b = 0; b < pool; ++b) {
-          if (!alive[(size_t)b]) continue;
-          const float g = dot(ids[s], ids[b]);
-          const float gs = g * inv[(size_t)s];
-          const float sim = gs * inv[(size_t)b] + 0.0f;
-          float acc = 0.0f;
-          for (int32_t uu = 0; uu < m; ++uu)
-            acc = std::fmaf(C[(size_t)uu * P + (size_t)b], cs[(size_t)uu * P], acc);
-          const float d = sim - acc;
-          const float ev = d / delta;
-          C[(size_t)m * P + (size_t)b] = ev;
-          r[(size_t)b] = std::fmaf(-ev, ev, r[(size_t)b]);
-        }
-        ++m;
-      }
-      for (int32_t t = steps; t < k; ++t) {
-        items[i * k + t] = -1;
-        scores[i * k + t] = -FLT_MAX;
-        if (gain) gain[i * k + t] = -FLT_MAX;
-      }
-    }
-  };
-  // rows are independent: host threads over row ranges when there is enough work
-  const double cost = (double)n * pool * (double)k * ((double)dim + 0.5 * k);
-  const int nt = cost < 1e8 ? 1
-                            : (int)std::min<int64_t>(
-                                  n, std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
-  if (nt <= 1) {
-    work(0, n);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
-    for (auto& t : th) t.join();
-  }
   return FRECSYS_OK;
 }
 
@@ -1829,117 +1214,13 @@ int frecsys_rank_candidates(frecsys_ctx* c, int32_t side, const int64_t* rows, i
     ScopedTimer t(c, "rank_candidates");
     HIP_TRY(c, launch_rank_candidates(a, c->stream));
     t.stop();
-    if ((rc = fetch_lists(c, items, scores, k, a.r0, a.n, a.out_items, a.out_scores))) return rc;
+    if ((rc = copy_lists(c, items, scores, k, a.r0, a.n, a.out_items, a.out_scores))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   // flops at the logical dim; bytes: one padded item row per candidate, the
   // ids read, the lists written
   add_work(c, "rank_candidates", 2.0 * (double)pairs * c->dim,
            (double)pairs * c->Dp * 4.0 + (double)pairs * 4.0 + (double)n * k * 8.0, n);
-  return FRECSYS_OK;
-}
-
-int frecsys_sample_negatives(int64_t n_items, const uint8_t* item_mask, const int64_t* row_ids,
-                             int64_t n_rows, const int64_t* hist_ptr, const int32_t* hist_items,
-                             const int64_t* gt_ptr, const int32_t* gt_items, int32_t n_neg,
-                             uint64_t seed, int32_t* neg_count, int32_t* negatives) {
-  const std::string w = "sample_negatives: ";
-  if (n_items < 1 || n_items > INT32_MAX)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_items must be in [1, 2^31)");
-  if (n_rows < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative row count");
-  if (n_neg < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_neg must not be negative");
-  if (n_neg > 0 && n_rows > INT64_MAX / n_neg)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "n_rows * n_neg overflows");
-  if (n_rows == 0) return FRECSYS_OK;
-  if (!neg_count) return fail(nullptr, FRECSYS_ERR_INVALID, w + "null neg_count");
-  const int64_t n = n_rows, m = n_items;
-  if (row_ids)
-    for (int64_t i = 0; i < n; ++i)
-      if (row_ids[i] < 0)
-        return fail(nullptr, FRECSYS_ERR_INVALID,
-                    w + "row id " + std::to_string(row_ids[i]) + " out of range");
-  if (!hist_ptr && hist_items)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "hist_items without hist_ptr");
-  if (hist_ptr) {
-    if (hist_ptr[0] < 0) return fail(nullptr, FRECSYS_ERR_INVALID, w + "negative hist_ptr");
-    for (int64_t i = 0; i < n; ++i)
-      if (hist_ptr[i + 1] < hist_ptr[i])
-        return fail(nullptr, FRECSYS_ERR_INVALID,
-                    w + "hist_ptr not monotone at row " + std::to_string(i));
-    if (hist_ptr[n] > hist_ptr[0] && !hist_items)
-      return fail(nullptr, FRECSYS_ERR_INVALID, w + "null hist_items");
-  }
-  {
-    const int32_t one = 1;
-    int32_t mk = 0;
-    const std::string e = metric_args_error(n, gt_ptr, gt_items, &one, 1, m, &mk);
-    if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  }
-  std::vector<int32_t> dlist;
-  int64_t M = m;
-  if (item_mask) {
-    for (int64_t j = 0; j < m; ++j)
-      if (item_mask[j]) dlist.push_back((int32_t)j);
-    M = (int64_t)dlist.size();
-  }
-  const uint64_t cap = kSampleCapBase + kSampleCapPerNeg * (uint64_t)n_neg;
-  std::atomic<int64_t> capped{-1};
-  // rows on the host thread pool; a task keeps one bitmap of the items and
-  // clears the bits of a row after it (blocked = history and ground truth,
-  // then the taken ids)
-  frecsys::ThreadPool::Get().ParallelFor(n, 64, [&](int64_t lo, int64_t hi) {
-    std::vector<uint64_t> bm((size_t)((m + 63) / 64), 0ull);
-    std::vector<int32_t> set;  // ids whose bit this row set
-    auto mark = [&](int64_t j) {
-      uint64_t& wd = bm[(size_t)(j >> 6)];
-      const uint64_t b = 1ull << (j & 63);
-      if (wd & b) return false;
-      wd |= b;
-      set.push_back((int32_t)j);
-      return true;
-    };
-    for (int64_t i = lo; i < hi; ++i) {
-      set.clear();
-      int64_t blocked = 0;  // distinct blocked ids that lie in D
-      if (hist_ptr)
-        for (int64_t p = hist_ptr[i]; p < hist_ptr[i + 1]; ++p) {
-          const int64_t j = hist_items[p];
-          if (j >= 0 && j < m && mark(j) && (!item_mask || item_mask[j])) ++blocked;
-        }
-      for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p) {
-        const int64_t j = gt_items[p];
-        if (mark(j) && (!item_mask || item_mask[j])) ++blocked;
-      }
-      const int64_t E = M - blocked;
-      int32_t* out = negatives ? negatives + i * n_neg : nullptr;
-      if (whole_pool_row(n_neg, E, M)) {
-        neg_count[i] = (int32_t)E;
-        if (out) std::fill(out, out + n_neg, -1);
-      } else {
-        neg_count[i] = n_neg;
-        const uint64_t r = (uint64_t)(row_ids ? row_ids[i] : i);
-        const uint64_t key = mix64(seed + kGolden * (r + 1));
-        int32_t have = 0;
-        for (uint64_t t = 0; have < n_neg; ++t) {
-          if (t >= cap) {
-            int64_t none = -1;
-            capped.compare_exchange_strong(none, i);
-            break;
-          }
-          const uint64_t x = mix64(key + kGolden * (t + 1));
-          const uint64_t idx = ((x >> 32) * (uint64_t)M) >> 32;
-          const int64_t j = item_mask ? dlist[(size_t)idx] : (int64_t)idx;
-          if (!mark(j)) continue;
-          if (out) out[have] = (int32_t)j;
-          ++have;
-        }
-      }
-      for (const int32_t j : set) bm[(size_t)(j >> 6)] &= ~(1ull << (j & 63));
-    }
-  });
-  if (capped.load() >= 0)
-    return fail(nullptr, FRECSYS_ERR_HIP,
-                w + "the draws of query row " + std::to_string(capped.load()) +
-                    " reached the cap");
   return FRECSYS_OK;
 }
 
@@ -1997,17 +1278,15 @@ int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n
   const bool cosine = (flags & FRECSYS_SIM_COSINE) != 0;
   HIP_TRY(c, hipSetDevice(c->device));
   // frecsys_recommend's scan of the side's own table (no history bitmap: the
-  // one excluded id of a row is tested in the scan)
+  // one excluded id of a row is tested in the scan).  Not scan_impl: table, norm
+  // pass, inv / skip_self, timer, work and splits counter would be six parameters.
   const ScanPlan p = scan_plan(c, k, m, n, 0);
   RecommendArgs a = scan_args(c, side, side, k, p.splits, false);
   if ((rc = Carver::run(c, [&](Carver& cv) { carve_scan(cv, a, p, rows != nullptr, n); })))
     return rc;
   // outside the per-row budget: one inverse norm per row of the side
   if (cosine && (rc = ensure(c, c->d_sim_inv, (size_t)m))) return rc;
-  const std::vector<uint32_t> maskw = item_mask_words(m, mask);
-  HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
-  if (rows) HIP_TRY(c, to_device(c, a.qrows, rows, (size_t)n));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((rc = upload_query(c, a, mask, rows, n))) return rc;
   if (cosine) {  // per call: every solve rewrites the table
     ScopedTimer t(c, "similar.norms");
     HIP_TRY(c, launch_row_inv_norm(c->emb[side], m, c->Dp, c->d_sim_inv, c->stream));
@@ -2021,85 +1300,14 @@ int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n
     ScopedTimer t(c, "similar");
     HIP_TRY(c, launch_recommend(a, c->stream));
     t.stop();
-    if ((rc = fetch_lists(c, ids, scores, k, r0, a.n, a.out_items, a.out_scores))) return rc;
+    if ((rc = copy_lists(c, ids, scores, k, r0, a.n, a.out_items, a.out_scores))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   // scoring flops at the logical dim; bytes: the queries and the table read,
   // the table once more by the norm pass, the lists written
   const double dd = c->dim;
   add_work(c, "similar", 2.0 * (double)n * (double)m * dd,
            ((double)n + (cosine ? 2.0 : 1.0) * (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
-  return FRECSYS_OK;
-}
-
-int frecsys_list_metrics(const int32_t* lists, int64_t n, int32_t list_k, const int64_t* gt_ptr,
-                         const int32_t* gt_items, const int32_t* k_list, int32_t nk, float* recall,
-                         float* ndcg) {
-  int32_t mk = 0;
-  const std::string e = metric_args_error(n, gt_ptr, gt_items, k_list, nk, -1, &mk);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: " + e);
-  if (list_k < mk)
-    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: list_k is below the largest cut-off");
-  if (n > 0 && (!lists || !recall || !ndcg))
-    return fail(nullptr, FRECSYS_ERR_INVALID, "list_metrics: bad arguments (null lists / outputs)");
-  const MetricTables& tab = metric_tables();
-  std::vector<int64_t> sp;
-  std::vector<int32_t> sg;
-  sorted_ground_truth(n, gt_ptr, gt_items, &sp, &sg);
-  std::vector<uint8_t> hit((size_t)mk);
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t* g0 = sg.data() + sp[(size_t)i];
-    const int32_t* g1 = sg.data() + sp[(size_t)i + 1];
-    const int64_t g = g1 - g0;
-    const int32_t* list = lists + i * list_k;
-    for (int32_t j = 0; j < mk; ++j)  // -1: an empty slot, never a hit
-      hit[(size_t)j] = list[j] >= 0 && std::binary_search(g0, g1, list[j]);
-    for (int32_t q = 0; q < nk; ++q) {
-      const int32_t kq = k_list[q];  // <= mk <= list_k
-      double hits = 0.0, dcg = 0.0;
-      for (int32_t j = 0; j < kq; ++j)
-        if (hit[(size_t)j]) {
-          hits += 1.0;
-          dcg += tab.gain[j];
-        }
-      const double norm = tab.idcg[std::min<int64_t>(kq, g)];
-      recall[i * nk + q] = (float)(hits / std::min<float>((float)kq, (float)g));
-      ndcg[i * nk + q] = (float)(dcg / norm);
-    }
-  }
-  return FRECSYS_OK;
-}
-
-int frecsys_position_metrics(const int32_t* rank, const int64_t* gt_ptr, const int32_t* eligible,
-                             int64_t n_rows, float* mrr, float* auc) {
-  const std::string w = "position_metrics: ";
-  if (n_rows < 0 || !gt_ptr)
-    return fail(nullptr, FRECSYS_ERR_INVALID, w + "bad arguments (null gt_ptr, n < 0)");
-  const int64_t n = n_rows;
-  const std::string e = gt_ptr_error(n, gt_ptr);
-  if (!e.empty()) return fail(nullptr, FRECSYS_ERR_INVALID, w + e);
-  if (n > 0 && (!rank || !eligible || !mrr || !auc))
-    return fail(nullptr, FRECSYS_ERR_INVALID,
-                w + "bad arguments (null ranks / eligible / outputs)");
-  for (int64_t i = 0; i < n; ++i)  // (so a row never has more distinct ranks than eligible items)
-    for (int64_t p = gt_ptr[i]; p < gt_ptr[i + 1]; ++p)
-      if (rank[p] < -1 || rank[p] >= eligible[i])
-        return fail(nullptr, FRECSYS_ERR_INVALID,
-                    w + "rank " + std::to_string(rank[p]) + " of row " + std::to_string(i) +
-                        " outside [-1, eligible)");
-  std::vector<int32_t> R;
-  for (int64_t i = 0; i < n; ++i) {
-    R.assign(rank + gt_ptr[i], rank + gt_ptr[i + 1]);
-    std::sort(R.begin(), R.end());
-    R.erase(std::unique(R.begin(), R.end()), R.end());
-    if (!R.empty() && R[0] < 0) R.erase(R.begin());
-    const int64_t g = (int64_t)R.size(), M = eligible[i];  // g <= M
-    int64_t inv = 0;
-    for (int64_t q = 0; q < g; ++q) inv += (int64_t)R[(size_t)q] - q;
-    mrr[i] = g ? (float)(1.0 / (double)((int64_t)R[0] + 1)) : 0.0f;
-    auc[i] = g == 0   ? 0.0f
-             : M == g ? 1.0f
-                      : (float)(1.0 - (double)inv / ((double)g * (double)(M - g)));
-  }
   return FRECSYS_OK;
 }
 
@@ -2184,29 +1392,6 @@ int frecsys_rank_positions(frecsys_ctx* c, int32_t side, const int64_t* rows, in
            (double)gt_ptr[n] * 4.0 + ((double)n + 1.0) * 8.0 + (double)gt_ptr[n] * 4.0 +
                (double)n * 12.0,
            n);
-  return FRECSYS_OK;
-}
-
-int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int32_t na,
-                        float* out) {
-  if (n < 0 || na < 0 || (n > 0 && !values) || (na > 0 && (!alphas || !out)))
-    return fail(nullptr, FRECSYS_ERR_INVALID, "metric_cvar: bad arguments");
-  // EvaluationResult::cvar (evaluation.h:83-102), verbatim
-  std::vector<float> ms(values, values + n);
-  std::sort(ms.begin(), ms.end());
-  for (int32_t j = 0; j < na; ++j) out[j] = 0.0f;
-  int64_t counter = 0;
-  float acc = 0.0f;
-  for (int64_t i = 0; i < n; ++i) {
-    acc += ms[(size_t)i];
-    for (int64_t j = counter; j < na; ++j) {
-      const int pos = (int)((float)n * alphas[j]);
-      if (pos == i) {
-        out[counter] = acc / (float)(i + 1);
-        counter++;
-      }
-    }
-  }
   return FRECSYS_OK;
 }
 

@@ -168,6 +168,7 @@ def test_independent(monkeypatch):
         _same(run(rows, 20, 200), mid)
         subs = ctx.timing("diversify.gram")[1]
         assert subs == ctx.timing("dpp.select")[1] and subs >= 12
+        assert ctx.timing("recommend")[1] >= 2   # explicit row ids over several scan batches
         assert ctx.timing("diversify.select")[1] == 0
         # pool 1024: a Gramian and a factor alone exceed the budget, one row each
         ctx.timing_reset()
