@@ -707,6 +707,64 @@ int frecsys_sampled_metrics(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
 #define FRECSYS_SIM_KEEP_SELF 2 /* without it a query row never lists itself */
 int frecsys_similar(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                     int32_t k, int32_t flags, const uint8_t* mask, int32_t* ids, float* scores);
+/* Audiences: the k best users for items ("who should see this item?"; the
+ * reference has no counterpart, Spark's ALS calls it recommendForItemSubset).
+ * Query i is row items[i] of the ITEM table (any order, repeats allowed), or
+ * row i when items is NULL; it lists the k best eligible users by descending
+ * score, ties by ascending user id, into users[i*k .. i*k+k) and, unless
+ * scores is NULL, their scores into scores[i*k .. i*k+k) (host).
+ *   score(i, u): acc = fma(V[i][c], U[u][c], acc) over the padded dim in
+ * ascending c from +0 -- bit for bit frecsys_score_pairs(USER, u, i) and the
+ * score frecsys_recommend lists for item i in user u's row (the product
+ * commutes, the order of c is the same, and a chain from +0 never yields -0).
+ *   A user u is eligible when its user_mask byte is non-zero (host [users],
+ * or NULL = every user) and, with FRECSYS_AUD_EXCLUDE_HISTORY, u is not in
+ * the ITEM-side CSR row of the query item (the users who interacted with it;
+ * columns unsorted, repeats allowed).  1 <= k <= 1024; the slots beyond the
+ * eligible count hold id -1 and score -FLT_MAX.
+ *   Two paths, one result.  n <= FRECSYS_AUDIENCE_THIN_MAX (read per call;
+ * default 4096, 0 forces the scan) takes the thin-query kernel (audience.hip):
+ * 8 queries stay on chip while a workgroup sweeps its split of the user table
+ * once per pass, and the splits' lists are merged in rounds.  More queries
+ * take frecsys_recommend's scan with the item rows as queries and the user
+ * table searched.  frecsys_audience_plan answers what is launched.  Neither
+ * the path, the splits, the passes nor the batch changes a result bit; no
+ * rows x users score matrix exists.  Workspace and knobs are
+ * frecsys_recommend's (FRECSYS_RECOMMEND_WS_MB, FRECSYS_RECOMMEND_SPLITS), the
+ * workspace goes with frecsys_release_workspaces.  Rank-local at any world
+ * size: no collective.  n == 0 returns FRECSYS_OK and touches nothing.
+ * FRECSYS_ERR_INVALID, before any device call: a null context, k out of range,
+ * an unknown flag bit, an item id out of range, items == NULL with n above
+ * the item count, null users with n > 0, the exclude flag without an ITEM CSR
+ * loaded, a table without embeddings, no users.  Timer key "audience": one
+ * launch group per query batch, the table passes of a batch in one grid;
+ * frecsys_work("audience"): 2 n m d flops (m = users), bytes = (passes m + n)
+ * Dp 4 + 8 n k with the plan's passes. */
+#define FRECSYS_AUD_EXCLUDE_HISTORY 1
+int frecsys_audience(frecsys_ctx* ctx, const int64_t* items, int64_t n, int32_t k,
+                     int32_t flags, const uint8_t* user_mask, int32_t* users, float* scores);
+/* What frecsys_audience launches for n queries against n_users users on a
+ * device of `cus` compute units (host arithmetic only: no context, no HIP
+ * call; reads the three knobs above as the call does).
+ *   thin: 1 = the thin-query kernel, 0 = the scan.  queries_per_pass: queries
+ * that share one read of the table (thin: 8, fewer when the budget holds
+ * fewer; scan: its 64-row block); passes = ceil(n / queries_per_pass).
+ * splits: the table is swept in chunks of chunk_rows rows; with C =
+ * ceil(n_users / chunk_rows), split s takes chunks [s C / splits, (s + 1) C /
+ * splits).  slots: candidate words per (query, split), >= k + chunk_rows.
+ * merge_rounds: the kernels behind the scan -- on the thin path every round
+ * but the last takes the k best of groups of 8192 / kp lists (kp: k rounded up
+ * to a power of two, 64 at least) and the last writes out the one list left;
+ * the scan's one merge takes its splits, at most 8192 / k.  rows_per_batch: queries per launch group;
+ * workspace_bytes: what a batch takes of the budget.  FRECSYS_ERR_INVALID: an
+ * unsupported dim, n_users < 1, n < 1, k outside [1, 1024], cus < 1, exclude
+ * not 0 / 1, a null out. */
+typedef struct {
+  int32_t thin, queries_per_pass, passes, splits, chunk_rows, slots, merge_rounds;
+  int64_t rows_per_batch, workspace_bytes;
+} frecsys_audience_plan_t;
+int frecsys_audience_plan(int32_t dim, int64_t n_users, int64_t n, int32_t k, int32_t cus,
+                          int32_t exclude, frecsys_audience_plan_t* out);
 /* Diversified lists: greedy maximal-marginal-relevance (MMR) re-ranking of a
  * pool of items per query row (no reference counterpart).  The three calls
  * below share one definition, fixed to the bit; frecsys_mmr_select is that

@@ -266,6 +266,18 @@ int frecsys_model_rank_candidates(frecsys_model* m, const int64_t* users, int64_
                                   const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                                   int32_t exclude_seen, const uint8_t* item_mask,
                                   int32_t* items, float* scores);
+/* The k best users for trained items (items[i]: a row of V; n ids, any order,
+ * repeats allowed, or NULL = rows 0 .. n-1): frecsys_audience (frecsys_hip.h).
+ * exclude_seen != 0 drops the users who have the item in the training tuples
+ * (loaded into the context here if no Train() has done it yet; a model loaded
+ * without its tuples answers FRECSYS_ERR_INVALID); user_mask: host [n_users]
+ * eligibility bytes or NULL; users / scores: host [n * k] (scores may be
+ * NULL).  Scores -- bit for bit frecsys_model_score's --, order, ties, the -1 /
+ * -FLT_MAX fill and the errors are frecsys_audience's; the arguments are
+ * checked before any device call. */
+int frecsys_model_audience(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
+                           int32_t exclude_seen, const uint8_t* user_mask, int32_t* users,
+                           float* scores);
 /* The k nearest neighbours of trained items among the items (items[i]: a row
  * of V) and of trained users among the users (users[i]: a row of U), by cosine
  * (FRECSYS_SIM_COSINE in flags) or dot product; without FRECSYS_SIM_KEEP_SELF

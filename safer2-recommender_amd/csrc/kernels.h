@@ -419,6 +419,53 @@ hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s);
 hipError_t launch_history_bits(const int64_t* row_ptr, const int32_t* col, const int64_t* qrows,
                                int64_t r0, int64_t n, int64_t m, uint32_t* bitmap, hipStream_t s);
 
+// rec_merge_kernel alone: the k best of each row's a.splits lists, a.counts
+// words each at a.cand + (row * a.splits + s) * cap, every list sorted
+// descending; a.splits * a.k words within the merge kernel's LDS.  Reads
+// a.n, a.k, a.splits, a.cand, a.counts, a.out_items, a.out_scores only.
+hipError_t launch_recommend_merge(const RecommendArgs& a, int64_t cap, hipStream_t s);
+
+// The thin-query scan (audience.hip): the k best eligible rows of a table Y
+// for each of a few query rows of X, by recommend.hip's word (score_key(score)
+// << 32 | ~id) and its score, the chain acc = fmaf(X[q][c], Y[u][c], acc), c
+// ascending from +0 over the padded dim.  thin_scan_kernel holds
+// audience_queries_per_pass() queries on chip and reads every row of its
+// split of Y once per pass; grid (passes of the batch) x (splits).  A split's
+// lists are cut to their best k, then aud_reduce_kernel takes the k best of
+// groups of audience_group(k) lists per round until one list is left, which
+// rec_merge_kernel writes out.  Eligibility as in RecommendArgs.
+struct AudienceArgs {
+  const float* X;            // query table, ld = Dp
+  const int64_t* qrows;      // table row of every query of the call, or nullptr
+  int64_t r0, n;             // this batch: queries r0 .. r0 + n - 1
+  const float* Y;            // the table searched, ld = Dp
+  int64_t m;                 // its rows
+  int Dp;
+  int k;                     // 1 .. 1024
+  int splits;                // 1 .. chunks of audience_chunk_rows() rows
+  const int64_t* row_ptr;    // CSR of the query table's side, or nullptr (no exclusion)
+  const int32_t* col;
+  const uint32_t* maskw;     // [recommend_words(m)] eligibility bits of Y's rows
+  uint32_t* bitmap;          // [n][recommend_words(m)] history bits (workspace), or nullptr
+  unsigned long long* cand;  // [n][splits][audience_slots(k)] candidates (workspace)
+  int32_t* counts;           // [n][splits] (workspace)
+  unsigned long long* red;   // [n][audience_reduce_lists(splits, k)][k] (workspace), or nullptr
+  int32_t* red_counts;       // [n][audience_reduce_lists(splits, k)]
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k]
+};
+int audience_queries_per_pass();
+int audience_chunk_rows();
+// Candidate slots per (query, split): k + a chunk, rounded up to a power of two.
+int audience_slots(int k);
+// Lists per group of a reduce round (a group's lists, k rounded up to a power
+// of two each, fill the kernel's LDS), the lists the first round leaves (0: one
+// split, no round), and the kernels behind the scan, the write-out included.
+int audience_group(int k);
+int audience_reduce_lists(int splits, int k);
+int audience_merge_rounds(int splits, int k);
+hipError_t launch_audience_thin(const AudienceArgs& a, hipStream_t s);
+
 // Exact positions of ground-truth items among all eligible items
 // (positions.hip): for query row i of the batch and entry t of its ground
 // truth gt[gt_ptr[r0 + i] - gt_base .. gt_ptr[r0 + i + 1] - gt_base), rank[t] =

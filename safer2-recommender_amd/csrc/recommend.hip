@@ -356,6 +356,15 @@ hipError_t launch_history_bits(const int64_t* row_ptr, const int32_t* col, const
   return hipGetLastError();
 }
 
+hipError_t launch_recommend_merge(const RecommendArgs& a, int64_t cap, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.k < 1 || a.k > 1024 || a.splits < 1 || (int64_t)a.splits * a.k > kMergeSlots ||
+      cap < a.k || !a.cand || !a.counts || !a.out_items)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)a.n), dim3(256), 0, s, a, cap);
+  return hipGetLastError();
+}
+
 hipError_t launch_recommend(const RecommendArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (a.k < 1 || a.k > 1024 || a.m < 1 || a.splits < 1 ||

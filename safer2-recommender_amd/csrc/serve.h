@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -78,6 +79,13 @@ std::string metric_args_error(int64_t n, const int64_t* gt_ptr, const int32_t* g
 // up over the dropped repeats; the thread count never changes the result.
 void sorted_ground_truth(int64_t n, const int64_t* gt_ptr, const int32_t* gt_items,
                          std::vector<int64_t>* sp, std::vector<int32_t>* sg);
+
+// Bytes the regions of a row batch may take: 256 MiB, or the knob (read per call).
+inline size_t workspace_budget() {
+  int64_t ws_mb = 256;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
+  return (size_t)ws_mb << 20;
+}
 
 // Whole-pool rule of a sampled row with pool size E among M maskable ids.
 inline bool whole_pool_row(int64_t n_neg, int64_t E, int64_t M) {

@@ -15,10 +15,13 @@
 // Drivers.  A call runs its rows in batches, one timed launch group each, and
 // synchronises after each batch's copy-back:
 //   scan (scan_impl with one object behind the scan: recommend,
-//     rank_metrics, recommend_diverse, recommend_dpp, rank_quality; similar,
-//     with a loop of its own): budget / bytes per row, the scan's and what is
-//     behind it, in whole 64-row blocks, with the item splits of scan_plan; a
-//     selection forms its Gramians in sub-batches, within a budget of their own;
+//     rank_metrics, recommend_diverse, recommend_dpp, rank_quality; similar
+//     and audience above its thin-query limit, with loops of their own):
+//     budget / bytes per row, the scan's and what is behind it, in whole 64-row
+//     blocks, with the item splits of scan_plan; a selection forms its Gramians
+//     in sub-batches, within a budget of their own;
+//   thin queries (audience): frecsys_audience_plan's splits and batch, per
+//     query its lists per split, one reduce round's lists, bits and outputs;
 //   pools (pools_impl: diversify, diversify_dpp): budget / bytes per row (the
 //     pool, its Gramian, the selection), at least one row;
 //   candidate lists (rank_candidates; cand_metrics_impl for
@@ -73,7 +76,8 @@ int check_rows(frecsys_ctx* c, const std::string& w, int32_t side, int32_t table
   } else if (n > ns) {
     return fail(c, FRECSYS_ERR_INVALID, w + "more rows than the side has");
   }
-  if (table != side && c->n[table] < 1) return fail(c, FRECSYS_ERR_INVALID, w + "no items");
+  if (table != side && c->n[table] < 1)
+    return fail(c, FRECSYS_ERR_INVALID, w + (table == FRECSYS_SIDE_USER ? "no users" : "no items"));
   return FRECSYS_OK;
 }
 
@@ -105,13 +109,6 @@ int check_cutoffs(frecsys_ctx* c, const std::string& w, const int32_t* k_list, i
     *k = std::max(*k, k_list[q]);
   }
   return FRECSYS_OK;
-}
-
-// Bytes the regions of a row batch may take: 256 MiB, or the knob (read per call).
-size_t workspace_budget() {
-  int64_t ws_mb = 256;
-  if (const char* v = getenv("FRECSYS_RECOMMEND_WS_MB")) ws_mb = std::max(1, atoi(v));
-  return (size_t)ws_mb << 20;
 }
 
 // The carver of c->d_rec.  take<T>(count) hands out the next 16-byte aligned
@@ -1308,6 +1305,91 @@ int frecsys_similar(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n
   const double dd = c->dim;
   add_work(c, "similar", 2.0 * (double)n * (double)m * dd,
            ((double)n + (cosine ? 2.0 : 1.0) * (double)m) * dd * 4.0 + (double)n * k * 8.0, n);
+  return FRECSYS_OK;
+}
+
+int frecsys_audience(frecsys_ctx* c, const int64_t* items, int64_t n_items, int32_t k,
+                     int32_t flags, const uint8_t* user_mask, int32_t* users, float* scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "audience: null context");
+  const std::string w = "audience: ";
+  int rc = check_query(c, w, FRECSYS_SIDE_USER, FRECSYS_SIDE_ITEM, &k, flags,
+                       FRECSYS_AUD_EXCLUDE_HISTORY);
+  if (rc) return rc;
+  if (n_items < 0 || (n_items > 0 && !users))
+    return fail(c, FRECSYS_ERR_INVALID, w + "bad arguments (null outputs)");
+  const bool exclude = (flags & FRECSYS_AUD_EXCLUDE_HISTORY) != 0;
+  if ((rc = check_rows(c, w, FRECSYS_SIDE_ITEM, FRECSYS_SIDE_USER, exclude, items, n_items)))
+    return rc;
+  const int64_t m = c->n[FRECSYS_SIDE_USER], n = n_items;
+  if (n == 0) return FRECSYS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  int dev_cus = 256;
+  (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  frecsys_audience_plan_t pl;
+  if ((rc = frecsys_audience_plan(c->dim, m, n, k, std::max(1, dev_cus), exclude ? 1 : 0, &pl)))
+    return fail(c, rc, w + "no plan for this shape");
+  c->rec_splits = pl.splits;
+  const int64_t nb = pl.rows_per_batch;
+  const std::vector<uint32_t> maskw = item_mask_words(m, user_mask);
+  if (pl.thin) {
+    // the thin-query kernel: per query of a batch its lists per split, what the
+    // first reduce round leaves, the history bits and the outputs
+    AudienceArgs a{};
+    a.X = c->emb[FRECSYS_SIDE_ITEM];
+    a.Y = c->emb[FRECSYS_SIDE_USER];
+    a.m = m;
+    a.Dp = c->Dp;
+    a.k = k;
+    a.splits = pl.splits;
+    a.row_ptr = exclude ? c->rp[FRECSYS_SIDE_ITEM] : nullptr;
+    a.col = exclude ? c->col[FRECSYS_SIDE_ITEM] : nullptr;
+    const size_t red = (size_t)audience_reduce_lists(pl.splits, k);
+    rc = Carver::run(c, [&](Carver& cv) {
+      a.cand = cv.take<unsigned long long>((size_t)nb * pl.splits * pl.slots);
+      a.counts = cv.take<int32_t>((size_t)nb * pl.splits);
+      a.red = cv.take_if<unsigned long long>(red > 0, (size_t)nb * red * k);
+      a.red_counts = cv.take_if<int32_t>(red > 0, (size_t)nb * red);
+      a.bitmap = cv.take_if<uint32_t>(exclude, (size_t)nb * maskw.size());
+      a.out_items = cv.take<int32_t>((size_t)nb * k);
+      a.out_scores = cv.take<float>((size_t)nb * k);
+      a.maskw = cv.take<uint32_t>(maskw.size());
+      a.qrows = cv.take_if<int64_t>(items != nullptr, (size_t)n);
+    });
+    if (rc) return rc;
+    HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+    if (items) HIP_TRY(c, to_device(c, a.qrows, items, (size_t)n));
+    for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per query batch
+      a.r0 = r0;
+      a.n = std::min(nb, n - r0);
+      ScopedTimer t(c, "audience");
+      HIP_TRY(c, launch_audience_thin(a, c->stream));
+      t.stop();
+      if ((rc = copy_lists(c, users, scores, k, r0, a.n, a.out_items, a.out_scores))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+  } else {
+    // frecsys_recommend's scan, the item rows as queries and the user table
+    // searched: the plan is scan_plan's arithmetic
+    const ScanPlan p{pl.splits, pl.slots, nb};
+    RecommendArgs a = scan_args(c, FRECSYS_SIDE_ITEM, FRECSYS_SIDE_USER, k, p.splits, exclude);
+    if ((rc = Carver::run(c, [&](Carver& cv) { carve_scan(cv, a, p, items != nullptr, n); })))
+      return rc;
+    HIP_TRY(c, to_device(c, a.maskw, maskw.data(), maskw.size()));
+    if (items) HIP_TRY(c, to_device(c, a.qrows, items, (size_t)n));
+    for (int64_t r0 = 0; r0 < n; r0 += nb) {  // one timed launch group per row batch
+      a.r0 = r0;
+      a.n = std::min(nb, n - r0);
+      ScopedTimer t(c, "audience");
+      HIP_TRY(c, launch_recommend(a, c->stream));
+      t.stop();
+      if ((rc = copy_lists(c, users, scores, k, r0, a.n, a.out_items, a.out_scores))) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  // scoring flops at the logical dim; bytes: the user table once per pass, the
+  // queries, the lists written
+  add_work(c, "audience", 2.0 * (double)n * (double)m * (double)c->dim,
+           ((double)pl.passes * (double)m + (double)n) * c->Dp * 4.0 + (double)n * k * 8.0, n);
   return FRECSYS_OK;
 }
 

@@ -722,4 +722,67 @@ int frecsys_metric_cvar(const float* values, int64_t n, const float* alphas, int
   return FRECSYS_OK;
 }
 
+// Queries up to which frecsys_audience takes the thin-query kernel when
+// FRECSYS_AUDIENCE_THIN_MAX is unset (the sweep it comes from).
+constexpr int64_t kAudienceThinMaxDefault = 4096;
+
+int frecsys_audience_plan(int32_t dim, int64_t n_users, int64_t n, int32_t k, int32_t cus,
+                          int32_t exclude, frecsys_audience_plan_t* out) {
+  const int Dp = padded_dim(dim);
+  if (Dp == 0 || n_users < 1 || n < 1 || k < 1 || k > 1024 || cus < 1 ||
+      (exclude != 0 && exclude != 1) || !out)
+    return fail(nullptr, FRECSYS_ERR_INVALID, "frecsys_audience_plan: bad arguments");
+  int64_t thin_max = kAudienceThinMaxDefault;
+  if (const char* v = getenv("FRECSYS_AUDIENCE_THIN_MAX")) thin_max = std::max<long long>(0, atoll(v));
+  int want_splits = 0;
+  if (const char* v = getenv("FRECSYS_RECOMMEND_SPLITS")) want_splits = std::max(0, atoi(v));
+  const int64_t m = n_users;
+  const size_t budget = workspace_budget();
+  const size_t bits = exclude ? (size_t)recommend_words(m) * 4 : 0;  // history bits per query
+  frecsys_audience_plan_t p{};
+  size_t per_row = 0;
+  int64_t nb = 0;
+  if (n <= thin_max) {
+    // about 4 workgroups per CU over the passes, one chunk per split at least;
+    // halved while one query's lists do not fit the budget
+    const int QT = audience_queries_per_pass();
+    p.thin = 1;
+    p.chunk_rows = audience_chunk_rows();
+    p.slots = audience_slots(k);
+    const int64_t chunks = (m + p.chunk_rows - 1) / p.chunk_rows, passes = (n + QT - 1) / QT;
+    int64_t splits = want_splits ? want_splits : (4 * (int64_t)cus + passes - 1) / passes;
+    splits = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(splits, chunks), 65535));
+    const auto bytes = [&](int64_t s) {
+      return (size_t)s * p.slots * 8 + (size_t)s * 4 +
+             (size_t)audience_reduce_lists((int)s, k) * ((size_t)k * 8 + 4) + (size_t)k * 8 + bits;
+    };
+    while (splits > 1 && bytes(splits) > budget) splits = (splits + 1) / 2;
+    p.splits = (int32_t)splits;
+    p.merge_rounds = audience_merge_rounds(p.splits, k);
+    per_row = bytes(splits);
+    nb = std::max<int64_t>(1, (int64_t)(budget / per_row));
+    p.queries_per_pass = (int32_t)std::min<int64_t>(QT, nb);
+    if (nb < n && nb >= QT) nb -= nb % QT;  // whole passes but in the last batch
+  } else {
+    // scan_plan's arithmetic (serve.hip) with the caller's CU count
+    const int max_splits = recommend_max_splits(k, m);
+    const int64_t row_blocks = (n + 63) / 64;
+    int64_t splits = std::min<int64_t>(max_splits, (2 * (int64_t)cus + row_blocks - 1) / row_blocks);
+    if (want_splits) splits = std::min(max_splits, want_splits);
+    p.splits = (int32_t)std::max<int64_t>(1, splits);
+    p.chunk_rows = 128;
+    p.slots = recommend_cap(k);
+    p.merge_rounds = 1;
+    per_row = (size_t)p.splits * p.slots * 8 + (size_t)p.splits * 4 + (size_t)k * 8 + bits;
+    nb = std::max<int64_t>(1, (int64_t)(budget / per_row));
+    p.queries_per_pass = (int32_t)std::min<int64_t>(64, nb);
+    if (nb < n && nb >= 64) nb &= ~(int64_t)63;  // whole 64-row blocks but in the last batch
+  }
+  p.passes = (int32_t)((n + p.queries_per_pass - 1) / p.queries_per_pass);
+  p.rows_per_batch = std::min(nb, n);
+  p.workspace_bytes = (int64_t)((size_t)p.rows_per_batch * per_row);
+  *out = p;
+  return FRECSYS_OK;
+}
+
 }  // extern "C"

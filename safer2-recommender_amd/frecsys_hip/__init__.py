@@ -20,6 +20,7 @@ import numpy as np
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
 REC_EXCLUDE_HISTORY = 1
 SIM_COSINE, SIM_KEEP_SELF = 1, 2
+AUD_EXCLUDE_HISTORY = 1
 DIV_RAW_SCORES = 2
 # the cut-offs and tail levels run_model evaluates (run_model.cc:97-100)
 EVAL_K_LIST = (5, 10, 20, 50, 100)
@@ -58,7 +59,8 @@ EXPORTS = (
     "frecsys_explain", "frecsys_csr_row_lengths", "frecsys_mmr_select", "frecsys_diversify",
     "frecsys_recommend_diverse", "frecsys_list_quality", "frecsys_exposure_summary",
     "frecsys_rank_quality", "frecsys_lists_quality", "frecsys_dpp_select",
-    "frecsys_diversify_dpp", "frecsys_recommend_dpp",
+    "frecsys_diversify_dpp", "frecsys_recommend_dpp", "frecsys_audience",
+    "frecsys_audience_plan",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -80,7 +82,7 @@ MODEL_EXPORTS = (
     "frecsys_model_diversify", "frecsys_model_evaluate_quality",
     "frecsys_model_evaluate_quality_fold_in", "frecsys_model_list_quality",
     "frecsys_model_recommend_dpp", "frecsys_model_recommend_dpp_fold_in",
-    "frecsys_model_diversify_dpp",
+    "frecsys_model_diversify_dpp", "frecsys_model_audience",
 )
 
 
@@ -214,6 +216,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_score_pairs": (ctypes.c_int, [P, I32, P, P, I64, P]),
         "frecsys_rank_candidates": (ctypes.c_int, [P, I32, P, I64, P, P, I32, I32, P, P, P]),
         "frecsys_similar": (ctypes.c_int, [P, I32, P, I64, I32, I32, P, P, P]),
+        "frecsys_audience": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
+        "frecsys_audience_plan": (ctypes.c_int, [I32, I64, I64, I32, I32, I32, P]),
         "frecsys_sample_negatives": (ctypes.c_int,
                                      [I64, P, P, I64, P, P, P, P, I32, ctypes.c_uint64, P, P]),
         "frecsys_rank_candidates_metrics": (ctypes.c_int,
@@ -278,6 +282,7 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
         "frecsys_model_rank_candidates": (ctypes.c_int, [P, P, I64, P, P, I32, I32, P, P, P]),
         "frecsys_model_similar_items": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
         "frecsys_model_similar_users": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
+        "frecsys_model_audience": (ctypes.c_int, [P, P, I64, I32, I32, P, P, P]),
         "frecsys_model_rank_candidates_fold_in": (ctypes.c_int,
                                                   [P, P, P, I64, P, P, I32, I32, P, P, P]),
         "frecsys_model_evaluate_candidates": (
@@ -380,6 +385,26 @@ def gram_plan(dim: int, n_rows: int, world: int = 1, rank: int = 0):
                                ctypes.byref(ng), ctypes.byref(lo), ctypes.byref(hi))
     _check_host(lib, rc)
     return int(rpl.value), int(nl.value), int(ng.value), int(lo.value), int(hi.value)
+
+
+class _AudiencePlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int32) for f in
+                ("thin", "queries_per_pass", "passes", "splits", "chunk_rows", "slots",
+                 "merge_rounds")] + [("rows_per_batch", ctypes.c_int64),
+                                     ("workspace_bytes", ctypes.c_int64)]
+
+
+def audience_plan(dim: int, n_users: int, n: int, k: int, cus: int = 256,
+                  exclude: bool = False) -> dict:
+    """Host-only: what Context.audience launches for n query items against
+    n_users users on a device of `cus` compute units -- the fields of
+    frecsys_audience_plan_t as a dict.  Reads FRECSYS_AUDIENCE_THIN_MAX,
+    FRECSYS_RECOMMEND_SPLITS and FRECSYS_RECOMMEND_WS_MB as the call does."""
+    lib = load_library()
+    pl = _AudiencePlan()
+    rc = lib.frecsys_audience_plan(dim, n_users, n, k, cus, 1 if exclude else 0, ctypes.byref(pl))
+    _check_host(lib, rc)
+    return {f: int(getattr(pl, f)) for f, _ in _AudiencePlan._fields_}
 
 
 def _ground_truth(gt_ptr, gt_items):
@@ -1221,6 +1246,28 @@ class Context:
                                              _ptr(ids), _ptr(scores)))
         return ids, scores
 
+    def audience(self, k: int, items=None, exclude_history: bool = True,
+                 mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(users int32 [n, k], scores float32 [n, k]): the k best users for
+        each query item (a row of the ITEM table), by score descending, user
+        id ascending -- frecsys_audience.  The score is recommend's for that
+        (user, item) pair, bit for bit.  items: item ids (any order, repeats
+        allowed; None = every item); exclude_history drops the users in the
+        item's row of the ITEM-side CSR; mask [users]: non-zero = candidate.
+        Slots beyond the eligible count hold id -1 and score -FLT_MAX."""
+        r = None if items is None else np.ascontiguousarray(items, dtype=np.int64).reshape(-1)
+        n = self.n[SIDE_ITEM] if r is None else len(r)
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_USER],), mk.shape
+        users = np.full((n, k) if k > 0 else (n, 0), -1, dtype=np.int32)
+        scores = np.zeros(users.shape, dtype=np.float32)
+        flags = AUD_EXCLUDE_HISTORY if exclude_history else 0
+        self._check(self.lib.frecsys_audience(self.h, _ptr(r), n, k, flags, _ptr(mk),
+                                              _ptr(users), _ptr(scores)))
+        return users, scores
+
     def pp_set_rating_index(self, side: int, rix: np.ndarray):
         r = np.ascontiguousarray(rix, dtype=np.int32)
         self._check(self.lib.frecsys_pp_set_rating_index(self.h, side, _ptr(r)))
@@ -1752,6 +1799,25 @@ class Model:
         frecsys_model_similar_users; user_mask [n_users]."""
         return self._similar(self.lib.frecsys_model_similar_users, self.n_users, users, k, metric,
                              include_self, user_mask)
+
+    def audience(self, items, k: int, exclude_seen: bool = True, user_mask=None):
+        """(users int32 [n, k], scores float32 [n, k]): the k best users for
+        each of the trained items `items` (rows of V), by score descending,
+        user id ascending -- frecsys_model_audience.  The scores are score()'s
+        bits; exclude_seen drops the users who have the item in the training
+        tuples; user_mask [n_users]: non-zero = candidate; -1 / -FLT_MAX
+        beyond the eligible count."""
+        r = np.ascontiguousarray(items, dtype=np.int64).reshape(-1)
+        mk = None
+        if user_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(user_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n_users,), mk.shape
+        users = np.full((len(r), k) if k > 0 else (len(r), 0), -1, dtype=np.int32)
+        scores = np.zeros(users.shape, dtype=np.float32)
+        self._check(self.lib.frecsys_model_audience(self.h, _ptr(r), len(r), k,
+                                                    1 if exclude_seen else 0, _ptr(mk),
+                                                    _ptr(users), _ptr(scores)))
+        return users, scores
 
     def rank_candidates_fold_in(self, hist_ptr, hist_items, cand_ptr, cand_items, k: int,
                                 exclude_seen: bool = True, item_mask=None):

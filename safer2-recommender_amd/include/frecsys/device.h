@@ -243,6 +243,10 @@ class DeviceContext {
                  int32_t* ids, float* scores) {
     return frecsys_similar(ctx_, side, rows, n, k, flags, mask, ids, scores);
   }
+  int TryAudience(const int64_t* items, int64_t n, int k, int flags, const uint8_t* mask,
+                  int32_t* users, float* scores) {
+    return frecsys_audience(ctx_, items, n, k, flags, mask, users, scores);
+  }
 
   // Recall@K / NDCG@K of the ranking Recommend would return with
   // k = max(k_list), computed on the device (frecsys_rank_metrics): recall,

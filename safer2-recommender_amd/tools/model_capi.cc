@@ -932,6 +932,32 @@ int frecsys_model_similar_users(frecsys_model* m, const int64_t* users, int64_t 
                        user_mask, ids, scores);
 }
 
+int frecsys_model_audience(frecsys_model* m, const int64_t* items, int64_t n, int32_t k,
+                           int32_t exclude_seen, const uint8_t* user_mask, int32_t* users,
+                           float* scores) {
+  const std::string w = "frecsys_model_audience: ";
+  if (!m || n < 0 || (n > 0 && !users)) return model_fail(FRECSYS_ERR_INVALID, w + "bad arguments");
+  if (exclude_seen)
+    if (int rc = needs_data(m, "frecsys_model_audience")) return rc;
+  DeviceContext& dev = frecsys::AsDeviceModel(m->rec.get())->device();
+  if (exclude_seen && n > 0) {
+    // the ITEM-side CSR, if no Train() has loaded it yet -- behind the checks
+    // of k and the item ids, so that a rejected call makes no device call
+    const int64_t n_items = dev.rows(DeviceContext::ITEM);
+    if (k < 1 || k > 1024) return model_fail(FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
+    if (!items && n > n_items)
+      return model_fail(FRECSYS_ERR_INVALID, w + "more rows than the side has");
+    for (int64_t i = 0; items && i < n; ++i)
+      if (items[i] < 0 || items[i] >= n_items)
+        return model_fail(FRECSYS_ERR_INVALID,
+                          w + "row id " + std::to_string(items[i]) + " out of range");
+    dev.LoadTraining(*m->train);
+  }
+  return context_status(dev, dev.TryAudience(items, n, k,
+                                             exclude_seen ? FRECSYS_AUD_EXCLUDE_HISTORY : 0,
+                                             user_mask, users, scores));
+}
+
 int frecsys_model_evaluate(frecsys_model* m, const int64_t* users, int64_t n,
                            const int64_t* gt_ptr, const int32_t* gt_items, const int32_t* k_list,
                            int32_t nk, const float* alpha_list, int32_t na, int32_t exclude_seen,
