@@ -14,6 +14,14 @@
 #define FRECSYS_SKIP(mask, bit) 0
 #endif
 
+// Split-bf16 SYRK: 1 reads a group's operand fragments from LDS while the
+// MFMAs of the group before it run (solve.hip); 0 keeps the read-then-multiply
+// loops, for a timed A/B (`make abvar ABDEF=-DFRECSYS_SYRK_PIPE=0`).  Compile
+// time only: the products, their operands and their order are the same.
+#ifndef FRECSYS_SYRK_PIPE
+#define FRECSYS_SYRK_PIPE 1
+#endif
+
 namespace frecsys_hip {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

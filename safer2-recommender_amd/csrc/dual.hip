@@ -215,6 +215,13 @@ __global__ void __launch_bounds__((DualCfg<TH, BF>::NTHR))
   constexpr bool RDS = BF;  // register-direct slabs
   constexpr int HP = C::HP, NT = C::NT, NW = C::NW, NTHR = C::NTHR, MT = C::MT;
   constexpr int SROW = C::SROW, NQ = C::NQ;
+  // fragments of the S product read one group ahead (FRECSYS_SYRK_PIPE; 3 or
+  // 6, 0: the read-then-multiply loop).  TH = 4 and 6 have the registers for
+  // three below their caps and their slab phase got shorter; TH = 7 and 8
+  // would use more VGPRs than before; TH = 3 and 5 sit at their 128-VGPR
+  // cap and were not timed
+  constexpr int PF = !(FRECSYS_SYRK_PIPE && BF) ? 0 : (TH == 4 || TH == 6) ? 3 : 0;
+  static_assert(PF == 0 || NW <= NT, "PF: every wave owns a first tile");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* tiles = smem;
   float* stage = smem;
@@ -415,7 +422,39 @@ __global__ void __launch_bounds__((DualCfg<TH, BF>::NTHR))
     }
     lds_barrier();
     if (!FRECSYS_SKIP(a.debug_skip, 1)) {
-      if constexpr (BF) {
+      if constexpr (BF && PF > 0) {
+        // the (tile, k-group) products of the slab in a software pipeline
+        // (solve.hip's chunk step): PF of group k + 1's six fragments are read
+        // before the MFMAs of group k -- in mfma_x6's order of first use a2,
+        // b0, a0 | b2, a1, b1 -- and the rest at the head of their own group.
+        // Per accumulator the same mfma_x6 sequence: the same bits.
+        const bf16x8* zb = reinterpret_cast<const bf16x8*>(zs);
+        auto frag = [&](int k, bool early, bf16x8 (&av)[3], bf16x8 (&bv)[3]) {
+          const int m = k >> 1, g = k & 1;
+          if (early) {
+            av[2] = zb[dgran<HP>(2, g, hi, aoff[m])];
+            bv[0] = zb[dgran<HP>(0, g, hi, boff[m])];
+            av[0] = zb[dgran<HP>(0, g, hi, aoff[m])];
+          }
+          if (early == (PF == 6)) {
+            bv[2] = zb[dgran<HP>(2, g, hi, boff[m])];
+            av[1] = zb[dgran<HP>(1, g, hi, aoff[m])];
+            bv[1] = zb[dgran<HP>(1, g, hi, boff[m])];
+          }
+        };
+        bf16x8 fa[2][3], fb[2][3];
+        frag(0, true, fa[0], fb[0]);  // every wave owns a first tile (NW <= NT)
+#pragma unroll
+        for (int k = 0; k < 2 * MT; ++k) {
+          if (valid[k >> 1]) {  // wave-uniform
+            if (PF < 6) frag(k, false, fa[k & 1], fb[k & 1]);
+            if (k + 1 < 2 * MT && valid[(k + 1) >> 1])
+              frag(k + 1, true, fa[(k + 1) & 1], fb[(k + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[k >> 1] = mfma_x6(fa[k & 1], fb[k & 1], acc[k >> 1]);
+          }
+        }
+      } else if constexpr (BF) {
         const bf16x8* zb = reinterpret_cast<const bf16x8*>(zs);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {

@@ -147,6 +147,9 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
   using C = TiledCfg<T, BF>;
   // SB: super-block tile ownership (sb_tile) for the split-bf16 SYRK at T = 8
   constexpr bool SB = BF && T == 8 && (kSyrkSB >= 2 || (PARTIAL && kSyrkSB >= 1));
+  // PIPE: the t % 8 chunk step with its operand reads one group ahead of the
+  // MFMAs (FRECSYS_SYRK_PIPE); T = 8 is the size the timed workloads run
+  constexpr bool PIPE = FRECSYS_SYRK_PIPE && BF && !SB && T == 8;
   constexpr int Dp = C::Dp, NT = C::NT, NW = C::NW, NTHR = C::NTHR;
   constexpr int MT = C::MT;
   constexpr int R = C::R, NQ = C::NQ, NSLOT = C::NSLOT;
@@ -305,12 +308,12 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
       bpart = live ? bpart + bsum : bpart;
     }
   };
-  auto write_bf = [&](int buf, const bf16x8 (&f)[2][3]) {
+  auto write_bf = [&](int buf, const bf16x8 (&f)[2][3], int hh0 = 0) {
     if constexpr (BF) {
       bf16x8* st = reinterpret_cast<bf16x8*>(stage) + buf * C::GRAN;
       if (bown) {
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
+        for (int hh = hh0; hh < 2; ++hh)
 #pragma unroll
           for (int p = 0; p < 3; ++p) st[bf_gran<Dp>(p, bg, hh, bc)] = f[hh][p];
       }
@@ -521,13 +524,15 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
       // slot stays valid; the values are never staged): a conditional load
       // block here made the waitcnt pass wait (vmcnt) for these fresh rows
       // before this step's scaling and MFMAs
-      load_bf(c + 2 < nchunks ? c + 2 : nchunks - 1, xnxt);
+      // (PIPE issues both below, behind the first common group's MFMAs)
+      auto gather_next = [&]() { load_bf(c + 2 < nchunks ? c + 2 : nchunks - 1, xnxt); };
+      if constexpr (!PIPE) gather_next();
       const bool live = c + 1 < nchunks;
       // chunk c+1's staging math is spread over the issue gaps of this
       // chunk's MFMAs: scaled values (and the rhs part) first, then two
       // 3-piece splits after each mfma_x6 of the tiles every wave has
       float xs[16];
-      scale_bf(c + 1, xcur, xs, live);
+      if constexpr (!PIPE) scale_bf(c + 1, xcur, xs, live);
       bf16x8 f[2][3];
       constexpr int SLOTS = (NT / NW) * 2 > 0 ? (NT / NW) * 2 : 1;
       constexpr int PER = (16 + SLOTS - 1) / SLOTS;
@@ -551,8 +556,15 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
 #pragma unroll
             for (int p = 0; p < 3; ++p) asm volatile("" : "+v"(f[hh][p]));
       };
-      const bf16x8* st = reinterpret_cast<const bf16x8*>(stage) + buf * C::GRAN;
-      if (SB && !FRECSYS_SKIP(a.debug_skip, 1)) {
+      // PIPE: the buffer's offset opaque, so that the fragment addresses are
+      // formed per step from it (one add per tile operand) -- as constants of
+      // the two-step unroll, those of buffer 1 lie past the 64 KiB the DS
+      // offset field reaches and took a register each (34) across the loop,
+      // the registers the second fragment set needs
+      int sbase = buf * C::GRAN;
+      if constexpr (PIPE) asm volatile("" : "+s"(sbase));
+      const bf16x8* st = reinterpret_cast<const bf16x8*>(stage) + sbase;
+      if (SB &&!FRECSYS_SKIP(a.debug_skip, 1)) {
         // the wave's column blocks' fragments, each feeding two or more
         // tiles (per-tile accumulation order as below: bit-identical)
         {
@@ -570,6 +582,64 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
               acc[m] = mfma_x6s(fr[P.pa[m]], fr[P.pb[m]], acc[m]);
               if (m < 4) split_slot(4 * g + m);
             }
+          }
+        }
+      } else if (PIPE && !FRECSYS_SKIP(a.debug_skip, 1)) {
+        // The (tile, k-group) products in a software pipeline: the six
+        // fragment reads of group k + 1 are issued before the MFMAs of group
+        // k, into the other of two fragment sets, so that only the step's
+        // first group waits a whole LDS round trip (it cannot be read before
+        // the barrier that ends the stores of its stage buffer).  Each acc[m]
+        // still takes mfma_x6s of k-group 0, then 1: the same bits.  The tile
+        // that only some waves own goes first -- its wave-uniform branch then
+        // ends in the reads of the first common group, and the common groups
+        // stay one basic block with the splits.
+        //   The step's other two LDS round trips -- the ring ids ahead of the
+        // row gathers, the scales ahead of the staging math -- used to stand
+        // in front of the first MFMA on all eight waves at once (they leave
+        // the barrier together, so no partner hides them); here they follow
+        // the first common group's MFMAs in the same basic block and are
+        // scheduled into its issue gaps.  Likewise the stage stores: f[0] is
+        // complete after slot SLOTS / 2 - 1 and goes out there, behind MFMAs,
+        // not with f[1] in front of the barrier (the other buffer is free all
+        // step; past the last chunk the stores land in a buffer nobody reads).
+        constexpr int FULL = NT / NW;
+        static_assert(!PIPE || (SLOTS == 2 * FULL && PER * SLOTS == 16 && 2 * Dp == NTHR),
+                      "PIPE: a slot per common group, every thread stages");
+        auto frag = [&](int m, int g, bf16x8 (&av)[3], bf16x8 (&bv)[3]) {
+#pragma unroll
+          for (int p = 0; p < 3; ++p) {
+            av[p] = st[bf_gran<Dp>(p, g, hi, aoff[m])];
+            bv[p] = st[bf_gran<Dp>(p, g, hi, boff[m])];
+          }
+        };
+        bf16x8 fa[2][3], fb[2][3];
+        if (MT > FULL && valid[MT - 1]) {
+          frag(MT - 1, 0, fa[0], fb[0]);
+          frag(MT - 1, 1, fa[1], fb[1]);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[MT - 1] = mfma_x6s(fa[0], fb[0], acc[MT - 1]);
+          frag(0, 0, fa[0], fb[0]);
+          __builtin_amdgcn_sched_barrier(0);
+          acc[MT - 1] = mfma_x6s(fa[1], fb[1], acc[MT - 1]);
+        } else {
+          frag(0, 0, fa[0], fb[0]);
+        }
+        bf16x8* so = reinterpret_cast<bf16x8*>(stage) + (C::GRAN - sbase);  // the other buffer
+#pragma unroll
+        for (int k = 0; k < 2 * FULL; ++k) {
+          if (k + 1 < 2 * FULL) frag((k + 1) >> 1, (k + 1) & 1, fa[(k + 1) & 1], fb[(k + 1) & 1]);
+          // the reads above stay above the MFMAs below
+          __builtin_amdgcn_sched_barrier(0);
+          acc[k >> 1] = mfma_x6s(fa[k & 1], fb[k & 1], acc[k >> 1]);
+          if (k == 0) {
+            gather_next();
+            scale_bf(c + 1, xcur, xs, live);
+          }
+          split_slot(k);
+          if (k == FULL - 1) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) so[bf_gran<Dp>(p, bg, 0, bc)] = f[0][p];
           }
         }
       } else if (!FRECSYS_SKIP(a.debug_skip, 1)) {
@@ -592,10 +662,15 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
         }
         if constexpr (NT / NW == 0) split_slot(0);
       } else {
+        if constexpr (PIPE) {
+          gather_next();
+          scale_bf(c + 1, xcur, xs, live);
+        }
 #pragma unroll
         for (int k = 0; k < SLOTS; ++k) split_slot(k);
       }
-      if (live) write_bf(buf ^ 1, f);
+      // (PIPE: the k-half 0 pieces went out behind the MFMAs)
+      if (live) write_bf(buf ^ 1, f, PIPE && !FRECSYS_SKIP(a.debug_skip, 1) ? 1 : 0);
       if (tid < R && c >= 1 && c + 2 < nchunks) {  // chunk c+2's sa / bw
         const int64_t k = k0 + (int64_t)(c + 2) * R + tid;
         float sa = 0.0f, bw = 0.0f;
@@ -621,9 +696,22 @@ __global__ void __launch_bounds__((TiledCfg<T, BF>::NTHR))
     // SB: one copy of the chunk loop per ownership pattern (the tiles'
     // accumulators then merge once, after the loop, not at every step)
     auto loop = [&](auto pc) __attribute__((always_inline)) {
-      for (int c = 0; c < nchunks; c += 2) {
-        step(c, xa, xb, pc);
-        if (c + 1 < nchunks) step(c + 1, xb, xa, pc);
+      if constexpr (PIPE) {
+        // pairs, then the odd chunk: with the second step of a pair under a
+        // condition, the waitcnt pass saw a path from one even step straight
+        // into the next and made the fragment and ring reads that reuse the
+        // gather's registers wait (vmcnt) for loads just issued
+        int c = 0;
+        for (; c + 1 < nchunks; c += 2) {
+          step(c, xa, xb, pc);
+          step(c + 1, xb, xa, pc);
+        }
+        if (c < nchunks) step(c, xa, xb, pc);
+      } else {
+        for (int c = 0; c < nchunks; c += 2) {
+          step(c, xa, xb, pc);
+          if (c + 1 < nchunks) step(c + 1, xb, xa, pc);
+        }
       }
       store_tiles();
     };
