@@ -19,9 +19,9 @@ CXXFLAGS := -O3 -std=c++17 -Wall -I include -I $(PKG)/include -pthread
 
 HIP_SRCS := $(CSRC)/solve.hip $(CSRC)/dual.hip $(CSRC)/spectral.hip $(CSRC)/gramian.hip \
             $(CSRC)/loss.hip $(CSRC)/wide.hip $(CSRC)/wide_syrk.hip $(CSRC)/topk.hip $(CSRC)/pp.hip \
-            $(CSRC)/recommend.hip $(CSRC)/audience.hip $(CSRC)/similar.hip $(CSRC)/rerank.hip $(CSRC)/metrics.hip $(CSRC)/sampled.hip $(CSRC)/positions.hip $(CSRC)/cg.hip $(CSRC)/explain.hip $(CSRC)/diversify.hip $(CSRC)/dpp.hip $(CSRC)/quality.hip $(CSRC)/capi.hip $(CSRC)/serve.hip $(CSRC)/serve_host.hip $(CSRC)/train.hip
+            $(CSRC)/recommend.hip $(CSRC)/audience.hip $(CSRC)/similar.hip $(CSRC)/rerank.hip $(CSRC)/metrics.hip $(CSRC)/sampled.hip $(CSRC)/positions.hip $(CSRC)/cg.hip $(CSRC)/explain.hip $(CSRC)/diversify.hip $(CSRC)/dpp.hip $(CSRC)/quality.hip $(CSRC)/twostage.hip $(CSRC)/capi.hip $(CSRC)/serve.hip $(CSRC)/serve_host.hip $(CSRC)/train.hip
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJ)/%.o,$(HIP_SRCS))
-HDRS     := $(CSRC)/kernels.h $(CSRC)/common.h $(CSRC)/chol.h $(CSRC)/chol_sched.h $(CSRC)/wide.h $(CSRC)/device_buf.h $(CSRC)/ctx.h $(CSRC)/serve.h \
+HDRS     := $(CSRC)/kernels.h $(CSRC)/common.h $(CSRC)/chol.h $(CSRC)/chol_sched.h $(CSRC)/wide.h $(CSRC)/device_buf.h $(CSRC)/ctx.h $(CSRC)/serve.h $(CSRC)/scan_words.h \
             include/frecsys_hip.h $(PKG)/include/frecsys/parallel.h
 
 .PHONY: all lib oracle run_model model_dump model_lib clean ablation

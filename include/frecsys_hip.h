@@ -349,6 +349,71 @@ int frecsys_eval_topk(frecsys_ctx* ctx, int32_t k, int32_t* topk);
 int frecsys_recommend(frecsys_ctx* ctx, int32_t side, const int64_t* rows, int64_t n_rows,
                       int32_t k, int32_t flags, const uint8_t* item_mask, int32_t* items,
                       float* scores);
+/* Two-stage recommend: a bf16 retrieval scan picks a pool per row, the pool is
+ * re-scored exactly, and a per-row certificate says when the list is
+ * frecsys_recommend's bit for bit.  side, rows, item_mask, the exclude flag,
+ * the eligibility and the outputs' layout are frecsys_recommend's;
+ * 1 <= k <= pool <= 1024, pool = 0: min(1024, max(64, 4 k)).
+ *
+ * Notation: the query row r has the fp32 row x, item j the fp32 row y_j, Dp =
+ * frecsys_padded_dim(dim), Dh = max(16, Dp) the width of the bf16 images.
+ * Rounding: v^ = v rounded to bf16 by round-to-nearest-even; a NaN stays a NaN
+ * (quiet); the exponent range is fp32's, so a finite value near FLT_MAX may
+ * round to +-inf.  frecsys_bf16_round (host) is the definition -- it returns
+ * the rounded values widened back to fp32 -- and the device conversion equals
+ * it bit for bit.
+ * Stage 1: s^_rj = the fp32 accumulator of v_mfma_f32_32x32x16_bf16 over x^_r
+ * and y^_j from +0, the k-steps (16 columns each) in ascending order for every
+ * (r, j), whatever the tile, split, batch or grid.  Row r's pool: its `pool`
+ * best eligible items by (s^ descending, id ascending), built by
+ * frecsys_recommend's candidate words, threshold rule and merge.  s^ is
+ * defined to the bit against itself only, and bounded against float64 (below).
+ * Stage 2: every pool item is re-scored as s_rj = frecsys_recommend's chain,
+ * fmaf(y[c], x[c], acc), c ascending from +0; the list is the k best of the
+ * pool by (s descending, id ascending), -1 / -FLT_MAX beyond the pool's fill.
+ * Certificate: ||.|| = the Euclidean norm of the fp32 row, the squares summed
+ * and the root taken in double on the device; N = max_j ||y_j|| over all item
+ * rows; c(Dp) = 2^-7 + 2^-16 + 3 Dp 2^-23; B_r = c(Dp) ||x_r|| N in double
+ * ((c ||x_r||) N; frecsys_two_stage_bound is the same arithmetic on the host).
+ * (bf16 has unit roundoff u = 2^-8, so |x^y^ - xy| <= (2u + u^2)|xy|;
+ * Cauchy-Schwarz bounds sum |x_c y_c| by ||x|| ||y||; frecsys_recommend's own
+ * chain errs by about Dp 2^-24 sum |xy|; the matrix core's accumulation is
+ * assumed to err by at most Dp 2^-23 sum |x^y^| -- together about 1.5 Dp 2^-23,
+ * and the 3 is a 2x margin on the accumulation terms.)  certified[r] = 1 when
+ *   (a) the pool is not full: every eligible item was re-scored; or
+ *   (b) (double)s_k > (double)s^_P + B_r, strictly: s_k the k-th exact score of
+ *       the list, s^_P the smallest approximate score of the full pool, and
+ *       s_k, s^_P, B_r all finite.
+ * Then every item outside the pool has s^ <= s^_P, so an exact score <= s^_P +
+ * B_r < s_k, and the list is frecsys_recommend's bit for bit, ties included.
+ * A row is never certified when the item table or its own query row holds a
+ * value with 0 < |v^| < 2^-126 (the matrix core may flush subnormals).  For
+ * every row, certified or not, every listed score is >= s*_k - 2 E_r, s*_k the
+ * exact k-th best eligible score and E_r the row's largest |s^ - s|.
+ * With FRECSYS_TS_EXACT in flags the uncertified rows are re-run through
+ * frecsys_recommend's scan and their byte becomes 2: the outputs are then
+ * frecsys_recommend's bits for EVERY row.
+ * certified (host [n_rows], or NULL): 0 / 1 / 2.  pool_items / pool_scores
+ * (host [n_rows * pool], or NULL): stage 1's pools as the scan left them, -1 /
+ * -FLT_MAX beyond the fill.  The item image (items * Dh * 2 bytes) is rebuilt
+ * by every call and released by frecsys_release_workspaces.  Rank-local.
+ * FRECSYS_ERR_INVALID, before any device work: a bad side, k or pool, an
+ * unknown flag, a row id out of range, null items with n_rows > 0, the exclude
+ * flag without a CSR, a table without embeddings; n_rows == 0 returns
+ * FRECSYS_OK.  Timer keys "two_stage.convert", "two_stage.scan",
+ * "two_stage.select", "two_stage.fallback"; frecsys_work("two_stage.scan"):
+ * 2 rows items d flops, (rows + items) Dh 2 + 8 rows pool bytes; counters
+ * "two_stage_certified", "two_stage_fallback_rows". */
+#define FRECSYS_TS_EXACT 2
+int frecsys_recommend_two_stage(frecsys_ctx* ctx, int32_t side, const int64_t* rows,
+                                int64_t n_rows, int32_t k, int32_t pool, int32_t flags,
+                                const uint8_t* item_mask, int32_t* items, float* scores,
+                                uint8_t* certified, int32_t* pool_items, float* pool_scores);
+/* Host only, no context: out[i] = in[i] rounded to bf16 (see above), as fp32. */
+int frecsys_bf16_round(const float* in, int64_t n, float* out);
+/* Host only: B = c(Dp) * query_norm * item_norm_max in double, Dp =
+ * frecsys_padded_dim(dim); NaN for an unsupported dim. */
+double frecsys_two_stage_bound(int32_t dim, double query_norm, double item_norm_max);
 /* Recall@K and NDCG@K of ranked lists on the host: the reference's
  * RankMetrics (recommender.h:152-182), once for every caller.  No context and
  * no HIP call: works on a machine without a GPU, like frecsys_partition.
@@ -1105,7 +1170,10 @@ int frecsys_snapshot_residual(frecsys_ctx* ctx, int32_t side, double* sq);
  *                     instead of the pre-split table -- results unchanged;
  *   "cg_iterations"   sum of the CG iteration counts of every entity solved
  *                     by frecsys_solve_side_cg;
- *   "cg_unconverged"  entities whose CG stopped at max_iterations.
+ *   "cg_unconverged"  entities whose CG stopped at max_iterations;
+ *   "two_stage_certified", "two_stage_fallback_rows"  rows of
+ *                     frecsys_recommend_two_stage that stage 2 certified, and
+ *                     rows it re-ran through the exact scan.
  * And two values that are no sums: "recommend_splits", the item splits the
  * last frecsys_recommend call ran with; "live_device_bytes", the device
  * memory every context of the process holds now in buffers of its own

@@ -111,6 +111,23 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                     const int32_t* hist_items, int64_t n, int32_t k,
                                     int32_t exclude_seen, const uint8_t* item_mask,
                                     int32_t* items, float* scores);
+/* The two calls above by retrieve-then-rank (frecsys_recommend_two_stage,
+ * frecsys_hip.h, where the bf16 scan, the pool, the exact re-scoring and the
+ * certificate are defined): 1 <= k <= pool <= 1024, pool = 0: the default;
+ * exact != 0 re-runs the rows that stage 2 cannot certify through
+ * frecsys_recommend's scan, so that items / scores are
+ * frecsys_model_recommend's bit for bit on every row; certified: host [n] or
+ * NULL, 0 / 1 / 2 per row.  The errors are frecsys_model_recommend's and
+ * frecsys_recommend_two_stage's. */
+int frecsys_model_recommend_two_stage(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                      int32_t pool, int32_t exact, int32_t exclude_seen,
+                                      const uint8_t* item_mask, int32_t* items, float* scores,
+                                      uint8_t* certified);
+int frecsys_model_recommend_two_stage_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                              const int32_t* hist_items, int64_t n, int32_t k,
+                                              int32_t pool, int32_t exact, int32_t exclude_seen,
+                                              const uint8_t* item_mask, int32_t* items,
+                                              float* scores, uint8_t* certified);
 /* Diversified lists for n trained users: greedy maximal-marginal-relevance
  * (MMR) re-ranking of each user's `pool` best items down to k
  * (frecsys_recommend_diverse, frecsys_hip.h, where the pool, the relevance,

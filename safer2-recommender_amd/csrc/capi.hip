@@ -1290,6 +1290,9 @@ int frecsys_release_workspaces(frecsys_ctx* c) {
   HIP_TRY(c, c->d_rec.release());
   HIP_TRY(c, c->d_sim_inv.release());
   HIP_TRY(c, c->d_samp_ids.release());
+  HIP_TRY(c, c->d_ts_img.release());
+  HIP_TRY(c, c->d_ts_norm.release());
+  HIP_TRY(c, c->d_ts_stats.release());
   return FRECSYS_OK;
 }
 
@@ -1382,6 +1385,14 @@ int frecsys_counter(frecsys_ctx* c, const char* what, int64_t* value) {
   }
   if (!strcmp(what, "recommend_splits")) {
     *value = c->rec_splits;
+    return FRECSYS_OK;
+  }
+  if (!strcmp(what, "two_stage_certified")) {
+    *value = c->ts_certified;
+    return FRECSYS_OK;
+  }
+  if (!strcmp(what, "two_stage_fallback_rows")) {
+    *value = c->ts_fallback_rows;
     return FRECSYS_OK;
   }
   if (!strcmp(what, "live_device_bytes")) {  // of the process, not of this context

@@ -128,6 +128,13 @@ struct frecsys_ctx {
   DevBuf<char> d_rec;            // the ranking calls' workspace (serve.hip carves it per call)
   DevBuf<float> d_sim_inv;       // frecsys_similar: inverse row norms of the side searched
   DevBuf<int32_t> d_samp_ids;    // frecsys_sampled_metrics: the candidate ids of a row batch
+  // frecsys_recommend_two_stage: the item table's bf16 image, its row norms
+  // and {largest norm bits, subnormal count}, rebuilt by every call; the rows
+  // certified and the rows re-run exactly so far (frecsys_counter)
+  DevBuf<char> d_ts_img;
+  DevBuf<double> d_ts_norm;
+  DevBuf<unsigned long long> d_ts_stats;
+  int64_t ts_certified = 0, ts_fallback_rows = 0;
   int64_t rec_splits = 0;       // item splits of the last call (frecsys_counter "recommend_splits")
   // conjugate-gradient path (frecsys_solve_side_cg): i of the last CG call
   // per row of each side (device scratch + host copy; -1: not solved here),

@@ -425,6 +425,65 @@ hipError_t launch_history_bits(const int64_t* row_ptr, const int32_t* col, const
 // a.n, a.k, a.splits, a.cand, a.counts, a.out_items, a.out_scores only.
 hipError_t launch_recommend_merge(const RecommendArgs& a, int64_t cap, hipStream_t s);
 
+// Two-stage recommend (twostage.hip; the definitions are
+// frecsys_recommend_two_stage's in include/frecsys_hip.h).
+//
+// bf16 of an fp32 bit pattern by round-to-nearest-even, as its 16 bits; a NaN
+// stays a NaN (quiet, its upper payload kept).  The host's frecsys_bf16_round
+// and every device conversion are this one function.
+__host__ __device__ inline uint32_t bf16_round_bits(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+// 0 < |v| < 2^-126 for the bf16 pattern h: outside the certificate's proof.
+__host__ __device__ inline bool bf16_subnormal(uint32_t h) {
+  return (h & 0x7f80u) == 0u && (h & 0x7fu) != 0u;
+}
+// c(Dp) of the certificate's bound B = c(Dp) ||x|| max ||y||.
+__host__ __device__ inline double two_stage_c(int Dp) {
+  return 0x1p-7 + 0x1p-16 + 3.0 * (double)Dp * 0x1p-23;
+}
+// Width of the bf16 images: the MFMA's K is 16.
+inline int two_stage_dh(int Dp) { return Dp < 16 ? 16 : Dp; }
+// The item image: per 128-item tile and 16-B granule (8 consecutive columns)
+// the tile's 128 items side by side -- image[(tile * Dh / 8 + g) * 128 + j] --
+// so that a k-slab of a tile is one contiguous run, copied into LDS as it
+// lies and read there as MFMA fragments.  Pad columns and the rows beyond m
+// are zero.
+size_t two_stage_image_bytes(int64_t m, int Dp);
+// ts_convert_kernel: the image of the m rows of T, norms[r] = ||T[r]|| (the
+// squares accumulated and the root taken in double), stats[0] = the bits of
+// the largest norm (a NaN norm counts as the largest), stats[1] = the values
+// whose bf16 is subnormal.
+hipError_t launch_two_stage_convert(const float* T, int64_t m, int Dp, void* image, double* norms,
+                                    unsigned long long* stats, hipStream_t s);
+// ts_scan_kernel in rec_scan_kernel's place: RecommendArgs as for
+// launch_recommend (a.k the pool), a.Y unused -- the items are read from
+// `image`.  The score of (row, item) is the fp32 accumulator of
+// v_mfma_f32_32x32x16_bf16 over the bf16 of both rows from +0, the k-steps in
+// ascending order: the same in every tile, split, batch and grid.
+hipError_t launch_two_stage_scan(const RecommendArgs& a, const void* image, hipStream_t s);
+// ts_select_kernel: row i of the batch re-scores the filled slots of its pool
+// (pool_items[i * pool ..), -1 beyond the fill; ids distinct) by the chain
+// acc = fmaf(y[c], x[c], acc), c ascending from +0 -- recommend.hip's score,
+// bit for bit -- and lists the k best by (score descending, id ascending),
+// -1 / -FLT_MAX beyond the fill; certified[i] as the header defines it.
+struct TwoStageSelectArgs {
+  const float* X;            // query table, ld = Dp
+  const int64_t* qrows;      // table row of every query row of the call, or nullptr
+  int64_t r0, n;             // this batch: query rows r0 .. r0 + n - 1
+  const float* Y;            // items, ld = Dp
+  int Dp;
+  int k, pool;               // 1 <= k <= pool <= 1024
+  const int32_t* pool_items;   // [n][pool], sorted by the approximate score
+  const float* pool_scores;    // [n][pool]
+  const unsigned long long* stats;  // launch_two_stage_convert's, of the item table
+  int32_t* out_items;        // [n][k]
+  float* out_scores;         // [n][k]
+  uint8_t* certified;        // [n]
+};
+hipError_t launch_two_stage_select(const TwoStageSelectArgs& a, hipStream_t s);
+
 // The thin-query scan (audience.hip): the k best eligible rows of a table Y
 // for each of a few query rows of X, by recommend.hip's word (score_key(score)
 // << 32 | ~id) and its score, the chain acc = fmaf(X[q][c], Y[u][c], acc), c

@@ -55,6 +55,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "scan_words.h"
 
 namespace frecsys_hip {
 
@@ -80,38 +81,7 @@ __global__ void __launch_bounds__(64)
   }
 }
 
-// The `nn` (<= CAP) candidates of buffer g sorted (descending) by one wave in
-// its LDS slice sb; the best min(nn, k) written back.  Returns that count;
-// *kth = the k-th best word when nn >= k.
-template <int CAP>
-__device__ __forceinline__ int compact_row(u64* __restrict__ g, u64* sb, int nn, int k, int lane,
-                                           u64* kth) {
-  if (nn > CAP) nn = CAP;  // never: a row enters a tile with at most CAP - IT candidates
-  int P = 64;
-  while (P < nn) P <<= 1;
-  for (int i = lane; i < P; i += 64) sb[i] = i < nn ? g[i] : 0ull;
-  wave_lds_sync();
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int p = lane; p < (P >> 1); p += 64) {
-        const int i = ((p & ~(stride - 1)) << 1) | (p & (stride - 1));
-        const int j = i | stride;
-        const bool up = (i & size) == 0;
-        const u64 a = sb[i], b = sb[j];
-        if (up ? a < b : a > b) {
-          sb[i] = b;
-          sb[j] = a;
-        }
-      }
-      wave_lds_sync();
-    }
-  }
-  const int keep = nn < k ? nn : k;
-  for (int i = lane; i < keep; i += 64) g[i] = sb[i];
-  if (nn >= k) *kth = sb[k - 1];
-  wave_lds_sync();
-  return keep;
-}
+// (compact_row, the cut of a candidate buffer to its best k: scan_words.h)
 
 // The staging tiles and the four waves' sort slices share one LDS region: a
 // wave sorts only between the barrier that ends a tile's appends (every MFMA

@@ -2,8 +2,8 @@
 // (include/frecsys_hip.h) that take a context and drive the device.  The
 // context-free host calls are serve_host.hip's; serve.h holds what the two
 // units share.  No kernels here: recommend.hip, similar.hip, rerank.hip,
-// sampled.hip, metrics.hip, positions.hip, explain.hip, diversify.hip, dpp.hip
-// and quality.hip hold them (kernels.h).
+// sampled.hip, metrics.hip, positions.hip, explain.hip, diversify.hip, dpp.hip,
+// quality.hip and twostage.hip hold them (kernels.h).
 //
 // Workspace.  Every call carves the one byte buffer c->d_rec into 16-byte
 // aligned typed regions (Carver): first the regions of a row batch (candidate
@@ -15,7 +15,8 @@
 // Drivers.  A call runs its rows in batches, one timed launch group each, and
 // synchronises after each batch's copy-back:
 //   scan (scan_impl with one object behind the scan: recommend,
-//     rank_metrics, recommend_diverse, recommend_dpp, rank_quality; similar
+//     rank_metrics, recommend_diverse, recommend_dpp, rank_quality, and
+//     recommend_two_stage with the bf16 scan in the fp32 scan's place; similar
 //     and audience above its thin-query limit, with loops of their own):
 //     budget / bytes per row, the scan's and what is behind it, in whole 64-row
 //     blocks, with the item splits of scan_plan; a selection forms its Gramians
@@ -293,6 +294,83 @@ struct ListsOut : BehindScan {
   int run(frecsys_ctx* c, const int32_t* lists, const float* list_scores, int64_t r0,
           int64_t cnt) override {
     return copy_lists(c, items, scores, k, r0, cnt, lists, list_scores);
+  }
+};
+
+// frecsys_recommend_two_stage behind its bf16 scan: the item table's image is
+// built before the first batch (ts_convert_kernel, per call: the tables change
+// with every solve), the scan leaves a batch's pools where `lists` / `scores`
+// point, ts_select_kernel re-scores them there and the lists, the certificate
+// bytes and (if asked for) the pools go to the host.  Per row of a batch: the
+// list and its byte; per call: the stage's own copy of the query row ids.
+struct TwoStageStage final : BehindScan {
+  const int64_t* rows;
+  const int64_t n;
+  int32_t* items;
+  float* scores;
+  std::vector<uint8_t> cert;  // [n], on the host for the fallback; sized behind the checks
+  int32_t* pool_items;
+  float* pool_scores;
+  TwoStageSelectArgs sa{};
+  int64_t* d_rows = nullptr;
+
+  TwoStageStage(const frecsys_ctx* c, int side, const int64_t* r, int64_t n_rows, int k, int pool,
+                int32_t* i, float* s, int32_t* pi, float* ps)
+      : rows(r), n(n_rows), items(i), scores(s), pool_items(pi), pool_scores(ps) {
+    sa.X = c->emb[side];
+    sa.Y = c->emb[1];
+    sa.Dp = c->Dp;
+    sa.k = k;
+    sa.pool = pool;
+  }
+  size_t scan_bytes() const override { return (size_t)sa.k * 8 + 1; }
+  void scan_carve(Carver& cv, int64_t nb) override {
+    sa.out_items = cv.take<int32_t>((size_t)nb * sa.k);
+    sa.out_scores = cv.take<float>((size_t)nb * sa.k);
+    sa.certified = cv.take<uint8_t>((size_t)nb);
+    d_rows = cv.take_if<int64_t>(rows != nullptr, (size_t)n);
+  }
+  // the image lies outside the per-row budget, in buffers of its own
+  int scan_upload(frecsys_ctx* c) override {
+    const int64_t m = c->n[1];
+    cert.assign((size_t)n, 0);  // n is within the side's rows here
+    int rc = ensure(c, c->d_ts_img, two_stage_image_bytes(m, c->Dp));
+    if (!rc) rc = ensure(c, c->d_ts_norm, (size_t)m);
+    if (!rc) rc = ensure(c, c->d_ts_stats, 2);
+    if (rc) return rc;
+    if (rows) HIP_TRY(c, to_device(c, d_rows, rows, (size_t)n));
+    sa.qrows = d_rows;
+    sa.stats = c->d_ts_stats;
+    ScopedTimer t(c, "two_stage.convert");
+    HIP_TRY(c, launch_two_stage_convert(c->emb[1], m, c->Dp, c->d_ts_img, c->d_ts_norm,
+                                        c->d_ts_stats, c->stream));
+    t.stop();
+    return FRECSYS_OK;
+  }
+  int run(frecsys_ctx* c, const int32_t* lists, const float* list_scores, int64_t r0,
+          int64_t cnt) override {
+    sa.r0 = r0;
+    sa.n = cnt;
+    sa.pool_items = lists;
+    sa.pool_scores = list_scores;
+    ScopedTimer t(c, "two_stage.select");
+    HIP_TRY(c, launch_two_stage_select(sa, c->stream));
+    t.stop();
+    HIP_TRY(c, to_host(c, cert.data() + r0, sa.certified, (size_t)cnt));
+    if (pool_items) HIP_TRY(c, to_host(c, pool_items + r0 * sa.pool, lists, (size_t)cnt * sa.pool));
+    if (pool_scores)
+      HIP_TRY(c, to_host(c, pool_scores + r0 * sa.pool, list_scores, (size_t)cnt * sa.pool));
+    return copy_lists(c, items, scores, sa.k, r0, cnt, sa.out_items, sa.out_scores);
+  }
+  // convert: a square-and-add per value; the table read, the image and the
+  // norms written.  select: every slot booked as filled; flops at the logical
+  // dim; one padded item row per slot, the pool read, the list written
+  void book(frecsys_ctx* c) const override {
+    const double m = (double)c->n[1], P = sa.pool;
+    add_work(c, "two_stage.convert", 2.0 * m * c->dim,
+             m * c->Dp * 4.0 + (double)two_stage_image_bytes(c->n[1], c->Dp) + m * 8.0, c->n[1]);
+    add_work(c, "two_stage.select", 2.0 * (double)n * P * c->dim,
+             (double)n * (P * (c->Dp * 4.0 + 8.0) + sa.k * 8.0 + 1.0), n);
   }
 };
 
@@ -691,6 +769,11 @@ struct ScanCall {
   int32_t k;
   int32_t flags;
   const uint8_t* item_mask;
+  // the timer and work key of the scan, and the scan's launcher: false,
+  // rec_scan_kernel (every call but frecsys_recommend_two_stage); true, the
+  // bf16 scan of the image in c->d_ts_img, whose bytes are the images'
+  const char* key = "recommend";
+  bool bf16 = false;
 };
 // The checks, before any device call (null_outputs is the caller's verdict on
 // its own outputs, gt or nullptr a ground truth), the return for zero rows,
@@ -730,18 +813,24 @@ int scan_impl(frecsys_ctx* c, const ScanCall& q, bool null_outputs, const Metric
   for (int64_t r0 = 0; r0 < n; r0 += p.nb) {  // one timed launch group per row batch
     a.r0 = r0;
     a.n = std::min(p.nb, n - r0);
-    ScopedTimer t(c, "recommend");
-    HIP_TRY(c, launch_recommend(a, c->stream));
+    ScopedTimer t(c, q.key);
+    HIP_TRY(c, q.bf16 ? launch_two_stage_scan(a, c->d_ts_img, c->stream)
+                      : launch_recommend(a, c->stream));
     t.mark();
     if (r0 == 0 && (rc = behind.scan_overlap(c))) return rc;
     t.finish();
     if ((rc = behind.run(c, a.out_items, a.out_scores, r0, a.n))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  // scoring flops at the logical dim; bytes: both tables read once, lists written
+  // scoring flops at the logical dim; bytes: both tables read once (the bf16
+  // scan: their images, 2 B a column of the padded width), lists written
   const double dd = c->dim;
-  add_work(c, "recommend", 2.0 * (double)n * (double)m * dd,
-           ((double)n + (double)m) * dd * 4.0 + (double)n * q.k * 8.0, n);
+  if (q.bf16)
+    add_work(c, q.key, 2.0 * (double)n * (double)m * dd,
+             ((double)n + (double)m) * two_stage_dh(c->Dp) * 2.0 + (double)n * q.k * 8.0, n);
+  else
+    add_work(c, q.key, 2.0 * (double)n * (double)m * dd,
+             ((double)n + (double)m) * dd * 4.0 + (double)n * q.k * 8.0, n);
   return behind.finish(c);
 }
 
@@ -983,6 +1072,55 @@ int frecsys_recommend(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t
   ListsOut out(items, scores, k);
   return scan_impl(c, {"recommend: ", side, rows, n_rows, k, flags, item_mask}, !items, nullptr,
                    out);
+}
+
+int frecsys_recommend_two_stage(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,
+                                int32_t k, int32_t pool, int32_t flags, const uint8_t* item_mask,
+                                int32_t* items, float* scores, uint8_t* certified,
+                                int32_t* pool_items, float* pool_scores) {
+  if (!c) return fail(c, FRECSYS_ERR_INVALID, "recommend_two_stage: null context");
+  const std::string w = "recommend_two_stage: ";
+  if (pool == 0) {  // the default: the 4 k of the re-ranking calls, at least 64
+    if (k < 1 || k > 1024) return fail(c, FRECSYS_ERR_INVALID, w + "k must be in [1, 1024]");
+    pool = std::min(1024, std::max(64, 4 * k));
+  }
+  if (int rc = check_diversify(c, w, k, pool, 0.0f, flags,
+                               FRECSYS_REC_EXCLUDE_HISTORY | FRECSYS_TS_EXACT))
+    return rc;
+  const int32_t scan_flags = flags & FRECSYS_REC_EXCLUDE_HISTORY;
+  TwoStageStage st(c, side, rows, n_rows, k, pool, items, scores, pool_items, pool_scores);
+  ScanCall q{w, side, rows, n_rows, pool, scan_flags, item_mask};
+  q.key = "two_stage.scan";
+  q.bf16 = true;
+  int rc = scan_impl(c, q, !items, nullptr, st);
+  if (rc || n_rows == 0) return rc;
+  // the rows stage 2 could not certify: re-run by the exact scan, if asked for
+  std::vector<int64_t> again, at;
+  for (int64_t i = 0; i < n_rows; ++i) {
+    if (st.cert[(size_t)i]) {
+      ++c->ts_certified;
+    } else if (flags & FRECSYS_TS_EXACT) {
+      again.push_back(rows ? rows[i] : i);
+      at.push_back(i);
+      st.cert[(size_t)i] = 2;
+    }
+  }
+  if (!again.empty()) {
+    const size_t na = again.size(), kk = (size_t)k;
+    std::vector<int32_t> fi(na * kk);
+    std::vector<float> fs(scores ? na * kk : 0);
+    ListsOut out(fi.data(), scores ? fs.data() : nullptr, k);
+    ScanCall fq{w, side, again.data(), (int64_t)na, k, scan_flags, item_mask};
+    fq.key = "two_stage.fallback";
+    if ((rc = scan_impl(c, fq, false, nullptr, out))) return rc;
+    for (size_t j = 0; j < na; ++j) {
+      std::memcpy(items + (size_t)at[j] * kk, fi.data() + j * kk, kk * sizeof(int32_t));
+      if (scores) std::memcpy(scores + (size_t)at[j] * kk, fs.data() + j * kk, kk * sizeof(float));
+    }
+    c->ts_fallback_rows += (int64_t)na;
+  }
+  if (certified) std::memcpy(certified, st.cert.data(), (size_t)n_rows);
+  return FRECSYS_OK;
 }
 
 int frecsys_rank_metrics(frecsys_ctx* c, int32_t side, const int64_t* rows, int64_t n_rows,

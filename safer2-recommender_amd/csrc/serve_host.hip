@@ -785,4 +785,23 @@ int frecsys_audience_plan(int32_t dim, int64_t n_users, int64_t n, int32_t k, in
   return FRECSYS_OK;
 }
 
+int frecsys_bf16_round(const float* in, int64_t n, float* out) {
+  if (n < 0 || (n > 0 && (!in || !out)))
+    return fail(nullptr, FRECSYS_ERR_INVALID, "frecsys_bf16_round: bad arguments");
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    std::memcpy(&u, in + i, 4);
+    u = bf16_round_bits(u) << 16;
+    std::memcpy(out + i, &u, 4);
+  }
+  return FRECSYS_OK;
+}
+
+double frecsys_two_stage_bound(int32_t dim, double query_norm, double item_norm_max) {
+#pragma clang fp contract(off)
+  const int Dp = padded_dim(dim);
+  if (Dp == 0) return std::nan("");
+  return two_stage_c(Dp) * query_norm * item_norm_max;
+}
+
 }  // extern "C"

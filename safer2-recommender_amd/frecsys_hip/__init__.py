@@ -19,6 +19,7 @@ import numpy as np
 
 SIDE_USER, SIDE_ITEM, SIDE_EVAL = 0, 1, 2
 REC_EXCLUDE_HISTORY = 1
+TS_EXACT = 2
 SIM_COSINE, SIM_KEEP_SELF = 1, 2
 AUD_EXCLUDE_HISTORY = 1
 DIV_RAW_SCORES = 2
@@ -60,7 +61,8 @@ EXPORTS = (
     "frecsys_recommend_diverse", "frecsys_list_quality", "frecsys_exposure_summary",
     "frecsys_rank_quality", "frecsys_lists_quality", "frecsys_dpp_select",
     "frecsys_diversify_dpp", "frecsys_recommend_dpp", "frecsys_audience",
-    "frecsys_audience_plan",
+    "frecsys_audience_plan", "frecsys_recommend_two_stage", "frecsys_bf16_round",
+    "frecsys_two_stage_bound",
 )
 
 # Every symbol include/frecsys_model.h declares.
@@ -83,6 +85,7 @@ MODEL_EXPORTS = (
     "frecsys_model_evaluate_quality_fold_in", "frecsys_model_list_quality",
     "frecsys_model_recommend_dpp", "frecsys_model_recommend_dpp_fold_in",
     "frecsys_model_diversify_dpp", "frecsys_model_audience",
+    "frecsys_model_recommend_two_stage", "frecsys_model_recommend_two_stage_fold_in",
 )
 
 
@@ -243,6 +246,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "frecsys_diversify_dpp": (ctypes.c_int, [P, P, P, I64, I32, I32, F, F, I32, P, P, P]),
         "frecsys_recommend_dpp": (ctypes.c_int,
                                   [P, I32, P, I64, I32, I32, F, F, I32, P, P, P, P]),
+        "frecsys_recommend_two_stage": (ctypes.c_int,
+                                        [P, I32, P, I64, I32, I32, I32, P, P, P, P, P, P]),
+        "frecsys_bf16_round": (ctypes.c_int, [P, I64, P]),
+        "frecsys_two_stage_bound": (ctypes.c_double, [I32, ctypes.c_double, ctypes.c_double]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -325,6 +332,10 @@ def load_model_library(path: str = MODEL_LIB_PATH) -> ctypes.CDLL:
             ctypes.c_int, [P, P, P, I64, I32, I32, F, F, I32, I32, P, P, P, P]),
         "frecsys_model_diversify_dpp": (ctypes.c_int,
                                         [P, P, P, I64, I32, I32, F, F, I32, P, P, P]),
+        "frecsys_model_recommend_two_stage": (ctypes.c_int,
+                                              [P, P, I64, I32, I32, I32, I32, P, P, P, P]),
+        "frecsys_model_recommend_two_stage_fold_in": (
+            ctypes.c_int, [P, P, P, I64, I32, I32, I32, I32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -499,6 +510,29 @@ def exposure_summary(exposure, item_mask=None) -> dict:
 def default_pool(k: int) -> int:
     """The pool the diversified calls draw k items from when none is given."""
     return min(1024, max(k, 4 * k))
+
+
+def bf16_round(values) -> np.ndarray:
+    """float32 array of the same shape: every value rounded to bf16 by
+    round-to-nearest-even and widened back, a NaN staying a NaN -- on the host
+    (frecsys_bf16_round: the rounding of recommend_two_stage's stage 1, bit for
+    bit; no GPU needed)."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty_like(v)
+    _check_host(lib, lib.frecsys_bf16_round(_ptr(v), v.size, _ptr(out)))
+    return out
+
+
+def two_stage_bound(dim: int, query_norm: float, item_norm_max: float) -> float:
+    """B = c(Dp) * query_norm * item_norm_max of recommend_two_stage's
+    certificate, in double on the host (frecsys_two_stage_bound)."""
+    return float(load_library().frecsys_two_stage_bound(dim, query_norm, item_norm_max))
+
+
+def default_two_stage_pool(k: int) -> int:
+    """The pool recommend_two_stage retrieves when none is given."""
+    return min(1024, max(64, 4 * k))
 
 
 def _pools(lists, scores):
@@ -903,6 +937,37 @@ class Context:
                                                REC_EXCLUDE_HISTORY if exclude_history else 0,
                                                _ptr(mk), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def recommend_two_stage(self, side: int, k: int, pool: Optional[int] = None, rows=None,
+                            exclude_history: bool = True, item_mask=None, exact: bool = True,
+                            return_pool: bool = False):
+        """(items int32 [n, k], scores float32 [n, k], certified uint8 [n][,
+        pool_items int32 [n, pool], pool_scores float32 [n, pool]]):
+        retrieve-then-rank (frecsys_recommend_two_stage).  A bf16 scan on the
+        matrix cores picks each row's `pool` best eligible items (default
+        default_two_stage_pool(k)), the pool is re-scored by recommend's exact
+        chain, and certified[r] = 1 where an error bound proves the list to be
+        recommend(side, k, ...)'s bit for bit.  exact re-runs the rows that are
+        not certified through recommend's scan (certified[r] = 2), so every row
+        carries recommend's bits; without it such a row holds the k best of
+        its pool.  rows, exclude_history, item_mask as for recommend."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = self.n[side] if r is None else len(r)
+        mk = None
+        if item_mask is not None:
+            mk = np.ascontiguousarray(np.asarray(item_mask) != 0, dtype=np.uint8)
+            assert mk.shape == (self.n[SIDE_ITEM],), mk.shape
+        p = default_two_stage_pool(k) if pool is None else pool
+        items = np.full((n, k) if k > 0 else (n, 0), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        cert = np.zeros(n, dtype=np.uint8)
+        pi = np.full((n, max(p, 0)), -1, dtype=np.int32) if return_pool else None
+        ps = np.zeros(pi.shape, dtype=np.float32) if return_pool else None
+        flags = (REC_EXCLUDE_HISTORY if exclude_history else 0) | (TS_EXACT if exact else 0)
+        self._check(self.lib.frecsys_recommend_two_stage(
+            self.h, side, _ptr(r), n, k, p, flags, _ptr(mk), _ptr(items), _ptr(scores),
+            _ptr(cert), _ptr(pi), _ptr(ps)))
+        return (items, scores, cert, pi, ps) if return_pool else (items, scores, cert)
 
     def recommend_diverse(self, side: int, k: int, pool: Optional[int] = None, lam: float = 0.7,
                           rows=None, raw_scores: bool = False, exclude_history: bool = True,
@@ -1530,6 +1595,34 @@ class Model:
         in the EVAL side of the model's context."""
         return self._recommend(*self._head(hist=(hist_ptr, hist_items)), k, exclude_seen,
                                item_mask)
+
+    def _recommend_two_stage(self, head, n, k, pool, exact, exclude_seen, item_mask):
+        mk = self._mask(item_mask)
+        items = np.full((n, max(k, 0)), -1, dtype=np.int32)
+        scores = np.zeros(items.shape, dtype=np.float32)
+        cert = np.zeros(n, dtype=np.uint8)
+        self._call("recommend_two_stage", head, n, k, 0 if pool is None else pool,
+                   int(bool(exact)), int(bool(exclude_seen)), _ptr(mk), _ptr(items), _ptr(scores),
+                   _ptr(cert))
+        return items, scores, cert
+
+    def recommend_two_stage(self, users, k: int, pool: Optional[int] = None, exact: bool = True,
+                            exclude_seen: bool = True, item_mask=None):
+        """(items int32 [n, k], scores float32 [n, k], certified uint8 [n]) for
+        trained users (frecsys_model_recommend_two_stage): recommend(users, k)
+        by a bf16 retrieval scan and an exact re-scoring of each row's pool
+        (Context.recommend_two_stage).  certified: 1 = proven equal to
+        recommend's list, 2 = re-run exactly (exact), 0 = neither."""
+        return self._recommend_two_stage(*self._head(users), k, pool, exact, exclude_seen,
+                                         item_mask)
+
+    def recommend_two_stage_fold_in(self, hist_ptr, hist_items, k: int,
+                                    pool: Optional[int] = None, exact: bool = True,
+                                    exclude_seen: bool = True, item_mask=None):
+        """The same for unseen users given by their histories, as
+        recommend_fold_in (frecsys_model_recommend_two_stage_fold_in)."""
+        return self._recommend_two_stage(*self._head(hist=(hist_ptr, hist_items)), k, pool, exact,
+                                         exclude_seen, item_mask)
 
     def _recommend_diverse(self, head, n, k, pool, lam, raw_scores, exclude_history, item_mask,
                            return_mmr):

@@ -108,6 +108,16 @@ class DeviceModel : public Recommender {
                            exclude_seen ? FRECSYS_REC_EXCLUDE_HISTORY : 0, mask);
   }
 
+  // Two-stage lists (frecsys_recommend_two_stage): a bf16 retrieval scan, the
+  // pool re-scored exactly, certified[i] = 1 where the list is Recommend's bit
+  // for bit (2: re-run exactly, with FRECSYS_TS_EXACT in flags).  Rows, mask
+  // and outputs as for RecommendDiverse; certified: host [n] or nullptr.
+  int RecommendTwoStage(int side, const int64_t* rows, int64_t n, int k, int pool, int flags,
+                        const uint8_t* mask, int32_t* items, float* scores, uint8_t* certified) {
+    return frecsys_recommend_two_stage(dev_->raw(), side, rows, n, k, pool, flags, mask, items,
+                                       scores, certified, nullptr, nullptr);
+  }
+
   // Diversified lists (frecsys_recommend_diverse): the greedy MMR selection of
   // k from the `pool` best items of each row of `side` (USER: trained users;
   // EVAL: the rows a FoldIn left there), against the model's item table.

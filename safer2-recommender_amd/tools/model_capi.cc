@@ -551,6 +551,26 @@ int recommend(frecsys_model* m, const std::string& w, const Query& q, int32_t k,
                                                       items, scores));
 }
 
+// As recommend: the fold-in form checks k, the pool (0: the default) and the
+// outputs before the projection, the trained form leaves them to the context.
+int recommend_two_stage(frecsys_model* m, const std::string& w, const Query& q, int32_t k,
+                        int32_t pool, int32_t exact, int32_t exclude_seen,
+                        const uint8_t* item_mask, int32_t* items, float* scores,
+                        uint8_t* certified) {
+  Rows r;
+  const auto own = [&](int64_t) -> std::string {
+    if (!q.fold_in) return "";
+    const std::string e = k_items_error(k, q.n, items);
+    if (!e.empty()) return e;
+    return pool != 0 && (pool < k || pool > 1024) ? "pool must be 0 or in [k, 1024]" : "";
+  };
+  if (int rc = open_query(m, w, q, exclude_seen, own, &r)) return answered(rc);
+  return context_status(
+      r.dev(), r.dm->RecommendTwoStage(r.side, r.ids, q.n, k, pool,
+                                       exclude_flag(exclude_seen) | (exact ? FRECSYS_TS_EXACT : 0),
+                                       item_mask, items, scores, certified));
+}
+
 int rank_candidates(frecsys_model* m, const std::string& w, const Query& q,
                     const int64_t* cand_ptr, const int32_t* cand_items, int32_t k,
                     int32_t exclude_seen, const uint8_t* item_mask, int32_t* items,
@@ -874,6 +894,24 @@ int frecsys_model_recommend_fold_in(frecsys_model* m, const int64_t* hist_ptr,
                                     int32_t* items, float* scores) {
   return recommend(m, "frecsys_model_recommend_fold_in: ", unseen(hist_ptr, hist_items, n), k,
                    exclude_seen, item_mask, items, scores);
+}
+
+int frecsys_model_recommend_two_stage(frecsys_model* m, const int64_t* users, int64_t n, int32_t k,
+                                      int32_t pool, int32_t exact, int32_t exclude_seen,
+                                      const uint8_t* item_mask, int32_t* items, float* scores,
+                                      uint8_t* certified) {
+  return recommend_two_stage(m, "frecsys_model_recommend_two_stage: ", trained(users, n), k, pool,
+                             exact, exclude_seen, item_mask, items, scores, certified);
+}
+
+int frecsys_model_recommend_two_stage_fold_in(frecsys_model* m, const int64_t* hist_ptr,
+                                              const int32_t* hist_items, int64_t n, int32_t k,
+                                              int32_t pool, int32_t exact, int32_t exclude_seen,
+                                              const uint8_t* item_mask, int32_t* items,
+                                              float* scores, uint8_t* certified) {
+  return recommend_two_stage(m, "frecsys_model_recommend_two_stage_fold_in: ",
+                             unseen(hist_ptr, hist_items, n), k, pool, exact, exclude_seen,
+                             item_mask, items, scores, certified);
 }
 
 int frecsys_model_score(frecsys_model* m, const int64_t* users, const int32_t* items, int64_t n,
